@@ -11,7 +11,14 @@ Independent pairs shard across ranks with no data-path collective ("scaling": "w
 processes its own batch of --batch pairs); the only RCCL traffic is the one-time broadcast of the rig's
 remap tables and the end-of-run reduction of timings / checksums.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step and the whole-step
+roofline that follows from them).  --full adds everything else the benchmark measures or checks: the per-kernel table
+from a few profiled single-stream steps, the in-run rocprofv3 counters (--no-pmc), the secondary measurements in
+"also" (--no-also), the CPU baseline (--no-cpu-baseline) and, with N ranks, the table broadcast + get_depth agreement
+check in "rccl".  --dump-outputs DIR writes the int16 disparities of the last timed step as float32 DIR/disparity.npy
+(a seeded sample of whole pairs when the batch is larger than 64 MB as float32; DIR/pair_index.npy says which).
 
 With --gpus N > 1 and no RANK in the environment the script launches itself under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); it exits non-zero with
@@ -77,12 +84,19 @@ def parse(argv=None):
                     help="sgbm = 5-path MODE_SGBM (the reference's call), hh = 8-path MODE_HH")
     ap.add_argument("--path", type=int, default=0, help="aggregation path: 0 auto, 1 scans, 2 band passes, 3 concurrent")
     ap.add_argument("--cost", type=int, default=0, help="cost-volume kernels: 0 auto (fused), 1 fused k_cost, 2 k_hsum + k_vsum")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements (other mode, gray, PCIe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-kernel table, in-run counters, the secondary "
+                         "measurements, the CPU baseline and the multi-rank agreement check (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the disparities of the last timed step as float32 DIR/disparity.npy (at most 64 MB: a "
+                         "seeded sample of whole pairs beyond that, indices in DIR/pair_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true",
+                    help="with --full: skip the secondary measurements (other mode, gray, PCIe)")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="strips in the CPU baseline sample (0 = two per thread)")
     ap.add_argument("--lib", default="", help="measurement only: load this build of libcalibrating_amd.so (A/B kernels)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the in-run rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ counters of one step in a child "
+                    help="with --full: skip the in-run rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ counters of one step in a child "
                          "process); roofline.traffic / valu_frac then come from the committed profiles/ summaries")
     ap.add_argument("--pmc-budget-s", type=float, default=240.0, help="wall-time budget of the in-run counter passes")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -94,7 +108,10 @@ def parse(argv=None):
                          "(tests/test_parallel_cpu.py).  The line it prints is marked \"data\": \"stub\" and is not a measurement")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget-s", type=float, default=25.0, help="time budget of the CPU baseline's thread sweep")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 PMC_SETS = (("FETCH_SIZE", ["FETCH_SIZE"]), ("WRITE_SIZE", ["WRITE_SIZE"]),
@@ -592,6 +609,145 @@ def config_c5(ca, synthetic, dev, streams, nb=128):
     return r
 
 
+def kernel_roofline(a, nb, world, stub, stage_ms, prof_steps, gpu_ms_step, b_alg, V):
+    """--full: the per-kernel table (hipEvent times of the profiled single-stream steps), the counters (in-run
+    rocprofv3 passes, or the committed profiles/ summaries) and the step's VALU / HBM floors -> the roofline keys
+    after gpu_ms_per_step."""
+    import torch
+    table = stage_table(V, a.width * a.height, a.channels, a.mode)
+    kernel_ms_step = sum(stage_ms.values()) / prof_steps   # one batch alone on the GPU
+    # HBM traffic per kernel from the committed PMC profile of the same kernels (separate rocprofv3 --pmc
+    # passes, 2*FETCH_SIZE + WRITE_SIZE per the gfx950 correction); null when no profile matches this workload
+    suffix = "_hh" if a.mode == "hh" else ""
+    # (rNN_pmc_traffic[_hh][_b<pairs per launch>].json; the one taken at this run's pairs per launch is preferred)
+    pmc_rel = _latest_profile("pmc_traffic%s*.json" % suffix, nb, exclude=None if suffix else "_hh")
+    pmc_other = _latest_profile("pmc_traffic%s.json" % suffix)
+    sq_rel = _latest_profile("pmc_sq%s.json" % suffix)
+    pmc = sq = None
+    pmc_note = "committed profile (--no-pmc)" if a.no_pmc else None
+    if world == 1 and not stub and not a.no_pmc:
+        # counters of THIS run's kernels, taken now (the timed region is over; its buffers are still allocated,
+        # the child needs its own ~1.3 GB per pair)
+        torch.cuda.empty_cache()
+        inrun, why = pmc_in_run(a, nb, a.pmc_budget_s)
+        if inrun:
+            pmc = sq = inrun
+            pmc_rel = sq_rel = "in-run: " + inrun["command"]
+            pmc_other = None
+        else:
+            pmc_note = "committed profile (in-run counters unavailable: %s)" % why
+    if pmc is None and a.channels == 3 and (a.width, a.height, a.disparities, a.block) == (1920, 1080, 128, 5):
+        pmc = json.load(open(os.path.join(ROOT, pmc_rel))) if pmc_rel else None
+        sq = json.load(open(os.path.join(ROOT, sq_rel))) if sq_rel else None
+    mix_rel, mix = valu_class_mix()
+
+    def pmc_bytes_per_pair(keys):
+        if not pmc:
+            return None
+        hit = [v["hbm_bytes_per_pair"] for k, v in pmc["kernels"].items()
+               if all(s in k for s in keys) and "hbm_bytes_per_pair" in v]
+        return hit[0] if len(hit) == 1 else None
+
+    def sq_counters(keys):
+        """(SQ_INSTS_VALU wave-instructions per pair, fraction of wave cycles spent in s_waitcnt / s_barrier) from the
+        committed SQ counter profile of the same kernel."""
+        if not sq:
+            return None, None
+        hit = [v for k, v in sq["kernels"].items() if all(s_ in k for s_ in keys)]
+        if len(hit) != 1 or not hit[0].get("SQ_INSTS_VALU"):
+            return None, None
+        return hit[0]["SQ_INSTS_VALU"] / sq["pairs_per_launch"], hit[0].get("derived", {}).get("wait_any_frac")
+
+    kernels = {}
+    for st, ms_sum in stage_ms.items():
+        ms = ms_sum / prof_steps
+        if st not in table or ms < 0.02:  # (an empty stage bracket still measures a few microseconds)
+            continue
+        name, per_pair, keys = table[st]
+        tr = pmc_bytes_per_pair(keys)
+        ach = per_pair * nb / (ms * 1e-3) / 1e9
+        kernels[st] = {"kernel": name, "avg_ms_per_launch": ms, "algorithmic_bytes_per_launch": float(per_pair * nb),
+                       "achieved": ach, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                       "traffic": (tr * nb) if tr is not None else None}
+        vi, waitf = sq_counters(keys)
+        if vi is not None:
+            # VALU issue roofline: one (packed-form) wave-instruction per CU and cycle; the instruction count is a
+            # property of the kernel (counted once, committed), the duration is this run's.  A kernel that reaches
+            # neither 0.8 of that nor 0.6 of the HBM peak is bound by its dependency chain (barrier per step, waits):
+            # `wave_wait_frac` = share of wave cycles in s_waitcnt / s_barrier
+            vf = vi * nb / (N_CUS * CLOCK_HZ) / (ms * 1e-3)
+            hf = ach / HBM_PEAK_GBS
+            # the kernel's own issue floor: its instructions at the measured rates of their two classes (the plain
+            # 32-bit forms issue at ~1.55 per cycle and CU, packed / DPP / three-operand forms at ~0.9)
+            shape = ("k_cost<%d, %d," % (a.channels, a.block),) if st == "cost" else \
+                ("k_band<16, %d," % ((a.disparities + 31) // 32),) if st in ("scan", "scan_last") else ()
+            ff, fs = next((m for k, m in mix.items() if all(s_ in k for s_ in keys + shape)), (0.0, 1.0))
+            floor_ms = vi * nb * (ff / RATE_FAST + fs / RATE_SLOW) / (N_CUS * CLOCK_HZ) * 1e3
+            kernels[st].update(valu_wave_insts_per_launch=vi * nb, valu_frac=vf, wave_wait_frac=waitf,
+                               valu_plain_class_frac=ff, valu_floor_ms=floor_ms,
+                               hbm_floor_ms=(tr * nb / (HBM_PEAK_GBS * 1e9) * 1e3) if tr is not None else None,
+                               bound="valu" if floor_ms >= 0.8 * ms else "hbm" if hf >= 0.6 else "latency")
+    dom = max(kernels, key=lambda k: kernels[k]["avg_ms_per_launch"]) if kernels else None
+    # whole-step traffic = every kernel of the committed PMC profile (incl. the small init / check kernels)
+    traffic_total = sum(v.get("hbm_bytes_per_pair", 0.0) for v in pmc["kernels"].values()) * nb if pmc else None
+    # the step's two floors: every VALU instruction of its kernels at the issue rate of its class, and every HBM byte
+    # the counters saw at the 8 TB/s peak -- what the step would take if one of the two were the only limit
+    floors = [k.get("valu_floor_ms") for k in kernels.values()]
+    valu_floor_ms = sum(f for f in floors if f is not None) if any(f is not None for f in floors) else None
+    hbm_floor_ms = traffic_total / (HBM_PEAK_GBS * 1e9) * 1e3 if traffic_total else None
+    # the same ratio from the profile taken at another number of pairs per launch, when it differs by more than 2 %
+    other_ratio = None
+    if pmc and pmc_other and pmc_other != pmc_rel:
+        po = json.load(open(os.path.join(ROOT, pmc_other)))
+        ro = sum(v["hbm_bytes_per_pair"] for v in po["kernels"].values()) / b_alg
+        if abs(ro / (traffic_total / (b_alg * nb)) - 1) > 0.02:
+            other_ratio = {"profile": pmc_other, "pairs_per_launch": po.get("pairs_per_launch"), "traffic_ratio": ro}
+    return {
+        "kernel_ms_per_step": kernel_ms_step,
+        "traffic": traffic_total,
+        "traffic_ratio": (traffic_total / (b_alg * nb)) if traffic_total else None,
+        "traffic_source": (pmc_rel + " (bytes per pair per launch x pairs per launch; taken at %s pairs per "
+                                     "launch)" % pmc.get("pairs_per_launch")) if pmc else None,
+        "counters": "in-run" if (pmc and str(pmc_rel).startswith("in-run")) else pmc_note,
+        # what the step would take if VALU issue / HBM bytes were its only limit, next to what it took
+        "valu_floor_ms": valu_floor_ms, "hbm_floor_ms": hbm_floor_ms,
+        "frac_of_valu_floor": (valu_floor_ms / gpu_ms_step) if valu_floor_ms else None,
+        "frac_of_hbm_floor": (hbm_floor_ms / gpu_ms_step) if hbm_floor_ms else None,
+        "valu_class_mix_source": mix_rel,
+        "traffic_ratio_other_profile": other_ratio,
+        "valu_source": (sq_rel + " (SQ_INSTS_VALU per pair x pairs per launch / (%d CUs x %.1f GHz) / this run's "
+                                 "kernel time)" % (N_CUS, CLOCK_HZ / 1e9)) if sq else None,
+        "dominant_kernel": dict(kernels[dom], stage=dom) if dom else None,
+        "kernels": kernels,
+    }
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes of .npy data in all
+
+
+def dump_outputs(d, out, max_bytes=DUMP_BYTES, seed=0):
+    """--dump-outputs: ``out`` (n, H, W) int16, the disparities compute() handed back in the last timed step, as float32
+    ``d/disparity.npy`` (exact: every int16 is a float32) and the pair indices it holds as float64 ``d/pair_index.npy``.
+    When the whole batch does not fit ``max_bytes``, a sample of whole pairs drawn with a fixed seed (the same pairs on
+    every run with the same arguments); when not even one pair fits, a seeded sample of pixels of the flattened batch,
+    whose flat indices go to ``d/flat_index.npy`` instead."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    n, H, W = out.shape
+    rng = np.random.default_rng(seed)
+    k = (max_bytes - 8 * n) // (4 * H * W)
+    if k >= 1:
+        idx = np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+        sel = out[torch.from_numpy(idx).to(out.device)]
+        np.save(os.path.join(d, "pair_index.npy"), idx.astype(np.float64))
+    else:
+        m = max_bytes // (4 + 8)
+        idx = np.unique(rng.integers(0, out.numel(), size=m))
+        sel = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+        np.save(os.path.join(d, "flat_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "disparity.npy"), sel.to(torch.float32).cpu().numpy())
+
+
 class StubMatcher:
     """--stub-compute: stands in for StereoSGBM where there is no GPU.  compute() writes a deterministic function of
     its inputs (so the checksum of checksums depends on every rank's shard) and does no stereo matching."""
@@ -713,26 +869,33 @@ def main():
         streams.append(None if stub else torch.cuda.Stream(device=dev))
     left, right, out, matcher = lefts[0], rights[0], outs[0], matchers[0]
 
-    # (1) kernel characterisation: a few steps on ONE stream with the library's hipEvents around every kernel
-    matcher.set_profiling(True)
-    kprof = max(1, min(a.steps, 5))
-    dt1, stage_ms = gpu_steps(matcher, left, right, out, kprof, a.warmup, sync=sync)
-    matcher.set_profiling(False)
-    prof_steps = kprof
+    # (1) kernel characterisation (--full): a few steps on ONE stream with the library's hipEvents around every kernel
+    stage_ms, prof_steps = {}, 0
+    if a.full:
+        matcher.set_profiling(True)
+        kprof = max(1, min(a.steps, 5))
+        dt1, stage_ms = gpu_steps(matcher, left, right, out, kprof, a.warmup, sync=sync)
+        matcher.set_profiling(False)
+        prof_steps = kprof
     # (2) the timed region: exactly --steps steps, `nfl` batches in flight, barrier + synchronize on both sides
     dt = pipelined_steps(matchers, streams, lefts, rights, outs, a.steps, a.warmup, distributed, sync=sync)
     for m in matchers:
         m.status()  # raises if a device-side bounded wait timed out
+    if a.dump_outputs and rank == 0:
+        # step k (warm-up steps counted) ran on set k % nfl: the last timed step is k = warmup + steps - 1
+        dump_outputs(a.dump_outputs, outs[(a.warmup + a.steps - 1) % nfl])
     checksum = sum(int(o.to(torch.int64).sum().item()) for o in outs)
     agg = aggregate(nb * a.steps, dt, checksum, dev, distributed)
     value = agg["total_pairs"] / agg["seconds"]
-    single_stream = nb * kprof / dt1
     del matchers[1:], lefts[1:], rights[1:], outs[1:], m, l, r  # (the loop variables hold the last set alive)
     if not stub:
         torch.cuda.empty_cache()  # (the host-link rate measured below drops when much more HBM is allocated)
 
     rccl = None
     if distributed:
+        rccl = dict(backend="gloo (CPU stub)" if stub else "nccl (RCCL)", world_size=world,
+                    per_rank=[dict(pairs=p, seconds=s, disparity_checksum=c) for p, s, c in agg["per_rank"]])
+    if distributed and a.full:
         # one-time table broadcast (rank 0 owns the rig), installed into every rank's Stereo; then every rank runs
         # the full get_depth on the SAME two pairs through the broadcast tables and the ranks compare checksums
         t0 = time.perf_counter()
@@ -758,18 +921,16 @@ def main():
                                 synthetic.scene_pair(77, a.width, a.height, 3)]).to(dev)
             res = stereo.get_depth_batch(imgs[:1].repeat(2, 1, 1, 1), imgs[1:].repeat(2, 1, 1, 1))
             dsum = int(torch.nan_to_num(res["unrectify_depth"]).mul(1e4).round().to(torch.int64).sum().item())
-        rccl = dict(backend="gloo (CPU stub)" if stub else "nccl (RCCL)", world_size=world,
-                    table_bytes=int(sum(t.numel() * t.element_size() for t in tables.values())),
-                    broadcast_s=t_bcast, get_depth_checksum=dsum, ranks_agree=bool(ranks_agree(dsum, dev)),
-                    per_rank=[dict(pairs=p, seconds=s, disparity_checksum=c) for p, s, c in agg["per_rank"]])
+        rccl.update(table_bytes=int(sum(t.numel() * t.element_size() for t in tables.values())),
+                    broadcast_s=t_bcast, get_depth_checksum=dsum, ranks_agree=bool(ranks_agree(dsum, dev)))
         del stereo, tables, res, imgs
 
     also = {}
-    if rank == 0 and world == 1 and not a.no_also and not stub:
+    if rank == 0 and world == 1 and a.full and not a.no_also and not stub:
         k2 = max(3, min(a.steps, 10))
         also["note"] = ("figures named *_pairs_per_s are measured with ONE batch in flight on one stream; get_depth_batch, "
                         "c4 and c5 say how they were run")
-        also["single_stream_pairs_per_s"] = single_stream
+        also["single_stream_pairs_per_s"] = nb * prof_steps / dt1
         if os.environ.get("CAMD_BENCH_DEBUG"):
             free, total = torch.cuda.mem_get_info()
             sys.stderr.write("before pcie_inclusive: %.1f GB of %.1f GB free\n" % (free / 1e9, total / 1e9))
@@ -816,96 +977,8 @@ def main():
 
     if rank == 0:
         b_alg, V = algorithmic_bytes_per_pair(a.width, a.height, a.disparities, a.channels)
-        table = stage_table(V, a.width * a.height, a.channels, a.mode)
-        kernel_ms_step = sum(stage_ms.values()) / prof_steps   # one batch alone on the GPU
         gpu_ms_step = agg["seconds"] / a.steps * 1e3             # the timed region (batches in flight overlap)
-        # HBM traffic per kernel from the committed PMC profile of the same kernels (separate rocprofv3 --pmc
-        # passes, 2*FETCH_SIZE + WRITE_SIZE per the gfx950 correction); null when no profile matches this workload
-        suffix = "_hh" if a.mode == "hh" else ""
-        # (rNN_pmc_traffic[_hh][_b<pairs per launch>].json; the one taken at this run's pairs per launch is preferred)
-        pmc_rel = _latest_profile("pmc_traffic%s*.json" % suffix, nb, exclude=None if suffix else "_hh")
-        pmc_other = _latest_profile("pmc_traffic%s.json" % suffix)
-        sq_rel = _latest_profile("pmc_sq%s.json" % suffix)
-        pmc = sq = None
-        pmc_note = "committed profile (--no-pmc)" if a.no_pmc else None
-        if world == 1 and not stub and not a.no_pmc:
-            # counters of THIS run's kernels, taken now (the timed region is over; its buffers are still allocated,
-            # the child needs its own ~1.3 GB per pair)
-            torch.cuda.empty_cache()
-            inrun, why = pmc_in_run(a, nb, a.pmc_budget_s)
-            if inrun:
-                pmc = sq = inrun
-                pmc_rel = sq_rel = "in-run: " + inrun["command"]
-                pmc_other = None
-            else:
-                pmc_note = "committed profile (in-run counters unavailable: %s)" % why
-        if pmc is None and a.channels == 3 and (a.width, a.height, a.disparities, a.block) == (1920, 1080, 128, 5):
-            pmc = json.load(open(os.path.join(ROOT, pmc_rel))) if pmc_rel else None
-            sq = json.load(open(os.path.join(ROOT, sq_rel))) if sq_rel else None
-        mix_rel, mix = valu_class_mix()
-
-        def pmc_bytes_per_pair(keys):
-            if not pmc:
-                return None
-            hit = [v["hbm_bytes_per_pair"] for k, v in pmc["kernels"].items()
-                   if all(s in k for s in keys) and "hbm_bytes_per_pair" in v]
-            return hit[0] if len(hit) == 1 else None
-
-        def sq_counters(keys):
-            """(SQ_INSTS_VALU wave-instructions per pair, fraction of wave cycles spent in s_waitcnt / s_barrier) from the
-            committed SQ counter profile of the same kernel."""
-            if not sq:
-                return None, None
-            hit = [v for k, v in sq["kernels"].items() if all(s_ in k for s_ in keys)]
-            if len(hit) != 1 or not hit[0].get("SQ_INSTS_VALU"):
-                return None, None
-            return hit[0]["SQ_INSTS_VALU"] / sq["pairs_per_launch"], hit[0].get("derived", {}).get("wait_any_frac")
-
-        kernels = {}
-        for st, ms_sum in stage_ms.items():
-            ms = ms_sum / prof_steps
-            if st not in table or ms < 0.02:  # (an empty stage bracket still measures a few microseconds)
-                continue
-            name, per_pair, keys = table[st]
-            tr = pmc_bytes_per_pair(keys)
-            ach = per_pair * nb / (ms * 1e-3) / 1e9
-            kernels[st] = {"kernel": name, "avg_ms_per_launch": ms, "algorithmic_bytes_per_launch": float(per_pair * nb),
-                           "achieved": ach, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                           "traffic": (tr * nb) if tr is not None else None}
-            vi, waitf = sq_counters(keys)
-            if vi is not None:
-                # VALU issue roofline: one (packed-form) wave-instruction per CU and cycle; the instruction count is a
-                # property of the kernel (counted once, committed), the duration is this run's.  A kernel that reaches
-                # neither 0.8 of that nor 0.6 of the HBM peak is bound by its dependency chain (barrier per step, waits):
-                # `wave_wait_frac` = share of wave cycles in s_waitcnt / s_barrier
-                vf = vi * nb / (N_CUS * CLOCK_HZ) / (ms * 1e-3)
-                hf = ach / HBM_PEAK_GBS
-                # the kernel's own issue floor: its instructions at the measured rates of their two classes (the plain
-                # 32-bit forms issue at ~1.55 per cycle and CU, packed / DPP / three-operand forms at ~0.9)
-                shape = ("k_cost<%d, %d," % (a.channels, a.block),) if st == "cost" else \
-                    ("k_band<16, %d," % ((a.disparities + 31) // 32),) if st in ("scan", "scan_last") else ()
-                ff, fs = next((m for k, m in mix.items() if all(s_ in k for s_ in keys + shape)), (0.0, 1.0))
-                floor_ms = vi * nb * (ff / RATE_FAST + fs / RATE_SLOW) / (N_CUS * CLOCK_HZ) * 1e3
-                kernels[st].update(valu_wave_insts_per_launch=vi * nb, valu_frac=vf, wave_wait_frac=waitf,
-                                   valu_plain_class_frac=ff, valu_floor_ms=floor_ms,
-                                   hbm_floor_ms=(tr * nb / (HBM_PEAK_GBS * 1e9) * 1e3) if tr is not None else None,
-                                   bound="valu" if floor_ms >= 0.8 * ms else "hbm" if hf >= 0.6 else "latency")
-        dom = max(kernels, key=lambda k: kernels[k]["avg_ms_per_launch"]) if kernels else None
-        # whole-step traffic = every kernel of the committed PMC profile (incl. the small init / check kernels)
-        traffic_total = sum(v.get("hbm_bytes_per_pair", 0.0) for v in pmc["kernels"].values()) * nb if pmc else None
-        # the step's two floors: every VALU instruction of its kernels at the issue rate of its class, and every HBM byte
-        # the counters saw at the 8 TB/s peak -- what the step would take if one of the two were the only limit
-        floors = [k.get("valu_floor_ms") for k in kernels.values()]
-        valu_floor_ms = sum(f for f in floors if f is not None) if any(f is not None for f in floors) else None
-        hbm_floor_ms = traffic_total / (HBM_PEAK_GBS * 1e9) * 1e3 if traffic_total else None
         achieved = b_alg * nb / (gpu_ms_step * 1e-3) / 1e9
-        # the same ratio from the profile taken at another number of pairs per launch, when it differs by more than 2 %
-        other_ratio = None
-        if pmc and pmc_other and pmc_other != pmc_rel:
-            po = json.load(open(os.path.join(ROOT, pmc_other)))
-            ro = sum(v["hbm_bytes_per_pair"] for v in po["kernels"].values()) / b_alg
-            if abs(ro / (traffic_total / (b_alg * nb)) - 1) > 0.02:
-                other_ratio = {"profile": pmc_other, "pairs_per_launch": po.get("pairs_per_launch"), "traffic_ratio": ro}
         line = {
             "metric": "stereo pairs/s at 1920x1080 numDisparities=128",
             "value": value, "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -919,7 +992,7 @@ def main():
                        "batches_in_flight_per_gpu": nfl, "host_cpus_bound": cpus_near_gpu,
                        "parallelism": "pairs sharded over %d GPU(s), no data-path collective" % world},
             # Headline = SURVEY section 8(d): B_alg x pairs per step / time of one step in the timed region, against
-            # the 8 TB/s HBM peak.  `kernels` / `dominant_kernel` characterise every kernel ALONE on the GPU (hipEvents
+            # the 8 TB/s HBM peak.  With --full, `kernels` / `dominant_kernel` characterise every kernel ALONE (hipEvents
             # on the compute stream, a few single-stream steps before the timed region; `kernel_ms_per_step` = their
             # sum): the kernel with the largest launch duration, priced with ITS algorithmic bytes.  Every number can
             # be recomputed from the latest profiles/rNN_*kernel_stats.csv, rNN_pmc_traffic*.json and rNN_pmc_sq*.json.
@@ -927,31 +1000,18 @@ def main():
                 "bound": "hbm", "scope": "whole step (all kernels of one batch)",
                 "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "algorithmic_bytes_per_pair": b_alg, "algorithmic_bytes_per_launch": float(b_alg * nb),
-                "gpu_ms_per_step": gpu_ms_step, "kernel_ms_per_step": kernel_ms_step,
-                "traffic": traffic_total,
-                "traffic_ratio": (traffic_total / (b_alg * nb)) if traffic_total else None,
-                "traffic_source": (pmc_rel + " (bytes per pair per launch x pairs per launch; taken at %s pairs per "
-                                             "launch)" % pmc.get("pairs_per_launch")) if pmc else None,
-                "counters": "in-run" if (pmc and str(pmc_rel).startswith("in-run")) else pmc_note,
-                # what the step would take if VALU issue / HBM bytes were its only limit, next to what it took
-                "valu_floor_ms": valu_floor_ms, "hbm_floor_ms": hbm_floor_ms,
-                "frac_of_valu_floor": (valu_floor_ms / gpu_ms_step) if valu_floor_ms else None,
-                "frac_of_hbm_floor": (hbm_floor_ms / gpu_ms_step) if hbm_floor_ms else None,
-                "valu_class_mix_source": mix_rel,
-                "traffic_ratio_other_profile": other_ratio,
-                "valu_source": (sq_rel + " (SQ_INSTS_VALU per pair x pairs per launch / (%d CUs x %.1f GHz) / this run's "
-                                         "kernel time)" % (N_CUS, CLOCK_HZ / 1e9)) if sq else None,
-                "dominant_kernel": dict(kernels[dom], stage=dom) if dom else None,
-                "kernels": kernels,
+                "gpu_ms_per_step": gpu_ms_step,
             },
         }
+        if a.full:
+            line["roofline"].update(kernel_roofline(a, nb, world, stub, stage_ms, prof_steps, gpu_ms_step, b_alg, V))
         if also:
             line["also"] = also
         if rccl:
             line["rccl"] = rccl
         if stub:
             line["stub"] = "TEST HOOK: CPU tensors and a no-op matcher; this line exercises the harness, it measures nothing"
-        if world == 1 and not a.no_cpu_baseline and not stub:
+        if world == 1 and a.full and not a.no_cpu_baseline and not stub:
             line["cpu_baseline"] = cpu_baseline(a, params)
         print(json.dumps(line))
     if distributed:

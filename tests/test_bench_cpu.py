@@ -83,3 +83,65 @@ def test_valu_class_mix_is_committed_and_sane():
         assert 0.0 < ff < 1.0 and abs(ff + fs - 1.0) < 1e-9, k
     # a kernel made of the plain class alone would issue at 1.55, of the packed class alone at 0.9
     assert bench.RATE_FAST > bench.RATE_SLOW > 0
+
+
+STUB = ["--gpus", "1", "--backend", "gloo", "--stub-compute", "--width", "96", "--height", "64", "--disparities", "16",
+        "--batch", "4", "--in-flight", "2", "--steps", "3", "--warmup", "1"]
+
+
+def _bench_line(*args):
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["OMP_NUM_THREADS"] = "1"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(args), capture_output=True, text=True,
+                       env=env, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) is the headline alone: exactly --steps timed steps, ms_per_step, the whole-step roofline,
+    nothing measured beside it.  --dump-outputs writes what compute() returned in the LAST timed step -- here step
+    warmup + steps - 1 = 3, which ran on batch set 3 % 2 = 1 -- and writes the same bits on every run."""
+    import numpy as np
+    import torch
+    d = _bench_line(*STUB, "--dump-outputs", str(tmp_path / "a"))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "int16"
+    assert abs(d["value"] - 4 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert "also" not in d and "cpu_baseline" not in d and "rccl" not in d
+    assert "kernels" not in d["roofline"] and d["roofline"]["gpu_ms_per_step"] == d["ms_per_step"]
+    got = np.load(tmp_path / "a" / "disparity.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 64, 96)
+    assert np.array_equal(np.load(tmp_path / "a" / "pair_index.npy"), np.arange(4.0))
+    l, r = bench.stub_inputs(1234 + 1000 * 1, 4, 64, 96, 3)
+    assert np.array_equal(got, (l[..., 0].to(torch.int16) - r[..., 0].to(torch.int16)).numpy().astype(np.float32))
+    _bench_line(*STUB, "--dump-outputs", str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "disparity.npy"), got)
+
+
+def test_full_run_adds_the_per_kernel_roofline():
+    d = _bench_line(*STUB, "--full")
+    assert d["steps"] == 3 and "kernels" in d["roofline"] and "counters" in d["roofline"]
+
+
+def test_dump_outputs_samples_within_the_budget(tmp_path):
+    """Larger than the budget: a seeded sample of whole pairs (the same pairs every time); larger than the budget even
+    for one pair: a seeded sample of pixels with their flat indices."""
+    import numpy as np
+    import torch
+    out = torch.arange(10 * 8 * 16, dtype=torch.int32).reshape(10, 8, 16).to(torch.int16)
+    budget = 8 * 10 + 3 * 4 * 8 * 16  # the index and three pairs
+    bench.dump_outputs(str(tmp_path / "a"), out, max_bytes=budget)
+    bench.dump_outputs(str(tmp_path / "b"), out, max_bytes=budget)
+    idx = np.load(tmp_path / "a" / "pair_index.npy")
+    got = np.load(tmp_path / "a" / "disparity.npy")
+    assert idx.dtype == np.float64 and len(idx) == 3 and np.all(np.diff(idx) > 0) and idx.max() < 10
+    assert got.dtype == np.float32 and np.array_equal(got, out.numpy()[idx.astype(int)].astype(np.float32))
+    assert got.nbytes + idx.nbytes <= budget
+    assert np.array_equal(np.load(tmp_path / "b" / "pair_index.npy"), idx)
+    bench.dump_outputs(str(tmp_path / "c"), out, max_bytes=12 * 40)  # < one pair
+    flat = np.load(tmp_path / "c" / "flat_index.npy")
+    got = np.load(tmp_path / "c" / "disparity.npy")
+    assert 0 < len(flat) <= 40 and np.array_equal(got, out.numpy().reshape(-1)[flat.astype(int)].astype(np.float32))

@@ -98,7 +98,7 @@ def test_rccl_path_with_one_forced_rank():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--width", "640", "--height", "360", "--no-also", "--no-cpu-baseline"]
+           "--batch", "8", "--width", "640", "--height", "360", "--full", "--no-also", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

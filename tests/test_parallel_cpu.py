@@ -105,7 +105,8 @@ def test_bench_main_runs_end_to_end_with_8_ranks_on_cpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                        "--backend", "gloo", "--stub-compute", "--width", "96", "--height", "64", "--disparities", "16"],
+                        "--backend", "gloo", "--stub-compute", "--width", "96", "--height", "64", "--disparities", "16",
+                        "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
