@@ -23,14 +23,37 @@ def _count(d, key):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+def _sgbm_pair(kind, H, W, cn, D, seed, split, slot):
+    """One pair of fuzz_sgbm's case kind: 0 noise, 1 opposite sawtooth ramps (shifted by the batch slot), 2 / 3
+    rectified texture, 4 drift (synthetic.drift_pair).  Every slot of a batch gets its own pair (seed and shift)."""
+    from calibrating_amd import synthetic
+    if kind == 4:  # saturation in the upper part, none below: C drifts under P2 / negative -> the exact int path
+        left, right = synthetic.drift_pair(H, W, cn, split=split, seed=seed)
+        if cn == 1:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    elif kind == 0:
+        r2 = np.random.default_rng(seed)
+        shape = (H, W) if cn == 1 else (H, W, cn)
+        left, right = r2.integers(0, 256, shape, dtype=np.uint8), r2.integers(0, 256, shape, dtype=np.uint8)
+    elif kind == 1:  # opposite sawtooth ramps: drives the window sums into saturation when preFilterCap is raised
+        x, y = np.arange(W)[None, :], np.arange(H)[:, None]
+        ramp = ((x * 16 + y * 40 + 8 * slot) % 256).astype(np.uint8)
+        left = ramp if cn == 1 else ramp[..., None].repeat(3, 2)
+        right = 255 - left
+    else:
+        left, right = synthetic.rectified_pair(seed=seed, H=H, W=W, D=max(min(D, W // 2), 8), cn=cn)
+    return left, right
+
+
+# ------------------------------------------------------------------------------------------------------------------
 def fuzz_sgbm(n, seed=77, log=print):
     """SGBM against oracle.sgbm_compute: random sizes (incl. widths that leave partial strips / single columns), channel
     counts, disparity ranges, block sizes up to 11, penalties up to the library's P2 limit, preFilterCap up to 63 (the
     saturating regime), all four modes, batches, both cost-kernel paths; every fifth case is built to drift out of the
-    int16 regime (synthetic.drift_pair) and must still match bit for bit."""
+    int16 regime (synthetic.drift_pair) and must still match bit for bit.  A batch holds distinct pairs of the case's
+    kind, each against its own oracle result, so a kernel that reads another slot's data fails."""
     import calibrating_amd as ca
     import oracle
-    from calibrating_amd import synthetic
     rng = np.random.default_rng(seed)
     br, bad = {}, []
     for case in range(n):
@@ -51,21 +74,8 @@ def fuzz_sgbm(n, seed=77, log=print):
                  uniquenessRatio=int(rng.integers(0, 30)), preFilterCap=int(rng.choice([0, 15, 31, 63])),
                  speckleWindowSize=int(rng.choice([0, 0, 40])), speckleRange=int(rng.integers(1, 4)), mode=mode)
         kind = case % 5
-        if kind == 4:  # saturation in the upper part, none below: C drifts under P2 / negative -> the exact int path
-            left, right = synthetic.drift_pair(H, W, cn, split=float(rng.uniform(0.2, 0.8)), seed=seed * 100003 + case)
-            if cn == 1:
-                left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
-        elif kind == 0:
-            r2 = np.random.default_rng(seed * 100003 + case)
-            shape = (H, W) if cn == 1 else (H, W, cn)
-            left, right = r2.integers(0, 256, shape, dtype=np.uint8), r2.integers(0, 256, shape, dtype=np.uint8)
-        elif kind == 1:  # opposite sawtooth ramps: drives the window sums into saturation when preFilterCap is raised
-            x, y = np.arange(W)[None, :], np.arange(H)[:, None]
-            ramp = ((x * 16 + y * 40) % 256).astype(np.uint8)
-            left = ramp if cn == 1 else ramp[..., None].repeat(3, 2)
-            right = 255 - left
-        else:
-            left, right = synthetic.rectified_pair(seed=seed * 100003 + case, H=H, W=W, D=max(min(D, W // 2), 8), cn=cn)
+        split = float(rng.uniform(0.2, 0.8)) if kind == 4 else None
+        left, right = _sgbm_pair(kind, H, W, cn, D, seed * 100003 + case, split, 0)
         try:
             want = oracle.sgbm_compute(left, right, **p)
         except ValueError:
@@ -77,6 +87,7 @@ def fuzz_sgbm(n, seed=77, log=print):
                 pass
             continue
         _count(br, "mode%d" % mode)
+        batch, slots = [(left, right)], {0: want}
         _count(br, ("gray" if cn == 1 else "rgb") + ("_drift_input" if kind == 4 else ""))
         try:
             for cost in ((1, 2) if mode != 2 and bs <= 11 else (0,)):
@@ -85,7 +96,10 @@ def fuzz_sgbm(n, seed=77, log=print):
                 if mode == 2 and force_band:
                     m.set_option("path", 2)
                 nb = int(rng.choice([1, 1, 3]))
-                got = m.compute(np.stack([left] * nb), np.stack([right] * nb)) if nb > 1 else m.compute(left, right)[None]
+                while len(batch) < nb:
+                    batch.append(_sgbm_pair(kind, H, W, cn, D, seed * 100003 + case + 7919 * len(batch), split, len(batch)))
+                got = (m.compute(np.stack([a for a, _ in batch[:nb]]), np.stack([b for _, b in batch[:nb]])) if nb > 1
+                       else m.compute(left, right)[None])
                 _count(br, "cost%d" % cost)
                 _count(br, "Dp%d" % m.geometry()["Dp"])  # which lane shape (16 lanes x Dp/32 registers from 96 on)
                 if nb > 1:
@@ -96,9 +110,11 @@ def fuzz_sgbm(n, seed=77, log=print):
                     if int(m.debug_volume("C").min()) < P2n:
                         _count(br, "left_u16_regime")
                 for i in range(nb):
-                    if not np.array_equal(got[i], want):
+                    if i not in slots:  # slot i of a batch holds its own pair of the case's kind
+                        slots[i] = oracle.sgbm_compute(*batch[i], **p)
+                    if not np.array_equal(got[i], slots[i]):
                         bad.append(dict(case=case, cost=cost, batch="%d/%d" % (i, nb), shape=(H, W, cn), params=p,
-                                        pixels=int((got[i] != want).sum())))
+                                        pixels=int((got[i] != slots[i]).sum())))
                         log("MISMATCH", bad[-1])
                         break
         except ValueError as e:

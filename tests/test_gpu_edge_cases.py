@@ -105,9 +105,14 @@ def test_sgbm_pitched_and_batched_inputs(oracle):
     big_r = np.zeros((40, 300, 3), np.uint8); big_r[:, :260] = right
     got = m.compute(torch.from_numpy(big_l).cuda()[:, :260], torch.from_numpy(big_r).cuda()[:, :260])
     assert np.array_equal(got.cpu().numpy(), ref)
-    L = np.stack([left] * 9); R = np.stack([right] * 9)        # 9 pairs: auto path = band passes
-    got9 = m.compute(L, R)
-    assert all(np.array_equal(got9[i], ref) for i in range(9))
+    # 9 distinct pairs (auto path = band passes), the first one in slot 4: each slot against its own oracle result
+    pairs = [synthetic.rectified_pair(seed=40 + i, H=40, W=260, D=64, cn=3) for i in range(8)]
+    pairs.insert(4, (left, right))
+    want = [oracle.sgbm_compute(a, b, **p) for a, b in pairs]
+    assert len({w.tobytes() for w in want}) == 9
+    got9 = m.compute(np.stack([a for a, _ in pairs]), np.stack([b for _, b in pairs]))
+    for i in range(9):
+        assert np.array_equal(got9[i], want[i]), i
     got1 = m.compute(left, right)                                # back to one pair on the same handle
     assert np.array_equal(got1, ref)
 

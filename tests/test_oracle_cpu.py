@@ -228,6 +228,29 @@ def test_oracle_refuses_undefined_narrow_case(oracle):
     assert oracle.sgbm_compute(img, img, numDisparities=64, blockSize=3).shape == (12, 66)
 
 
+@pytest.mark.parametrize("cn,mode", [(1, 0), (3, 1), (1, 3), (3, 2)])
+@pytest.mark.parametrize("nthreads", [1, 3, 8])
+def test_batch_entry_equals_single_pairs(oracle, cn, mode, nthreads):
+    """oracle.sgbm_compute_batch (OpenMP, one thread per pair: what the batch-scale GPU tests check against) returns
+    pair i's sgbm_compute, on distinct pairs of every kind, with more threads than pairs and fewer."""
+    H, W, D = 21, 83, 32
+    pairs = [synthetic.rectified_pair(seed=s, H=H, W=W, D=D, cn=cn) for s in (1, 2, 3)]
+    pairs.append(synthetic.drift_pair(H, W, cn, split=0.4, seed=4))
+    rng = np.random.default_rng(5)
+    shape = (H, W) if cn == 1 else (H, W, cn)
+    pairs.append((rng.integers(0, 256, shape, dtype=np.uint8), rng.integers(0, 256, shape, dtype=np.uint8)))
+    p = _p(cn, D, 5, -2, mode, preFilterCap=31, speckleWindowSize=30, speckleRange=2)
+    L, R = np.stack([a for a, _ in pairs]), np.stack([b for _, b in pairs])
+    got = oracle.sgbm_compute_batch(L, R, nthreads=nthreads, **p)
+    want = [oracle.sgbm_compute(a, b, **p) for a, b in pairs]
+    assert got.shape == (len(pairs), H, W) and got.dtype == np.int16
+    assert len({w.tobytes() for w in want}) == len(pairs)  # distinct answers: a swapped or shifted pair shows
+    for i, w in enumerate(want):
+        assert np.array_equal(got[i], w), i
+    with pytest.raises(ValueError):
+        oracle.sgbm_compute_batch(L, R, nthreads=nthreads, **dict(p, numDisparities=W - 1))  # width1 = 1: refused
+
+
 def test_pointcloud_oracle_roundtrip_and_zbuffer():
     """oracle/pointcloud_ref.py: depth -> cloud -> depth is the identity; the nearest point wins a pixel."""
     from oracle import pointcloud_ref as ref
