@@ -77,6 +77,22 @@ def inv3(m):
     ]).reshape(3, 3)
 
 
+def matmul3_loop(a, b):
+    """3x3 product in the order of a plain triple loop (s = 0; s += a[i, q] * b[q, j]), every product and sum rounded
+    on its own -- how cv::initUndistortRectifyMap's ``Ar * R`` is formed in the oracle and in tables.hip.  (NumPy's
+    ``@`` goes to a BLAS whose kernels fuse multiply-adds: 1 ulp apart in some entries, enough to move a float32 map
+    value of a 4K table by 1 ulp.)"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    out = np.empty((3, 3))
+    for i in range(3):
+        for j in range(3):
+            s = 0.0
+            for q in range(3):
+                s += float(a[i, q]) * float(b[q, j])
+            out[i, j] = s
+    return out
+
+
 def init_undistort_rectify_map(A, dist, R, Anew, size):
     """cv2.initUndistortRectifyMap(A, dist, R, Anew, size, CV_32FC1) -> (mapx, mapy) float32 (h, w).
 
@@ -92,7 +108,7 @@ def init_undistort_rectify_map(A, dist, R, Anew, size):
     if k[12] != 0 or k[13] != 0:
         raise NotImplementedError("tilted sensor model (tauX, tauY) is not on this path")
     k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4 = k[:12]
-    ir = inv3(Anew[:, :3] @ R).reshape(9)
+    ir = inv3(matmul3_loop(Anew[:, :3], R)).reshape(9)
     i = np.arange(h, dtype=np.float64)[:, None]
 
     def accumulate(start, step):

@@ -89,3 +89,20 @@ def test_speckle_full_size(oracle, h, w, nb):
         want = oracle.filter_speckles_s16(imgs[i], -16, 200, 32)
         assert (want != imgs[i]).any()
         assert np.array_equal(got[i], want), (i, int((got[i] != want).sum()))
+
+
+# the kernels around SGBM on the get_depth path: one slice per fuzzer, floors in fuzzers.POST_SLICES (also checked
+# against the generators without a GPU, tests/test_fuzzers_cpu.py)
+@pytest.mark.parametrize("name", sorted(fuzzers.POST_SLICES))
+def test_fuzz_post_slice(oracle, name):
+    n, seeds, floors = fuzzers.POST_SLICES[name]
+    _run(fuzzers.POST_FUZZERS[name][1], n, seeds, floors)
+
+
+def test_fuzz_depth_slice_meets_negative_zeros(oracle):
+    """The -0.0 of masked pixels (translate with a negative min_disparity) occurs in the references of the depth slice,
+    so its bitwise comparison is what judges the kernels' __fmul_rn(0.f, d)."""
+    n, seeds, _ = fuzzers.POST_SLICES["depth"]
+    res = fuzzers.fuzz_depth(n // 4, seeds[0])
+    assert not res["mismatches"], res["mismatches"][:3]
+    assert res["branches"].get("reference_has_negative_zero", 0) >= 3, res["branches"]
