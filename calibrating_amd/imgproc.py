@@ -235,3 +235,69 @@ def unrectify_depth(depth, M_row2, mapx, mapy):
                                                 out.data_ptr(), ow, oh, n, _native.current_stream())
     _native.check(rc, "unrectify_depth")
     return hostio.to_host(out) if was_np else out
+
+
+def check_distortion(D):
+    """The distortion vector as the kernels take it (float64, flat, up to 14 entries); tilted-sensor coefficients
+    (tauX, tauY = D[12:14]) are refused here, before any device call, as everywhere else in the library."""
+    D = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
+    if D.size > 14:
+        raise ValueError("%d distortion coefficients; cv2's model has at most 14" % D.size)
+    if D.size > 12 and (D[12:] != 0).any():
+        raise ValueError("tilted-sensor distortion (tauX, tauY) not implemented")
+    return D
+
+
+def distort_index_map(K, D, size, device=None):
+    """The per-rig part of ``Stereo.distort_depth`` (stereo_camera.py:440-462) built on the GPU: an int32 CUDA tensor
+    (h, w) whose entry [y, x] is the row-major index of the FIRST pixel of the undistorted image that
+    cv2.undistortPoints -> cv2.projectPoints -> .astype(np.int32) sends to (x, y) -- what np.unique(axis=0,
+    return_index=True) picks -- or -1 where none lands.
+
+    A rig with a target outside the image raises ``IndexError`` (the one synchronisation of this table: its counters
+    are read here, once).  The reference raises it too for targets >= w / >= h and silently wraps negative ones to the
+    far edge (NumPy's negative indexing); here both sides are refused."""
+    import torch
+    D = check_distortion(D)
+    w, h = int(size[0]), int(size[1])
+    if w <= 0 or h <= 0:
+        raise ValueError("image size must be positive, got %s" % ((w, h),))
+    K = np.ascontiguousarray(np.asarray(K, np.float64)[:3, :3]).reshape(9)
+    _native.require_device()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    idx = torch.empty((h, w), dtype=torch.int32, device=dev)
+    stats = torch.empty(6, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _native.lib().camd_distort_index_map(K.ctypes.data, D.ctypes.data if D.size else None, int(D.size), w, h,
+                                                  idx.data_ptr(), stats.data_ptr(), _native.current_stream())
+    _native.check(rc, "distort_index_map")
+    n_out, min_u, max_u, min_v, max_v, n_nonfinite = (int(v) for v in stats.cpu())
+    if n_out:
+        where = "U in [%d, %d], V in [%d, %d]" % (min_u, max_u, min_v, max_v) if min_u <= max_u else "no finite target"
+        raise IndexError("distort_depth: %d of %d pixels of the undistorted image land outside the %dx%d distorted image "
+                         "(%s; %d of them not finite) -- the reference raises IndexError for targets beyond the far edges "
+                         "and wraps negative ones around; this rig is refused" % (n_out, w * h, w, h, where, n_nonfinite))
+    return idx
+
+
+def distort_depth(depth, src_index):
+    """stereo_camera.py:438,463 (``res = zeros; res[y, x] = depths[index]``) as one gather through ``src_index``
+    (``distort_index_map``): depth (h, w) or (n, h, w), float64 or float32 -> the same shape and dtype; holes are 0."""
+    import torch
+    idx, _ = _to_dev(src_index, torch.int32)
+    z, was_np = _to_dev(depth)
+    if z.dtype not in (torch.float64, torch.float32):
+        raise ValueError("depth must be float64 or float32, got %s" % z.dtype)
+    if idx.dim() != 2 or z.dim() not in (2, 3) or tuple(z.shape[-2:]) != tuple(idx.shape):
+        raise ValueError("depth %s does not match the %s index table: expected (h, w) or (n, h, w)"
+                         % (tuple(z.shape), tuple(idx.shape)))
+    if idx.device != z.device:
+        raise ValueError("the index table lives on %s, the depth on %s" % (idx.device, z.device))
+    h, w = idx.shape
+    out = torch.empty_like(z)
+    if z.numel():
+        with torch.cuda.device(z.device):
+            rc = _native.lib().camd_distort_depth(z.data_ptr(), z.element_size(), w, h, idx.data_ptr(), out.data_ptr(),
+                                                  z.numel() // (h * w), _native.current_stream())
+        _native.check(rc, "distort_depth")
+    return hostio.to_host(out) if was_np else out

@@ -12,19 +12,21 @@ the bodies are this package's own: rig geometry lives in ``geometry.py`` as pure
   disparity_to_depth                  :408-413
   unrectify_depth                     :415-428   -> imgproc.unrectify_depth
   undistort_img                       :430-431   -> imgproc.remap_fixed_bilinear
-Extrinsic calibration (cv2.stereoCalibrate, :95-123) and ``distort_depth`` (:433-464) are outside
-the hot path: construct the rig from known {K, D, R, t} via ``Stereo.load`` or the R/t keywords.
+  distort_depth                       :433-464   -> imgproc.distort_index_map (once per rig) + imgproc.distort_depth
+Extrinsic calibration (cv2.stereoCalibrate, :95-123) is outside the hot path: construct the rig from
+known {K, D, R, t} via ``Stereo.load`` or the R/t keywords.
 
 NumPy in -> NumPy out (one H2D copy of the pair, one D2H copy per result entry); torch CUDA tensors
 in -> torch tensors out, zero-copy.
 """
 import numpy as np
 
-from . import geometry, hostio, imgproc
+from . import _native, geometry, hostio, imgproc
 from .camera import Cam, read_record, write_record
 from .stereo_matching import SemiGlobalBlockMatching
 
 _TABLE_KEYS = ("map1x", "map1y", "map2x", "map2y", "mask")
+_SIDE_TABLES = ("unrect:", "undist:", "distort:")  # prefixes of the other per-device entries of Stereo._dev
 # A broadcast bundle (SURVEY.md section 5 / 8e): the six float32 maps, the validity mask and a block of 64 doubles
 # from which a worker rank builds its rig without ever seeing the rig record.
 _BUNDLE_MAGIC = 20250930.0
@@ -97,7 +99,7 @@ class Stereo:
     def _host_table(self, name, build):
         if name not in self._host:
             if getattr(self, "_bundle_only", False):  # no camera 2 intrinsics to rebuild from: the installed tensors
-                tables = [v for k, v in self._dev.items() if not k.startswith("unrect:")]
+                tables = [v for k, v in self._dev.items() if not k.startswith(_SIDE_TABLES)]
                 if not tables:
                     raise RuntimeError("this rig was built from a table bundle but holds no installed tables")
                 tb = tables[0]
@@ -141,7 +143,7 @@ class Stereo:
                 raise RuntimeError("this rig was built from a table bundle installed on %s; it has no tables for %s and "
                                    "cannot rebuild them (a bundle carries no camera 2 intrinsics) -- install_tables() the "
                                    "bundle on that device, or load the rig's record there"
-                                   % (sorted(k for k in self._dev if not k.startswith("unrect:")), key))
+                                   % (sorted(k for k in self._dev if not k.startswith(_SIDE_TABLES)), key))
             m1x, m1y, mask = imgproc.init_undistort_rectify_map(
                 self.cam1.K, self.cam1.D, self.R1, self.K, self.xy, valid_for=self.cam1.xy, device=device)
             m2x, m2y = imgproc.init_undistort_rectify_map(
@@ -363,9 +365,45 @@ class Stereo:
         out = imgproc.remap_fixed_bilinear(i1, mxy, ma)
         return hostio.to_host(out) if was_np else out
 
+    def _distort_table(self, device):
+        """The int32 source-index table of ``distort_depth`` (imgproc.distort_index_map), built once per device and
+        memoised next to the unrectify tables.  Building it reads its out-of-range counters -- the only synchronisation
+        of this stage -- and raises ``IndexError`` for a rig whose targets leave the image."""
+        key = "distort:" + self._dev_key(device)
+        if key not in self._dev:
+            if getattr(self, "_bundle_only", False):
+                # a bundle carries no distort table; like _tables, a rig made from one never rebuilds behind the caller's back
+                raise RuntimeError("this rig was built from a table bundle, which carries no distort_depth table, and does "
+                                   "not rebuild tables it was not given -- load the rig's record on %s" % key[8:])
+            self._dev[key] = imgproc.distort_index_map(self.cam1.K, self.cam1.D, self.cam1.xy, device=device)
+        return self._dev[key]
+
+    def _check_distort_input(self, depth):
+        """Shape, dtype and distortion model of a ``distort_depth`` call, refused before any device call."""
+        w, h = (int(v) for v in self.cam1.xy)
+        shape, dtype = tuple(getattr(depth, "shape", ())), str(getattr(depth, "dtype", None)).replace("torch.", "")
+        if len(shape) not in (2, 3) or shape[-2:] != (h, w):
+            raise ValueError("distort_depth: depth must be (%d, %d) or (n, %d, %d) -- camera 1's image -- got %s"
+                             % (h, w, h, w, shape if shape else type(depth).__name__))
+        if dtype not in ("float64", "float32"):
+            raise ValueError("distort_depth: depth must be float64 or float32, got %s" % dtype)
+        if not isinstance(depth, np.ndarray) and not getattr(depth, "is_cuda", False):
+            raise ValueError("distort_depth: tensor inputs must live on the GPU")
+        imgproc.check_distortion(self.cam1.D)
+
     def distort_depth(self, depth):
-        raise NotImplementedError("Stereo.distort_depth ('OOM warning and very slow' in the reference, "
-                                  "stereo_camera.py:433-464) is outside the MI355X hot path")
+        """Depth of the undistorted camera-1 image (``unrectify_depth``) registered to the RAW, still distorted image
+        (:433-464): every pixel goes through cv2.undistortPoints / cv2.projectPoints and is truncated to a target pixel;
+        where several land on one target the first in row-major order wins, targets nobody lands on stay 0.  The
+        mapping depends on the rig only, so it is a table built once per device (``_distort_table``) and a call is one
+        gather.  ``depth``: (h, w) or (n, h, w) of camera 1's size, float64 or float32, ndarray -> ndarray, CUDA tensor
+        -> tensor; shape and dtype are kept.  A rig with a target outside the image raises ``IndexError``."""
+        self._check_distort_input(depth)
+        if isinstance(depth, np.ndarray):
+            _native.require_device()
+        d, was_np = self._to_dev(depth)
+        out = imgproc.distort_depth(d, self._distort_table(d.device))
+        return hostio.to_host(out) if was_np else out
 
     def set_stereo_matching(self, stereo_matching, max_depth=None, translation_rectify_img=None):
         """Install the matcher plugin (:466-489).  ``max_depth`` (default MAX_DEPTH) fixes
@@ -406,14 +444,31 @@ class Stereo:
         return imgproc.disp_to_depth(disp16, *args)
 
     RESULT_KEYS = ("rectify_img1", "rectify_img2", "disparity", "rectify_depth", "unrectify_depth", "undistort_img1")
+    DISTORT_KEYS = ("distort_img1", "distort_depth")  # what return_distort_depth=True adds (:528-532)
 
-    def get_depth_async(self, img1, img2, return_unrectify_depth=True, keys=None):
+    def _asked(self, who, keys, return_unrectify_depth, return_distort_depth):
+        """-> (want(key), unrectify branch on, distort branch on) of a get_depth* call.  ``keys`` decides when given:
+        asking for a distort entry switches that branch on, and ``distort_depth`` needs ``unrectify_depth`` computed
+        (not returned).  Without ``keys`` the flags decide, and as in the reference (:521) the distort branch implies
+        the unrectify branch."""
+        if keys is None:
+            distort = bool(return_distort_depth)
+            return (lambda k: True), bool(return_unrectify_depth) or distort, distort
+        keys = (keys,) if isinstance(keys, str) else tuple(keys)
+        known = self.RESULT_KEYS + self.DISTORT_KEYS
+        unknown = [k for k in keys if k not in known]
+        if unknown:
+            raise ValueError("%s(keys=...): unknown result entries %s (known: %s)" % (who, unknown, list(known)))
+        distort = any(k in keys for k in self.DISTORT_KEYS)
+        return (lambda k: k in keys), any(k in keys for k in ("unrectify_depth", "undistort_img1", "distort_depth")), distort
+
+    def get_depth_async(self, img1, img2, return_unrectify_depth=True, keys=None, return_distort_depth=False):
         """``get_depth`` without its final wait (not in the reference, whose calls are synchronous): everything is
         queued -- upload, kernels, the results' way back to page-locked host blocks -- and a ``PendingDepth`` is returned;
         ``.result()`` waits for THIS call's copies only and hands over the same dict ``get_depth`` returns.  A caller
         that keeps two or three calls in flight overlaps the ~1 ms a 1080p result dict spends on PCIe with the next
         call's kernels: one pair per call then runs at the rate of the kernels alone (tools/gpu_numpy_latency.py)."""
-        return self._get_depth(img1, img2, return_unrectify_depth, False, keys, defer=True)
+        return self._get_depth(img1, img2, return_unrectify_depth, return_distort_depth, keys, defer=True)
 
     def get_depth(self, img1, img2, return_unrectify_depth=True, return_distort_depth=False, keys=None):
         """Return dict: rectify_img1, rectify_depth, disparity, rectify_img2 (+ unrectify_depth,
@@ -423,22 +478,21 @@ class Stereo:
         ``keys`` (not in the reference): the entries the caller wants, e.g. ``keys=("unrectify_depth",)``.  The full
         dict of a 1080p pair is ~60 MB -- two float64 depth maps among them -- and its way back over PCIe costs as much
         as a third of the kernels; entries that are not asked for are neither copied nor, where nothing else needs
-        them (undistort_img1, unrectify_depth), computed.  ``None`` = the reference's dict."""
+        them (undistort_img1, unrectify_depth), computed.  ``None`` = the reference's dict.
+
+        ``return_distort_depth=True`` (:528-532) implies the unrectify branch and adds ``DISTORT_KEYS``: ``distort_img1``
+        -- the ``img1`` argument itself, as the reference hands it back -- and ``distort_depth`` =
+        ``distort_depth(unrectify_depth)``, depth registered to the raw image.  Naming one of them in ``keys`` switches
+        the branch on as well.  Its table is built on the first such call (one synchronisation, once per rig and
+        device); later calls add one gather kernel and no synchronisation."""
         return self._get_depth(img1, img2, return_unrectify_depth, return_distort_depth, keys, defer=False)
 
     def _get_depth(self, img1, img2, return_unrectify_depth, return_distort_depth, keys, defer):
         """The body of get_depth / get_depth_async (``defer``: hand back a PendingDepth instead of waiting)."""
         import torch
         assert hasattr(self, "stereo_matching"), "Please stereo.set_stereo_matching(stereo_matching)"
-        if return_distort_depth:
-            self.distort_depth(None)
-        if keys is not None:
-            keys = (keys,) if isinstance(keys, str) else tuple(keys)
-            unknown = [k for k in keys if k not in self.RESULT_KEYS]
-            if unknown:
-                raise ValueError("get_depth(keys=...): unknown result entries %s (known: %s)" % (unknown, list(self.RESULT_KEYS)))
-            return_unrectify_depth = "unrectify_depth" in keys or "undistort_img1" in keys
-        want = (lambda k: True) if keys is None else (lambda k: k in keys)
+        want, return_unrectify_depth, distort = self._asked("get_depth", keys, return_unrectify_depth, return_distort_depth)
+        distort_img1 = img1  # :530 hands back the argument itself
         img1, img2 = self._get_img(img1), self._get_img(img2)
         was_np = isinstance(img1, np.ndarray)
         sink, result = None, {}
@@ -455,6 +509,8 @@ class Stereo:
         if was_np:
             sink = hostio.Sink(i1.device)
         tb = self._tables(i1.device)
+        if distort and want("distort_depth"):
+            self._distort_table(i1.device)  # a rig it refuses (IndexError) is refused before any kernel of the call is queued
         rectify_img1 = imgproc.remap(i1, tb["map1x"], tb["map1y"], imgproc.INTER_LANCZOS4)
         emit(rectify_img1=rectify_img1)
         if return_unrectify_depth and want("undistort_img1"):
@@ -483,11 +539,15 @@ class Stereo:
                 disparity = torch.from_numpy(np.ascontiguousarray(disparity)).to(i1.device)
             disparity = tb["mask"].to(torch.bool) * disparity
             rectify_depth = self.disparity_to_depth(disparity)
-        if return_unrectify_depth and want("unrectify_depth"):
+        if return_unrectify_depth and (want("unrectify_depth") or (distort and want("distort_depth"))):
             # queued before the copies of disparity / rectify_depth start: the caller usually waits for this one
             unrect = self.unrectify_depth(rectify_depth)
             emit(unrectify_depth=unrect)
+            if distort and want("distort_depth"):
+                emit(distort_depth=self.distort_depth(unrect))
         emit(disparity=disparity, rectify_depth=rectify_depth)
+        if distort and want("distort_img1"):
+            result["distort_img1"] = distort_img1  # (not through the sink: it never left the caller's hands)
         if defer:
             return PendingDepth(result, sink)
         if sink is not None:
@@ -496,7 +556,7 @@ class Stereo:
                 plugin.stereo_sgbm.status()  # collect() synchronised: surface device-side timeouts at no extra cost
         return result
 
-    def get_depth_batch(self, imgs1, imgs2, return_unrectify_depth=True, keys=None):
+    def get_depth_batch(self, imgs1, imgs2, return_unrectify_depth=True, keys=None, return_distort_depth=False):
         """``get_depth`` for ``n`` pairs of the same rig at once: ``imgs1`` / ``imgs2`` are ``(n, h, w, 3)``
         uint8 (NumPy or torch CUDA), every value of the returned dict carries the leading ``n``.
 
@@ -506,15 +566,11 @@ class Stereo:
         to ``get_depth(imgs1[i], imgs2[i])``.  Requires the SGBM plugin; a ``max_size`` below the rectified image
         size downsizes the whole batch first, as the matcher does for one pair.  ``keys``: as in ``get_depth`` -- only
         the asked entries are returned (and copied to the host for ndarray input; a batch of 64 1080p pairs is 3.8 GB).
+        ``return_distort_depth``: as in ``get_depth`` (``distort_img1`` is ``imgs1`` itself).
         """
         assert hasattr(self, "stereo_matching"), "Please stereo.set_stereo_matching(stereo_matching)"
-        if keys is not None:
-            keys = (keys,) if isinstance(keys, str) else tuple(keys)
-            unknown = [k for k in keys if k not in self.RESULT_KEYS]
-            if unknown:
-                raise ValueError("get_depth_batch(keys=...): unknown result entries %s (known: %s)" % (unknown, list(self.RESULT_KEYS)))
-            return_unrectify_depth = "unrectify_depth" in keys or "undistort_img1" in keys
-        want = (lambda k: True) if keys is None else (lambda k: k in keys)
+        want, return_unrectify_depth, distort = self._asked("get_depth_batch", keys, return_unrectify_depth,
+                                                            return_distort_depth)
         i1, was_np = self._to_dev(imgs1)
         i2, _ = self._to_dev(imgs2)
         # (the two cameras of a rig may differ in resolution -- each is rectified through its own maps,
@@ -523,6 +579,8 @@ class Stereo:
             raise ValueError("imgs1 / imgs2 must be (n, h, w, c) stacks of the same number of pairs and channels")
         if self._native_sgbm() is None:
             raise ValueError("get_depth_batch needs the SemiGlobalBlockMatching plugin (with its own __call__)")
+        if distort and want("distort_depth"):
+            self._distort_table(i1.device)  # a rig it refuses (IndexError) is refused before any kernel of the call is queued
         rectify_img1, rectify_img2 = self.rectify(i1, i2)
         sm = self._sgbm_full_res(rectify_img1.shape[1:3])
         tb = self._tables(i1.device)
@@ -535,8 +593,10 @@ class Stereo:
         result = dict(rectify_img1=rectify_img1, rectify_depth=rectify_depth, disparity=disparity,
                       rectify_img2=rectify_img2)
         if return_unrectify_depth:
-            if want("unrectify_depth"):
+            if want("unrectify_depth") or (distort and want("distort_depth")):
                 result.update(unrectify_depth=self.unrectify_depth(rectify_depth))
+                if distort and want("distort_depth"):
+                    result.update(distort_depth=self.distort_depth(result["unrectify_depth"]))
             if want("undistort_img1"):
                 result.update(undistort_img1=self.undistort_img(i1))
         result = {k: v for k, v in result.items() if want(k)}
@@ -544,4 +604,6 @@ class Stereo:
             # (to_host_list: with a single asked key, to_host's bare ndarray would be zipped row by row)
             result = dict(zip(result, hostio.to_host_list(*result.values())))
             sm.stereo_sgbm.status()  # to_host synchronised: surface device-side timeouts at no extra cost
+        if distort and want("distort_img1"):
+            result["distort_img1"] = imgs1  # the argument itself (:530), not a copy
         return result

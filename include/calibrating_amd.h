@@ -216,6 +216,22 @@ int camd_disp16_resized_to_depth(const int16_t* disp16, int sw, int sh, const ui
 int camd_unrectify_depth(const double* depth, int w, int h, const double M_row2_host[3],
                          const float* mapx, const float* mapy, double* out, int ow, int oh,
                          int batch, void* stream);
+/* replaces the per-rig part of Stereo.distort_depth (stereo_camera.py:440-462): every pixel of the undistorted w x h
+ * image of camera K through cv2.undistortPoints(., K, None) -> cv2.projectPoints(., 0, 0, K, dist) -> .astype(int32)
+ * (truncation) -> np.unique(axis=0, return_index=True).  src_index: device int32 [h][w]; entry [y][x] is the LOWEST
+ * row-major source index v*w + u whose target is (x, y), or -1 where no pixel lands (a hole).  dist: ndist <= 14
+ * host doubles (k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tauX tauY); non-zero tauX / tauY (tilted sensor) are refused with
+ * CAMD_ERR_UNSUPPORTED.  stats: device int32[6] = {n_out, minU, maxU, minV, maxV, n_nonfinite}: how many source pixels
+ * have a target outside [0, w) x [0, h) (non-finite targets included; they are counted and never written) and the
+ * range of the finite targets.  The reference raises IndexError for a target >= w / >= h and wraps a negative one to
+ * the far edge; a caller that wants neither reads stats once per table and refuses the rig when n_out != 0.        */
+int camd_distort_index_map(const double K[9], const double* dist, int ndist, int w, int h, int32_t* src_index,
+                           int32_t* stats, void* stream);
+/* replaces stereo_camera.py:438,463 (res = zeros; res[y, x] = depths[index]) as a gather through src_index:
+ * out[b][p] = src_index[p] < 0 ? 0 : depth[b][src_index[p]].  depth / out: [batch][h][w] of elem_bytes = 8 (float64)
+ * or 4 (float32), contiguous, out != depth, batch <= 2^19; an index outside [0, w*h) reads nothing and yields 0.    */
+int camd_distort_depth(const void* depth, int elem_bytes, int w, int h, const int32_t* src_index, void* out, int batch,
+                       void* stream);
 
 /* ---- depth post-ops (the step after get_depth in the reference's demos) ---------------------------
  * replaces utils.depth_to_point_cloud (utils.py:213-246): non-zero depths in row-major order of the sampling
