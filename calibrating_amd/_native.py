@@ -32,6 +32,7 @@ MODE_HH4 = 3
 INTER_NEAREST = 0
 INTER_LINEAR = 1
 INTER_LANCZOS4 = 4
+VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_arr2d
 
 
 class SgbmParams(ctypes.Structure):
@@ -81,6 +82,10 @@ SIGNATURES = {
                                           c_void_p, c_void_p]),
     "camd_project_depth": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int,
                                    c_void_p, c_void_p, c_void_p]),
+    "camd_reproject_remap": (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int,
+                                     c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
+    "camd_point_cloud_to_arr2d": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                          c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_set_global_option": (c_int, [c_int, c_int]),
     "camd_lanczos4_table_host": (c_int, [c_void_p]),
     "camd_bilinear_table_host": (c_int, [c_void_p]),

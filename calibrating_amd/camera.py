@@ -113,3 +113,14 @@ class Cam(dict):
         from . import pointcloud
         rate = pointcloud.get_appropriate_interpolation_rate(cam1, cam2, interpolation)
         return pointcloud.project_depth(depth2, cam2.K, T, cam1.K, cam1.xy, interpolation_rate=rate)
+
+    def reproject_img(cam1, cam2, depth2, img2, T=None, interpolation=1.5):
+        """``img2`` of ``cam2`` brought into this camera's frame through ``depth2`` -- the image half of
+        ``vis_reproject_img_alignment`` (camera.py:322-342), on the GPU; ``Stereo.undistort_img`` gives the other half.
+        ``T`` = pose of cam2 in this camera (4x4), required as in ``project_cam2_depth``."""
+        assert not np.any(cam2.D), f"cam2.D has distort: {cam2.D}"
+        if T is None:
+            raise NotImplementedError("pass T (cam2 in cam1): board-based extrinsics are outside the MI355X path")
+        from . import pointcloud
+        rate = pointcloud.get_appropriate_interpolation_rate(cam1, cam2, interpolation)
+        return pointcloud.reproject_img(img2, depth2, cam2.K, T, cam1.K, cam1.xy, interpolation_rate=rate)

@@ -3,6 +3,8 @@
 //   utils.apply_T_to_point_cloud (utils.py:152-161)
 //   utils.point_cloud_to_depth   (utils.py:249-318)   projection + "far first, near last" overwrite = z-buffer
 //   Cam.project_cam2_depth       (camera.py:298-309)  the three above composed; here ONE fused scatter kernel
+//   utils.point_cloud_to_arr2d   (utils.py:254-317)   the same z-buffer carrying a payload (values of the winning point)
+//   utils.get_reproject_remap    (utils.py:332-344)   ... whose payload is the (u, v) of the source grid cell
 // float64 throughout like the reference's NumPy.  Matrix products are evaluated left to right without
 // contraction; NumPy's BLAS may order / fuse them differently, so parity with the oracle is to ~1 ulp on the
 // points and exact on the z-buffer except where a projection lands within rounding error of x.5.
@@ -139,17 +141,30 @@ __global__ __launch_bounds__(256) void k_fill_u64(unsigned long long* p, size_t 
 struct Mat34 { double m[12]; };
 struct Mat33 { double m[9]; };
 
-// project one camera-space point with K (utils.py:286-288, 311-316) and keep the nearest per pixel
-__device__ __forceinline__ void zbuffer_point(double X, double Y, double Z, const Mat33& K, int w, int h,
-                                              unsigned long long* __restrict__ keys)
+// project one camera-space point with K (utils.py:286-288, 311-316): the target pixel and the z-buffer key of the point.
+// Every pass of every z-buffer calls this one function, so that a pass which recomputes a point sees the bits the
+// pass before it saw.  false: the point lands outside the image (or its projection is NaN / inf) and is dropped.
+__device__ __forceinline__ bool project_pixel(double X, double Y, double Z, const Mat33& K, int w, int h, size_t* pix,
+                                              unsigned long long* key)
 {
     const double xs = dot3(X, Y, Z, K.m[0], K.m[1], K.m[2]);
     const double ys = dot3(X, Y, Z, K.m[3], K.m[4], K.m[5]);
     const double zs = dot3(X, Y, Z, K.m[6], K.m[7], K.m[8]);
     const double u = xs / zs, v = ys / zs;
     const double ru = rint(u), rv = rint(v);  // np.round: half to even
-    if (!(ru >= 0.0 && ru < (double)w && rv >= 0.0 && rv < (double)h)) return;  // also drops NaN / inf
-    atomicMin(keys + (size_t)(int)rv * w + (int)ru, zkey(zs));
+    if (!(ru >= 0.0 && ru < (double)w && rv >= 0.0 && rv < (double)h)) return false;  // also drops NaN / inf
+    *pix = (size_t)(int)rv * w + (int)ru;
+    *key = zkey(zs);
+    return true;
+}
+
+// ... and keep the nearest per pixel
+__device__ __forceinline__ void zbuffer_point(double X, double Y, double Z, const Mat33& K, int w, int h,
+                                              unsigned long long* __restrict__ keys)
+{
+    size_t pix;
+    unsigned long long key;
+    if (project_pixel(X, Y, Z, K, w, h, &pix, &key)) atomicMin(keys + pix, key);
 }
 
 __global__ __launch_bounds__(256) void k_pc_scatter(const double* __restrict__ points, size_t n, int stride, Mat33 K, int w,
@@ -177,14 +192,14 @@ __global__ __launch_bounds__(256) void k_apply_T(const double* __restrict__ src,
     dst[i * 3 + 2] = dot4(T.m[8], T.m[9], T.m[10], T.m[11], x, y, z, 1.0);
 }
 
-// Cam.project_cam2_depth fused: depth2 grid cell -> point (K2^-1) -> T -> K1 projection -> z-buffer
-__global__ __launch_bounds__(256) void k_project_depth(const double* __restrict__ depth2, PcGrid g, Mat33 K2inv, Mat34 T,
-                                                       Mat33 K1, int w1, int h1, unsigned long long* __restrict__ keys)
+// one cell of camera 2's sampling grid -> point (K2^-1) -> T -> K1 projection: target pixel and key (false: z == 0 or
+// outside).  Shared by the depth-only scatter and by both atomics passes of the payload z-buffer below.
+__device__ __forceinline__ bool grid_cell_pixel(const double* __restrict__ depth2, const PcGrid& g, int x, int y,
+                                                const Mat33& K2inv, const Mat34& T, const Mat33& K1, int w1, int h1,
+                                                size_t* pix, unsigned long long* key)
 {
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= g.gw) return;
     const double z = pc_sample(depth2, g, x, y);
-    if (z == 0.0) return;
+    if (z == 0.0) return false;
     const double u = g.rate == 1.0 ? (double)x : (double)x / g.rate;
     const double v = g.rate == 1.0 ? (double)y : (double)y / g.rate;
     const double p0 = u * z, p1 = v * z, p2 = 1.0 * z;
@@ -194,7 +209,100 @@ __global__ __launch_bounds__(256) void k_project_depth(const double* __restrict_
     const double X1 = dot4(T.m[0], T.m[1], T.m[2], T.m[3], X, Y, Z, 1.0);
     const double Y1 = dot4(T.m[4], T.m[5], T.m[6], T.m[7], X, Y, Z, 1.0);
     const double Z1 = dot4(T.m[8], T.m[9], T.m[10], T.m[11], X, Y, Z, 1.0);
-    zbuffer_point(X1, Y1, Z1, K1, w1, h1, keys);
+    return project_pixel(X1, Y1, Z1, K1, w1, h1, pix, key);
+}
+
+// Cam.project_cam2_depth fused: depth2 grid cell -> point (K2^-1) -> T -> K1 projection -> z-buffer
+__global__ __launch_bounds__(256) void k_project_depth(const double* __restrict__ depth2, PcGrid g, Mat33 K2inv, Mat34 T,
+                                                       Mat33 K1, int w1, int h1, unsigned long long* __restrict__ keys)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= g.gw) return;
+    size_t pix;
+    unsigned long long key;
+    if (grid_cell_pixel(depth2, g, x, y, K2inv, T, K1, w1, h1, &pix, &key)) atomicMin(keys + pix, key);
+}
+
+// ---- the z-buffer that remembers its winner (point_cloud_to_arr2d with values, get_reproject_remap) -----------------
+// The reference sorts the points far to near and lets the later write win (utils.py:280-288, 312-316); what arrives in
+// a pixel is the PAYLOAD of the nearest point.  Three passes over caller-provided buffers:
+//   1  keys[pix]  = min over the sources of zkey(zs)                       (atomicMin, u64; ZKEY_EMPTY = nobody)
+//   2  owner[pix] = 1 + max index of the sources whose key equals keys[pix] (atomicMax, u32; 0 = nobody)
+//   3  one thread per target pixel gathers the owner's payload, or the background value
+// Two atomics passes because a 64-bit atomicMin cannot carry a 64-bit depth AND an index, and depth bits may not be
+// dropped: the winner is decided on all 64 of them.  Both are commutative, so the result does not depend on the order
+// in which the hardware serves them.  Points with bit-equal z on one pixel: the larger index wins -- what a STABLE
+// far-to-near sort followed by last-write-wins gives; np.argsort's default (introsort) leaves that case to its
+// internals.  index = row-major cell of the sampling grid (fused form) or row of the point array (generic form).
+__global__ __launch_bounds__(256) void k_zb_clear(unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner,
+                                                  size_t n)
+{
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { keys[i] = ZKEY_EMPTY; owner[i] = 0u; }
+}
+
+template <bool OWNER>
+__global__ __launch_bounds__(256) void k_reproject_pass(const double* __restrict__ depth2, size_t depth_stride, PcGrid g,
+                                                        Mat33 K2inv, Mat34 T, Mat33 K1, int w1, int h1,
+                                                        unsigned long long* __restrict__ keys,
+                                                        uint32_t* __restrict__ owner)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= g.gw) return;
+    const size_t b = blockIdx.z, npix = (size_t)w1 * h1;
+    size_t pix;
+    unsigned long long key;
+    if (!grid_cell_pixel(depth2 + b * depth_stride, g, x, y, K2inv, T, K1, w1, h1, &pix, &key)) return;
+    if (!OWNER) atomicMin(keys + b * npix + pix, key);
+    else if (keys[b * npix + pix] == key) atomicMax(owner + b * npix + pix, (uint32_t)((size_t)y * g.gw + x) + 1u);
+}
+
+// pass 3 of get_reproject_remap: owner -> (x, y) of the grid cell -> np.float32(x / rate), np.float32(y / rate)
+// (utils.py:234-240, 339); -1 where nothing landed (bg_value=-1, :342)
+__global__ __launch_bounds__(256) void k_reproject_emit(const uint32_t* __restrict__ owner, int gw, double rate, size_t npix,
+                                                        float bg, float* __restrict__ mapx, float* __restrict__ mapy,
+                                                        size_t map_stride)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (i >= npix) return;
+    const uint32_t o = owner[b * npix + i];
+    float fx = bg, fy = bg;
+    if (o) {
+        const uint32_t x = (o - 1u) % (uint32_t)gw, y = (o - 1u) / (uint32_t)gw;
+        fx = (float)(rate == 1.0 ? (double)x : (double)x / rate);
+        fy = (float)(rate == 1.0 ? (double)y : (double)y / rate);
+    }
+    mapx[b * map_stride + i] = fx;
+    mapy[b * map_stride + i] = fy;
+}
+
+__global__ __launch_bounds__(256) void k_pc_owner(const double* __restrict__ points, size_t n, int stride, Mat33 K, int w,
+                                                  int h, const unsigned long long* __restrict__ keys,
+                                                  uint32_t* __restrict__ owner)
+{
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    size_t pix;
+    unsigned long long key;
+    if (!project_pixel(points[i * stride], points[i * stride + 1], points[i * stride + 2], K, w, h, &pix, &key)) return;
+    if (keys[pix] == key) atomicMax(owner + pix, (uint32_t)i + 1u);
+}
+
+// pass 3 of point_cloud_to_arr2d: out[pix][c] = values[owner][c] (utils.py:314-316), bg where nothing landed (:308)
+template <typename V>
+__global__ __launch_bounds__(256) void k_arr2d_gather(const uint32_t* __restrict__ owner, size_t npix,
+                                                      const V* __restrict__ values, int channels, V bg,
+                                                      V* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    const uint32_t o = owner[i];
+    if (o) {
+        const V* src = values + (size_t)(o - 1u) * channels;
+        for (int c = 0; c < channels; c++) out[i * channels + c] = src[c];
+    } else {
+        for (int c = 0; c < channels; c++) out[i * channels + c] = bg;
+    }
 }
 
 static int make_grid(PcGrid* g, int w, int h, double rate, const char* who)
@@ -312,6 +420,91 @@ int camd_project_depth(const double* depth2, int w2, int h2, const double K2inv[
     hipLaunchKernelGGL(k_fill_u64, dim3(div_up((long long)npix, 256)), dim3(256), 0, st, keys_ws, npix, ZKEY_EMPTY);
     hipLaunchKernelGGL(k_project_depth, dim3(div_up(g.gw, 256), g.gh), dim3(256), 0, st, depth2, g, Ki, M, Km, w1, h1, keys_ws);
     hipLaunchKernelGGL(k_pc_resolve, dim3(div_up((long long)npix, 256)), dim3(256), 0, st, keys_ws, npix, 0.0, depth1);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_reproject_remap(const double* depth2, int w2, int h2, size_t depth_stride, const double K2inv[9],
+                         const double T_2in1[16], const double K1[9], double rate, int w1, int h1, float* mapx,
+                         float* mapy, size_t map_stride, unsigned long long* keys_ws, uint32_t* owner_ws, int batch,
+                         void* stream)
+{
+    PcGrid g;
+    int rc = make_grid(&g, w2, h2, rate, "camd_reproject_remap");
+    if (rc != CAMD_OK) return rc;
+    if (!depth2 || !K2inv || !T_2in1 || !K1 || !mapx || !mapy || !keys_ws || !owner_ws || w1 <= 0 || h1 <= 0 ||
+        batch <= 0 || batch > 65535 || g.gh > 65535 || (size_t)w1 * h1 > ((size_t)1 << 38) / (size_t)(batch > 0 ? batch : 1) ||
+        (batch > 1 && (depth_stride < (size_t)w2 * h2 || map_stride < (size_t)w1 * h1))) {
+        set_error("camd_reproject_remap: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if ((unsigned long long)g.gw * (unsigned long long)g.gh >= 0xffffffffull) {
+        set_error("camd_reproject_remap: a sampling grid of %d x %d cells does not fit the 32-bit owner index", g.gw, g.gh);
+        return CAMD_ERR_BAD_ARG;
+    }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npix = (size_t)w1 * h1;
+    Mat33 Ki, Km;
+    Mat34 M;
+    for (int i = 0; i < 9; i++) { Ki.m[i] = K2inv[i]; Km.m[i] = K1[i]; }
+    for (int i = 0; i < 12; i++) M.m[i] = T_2in1[i];
+    const dim3 src_grid(div_up(g.gw, 256), g.gh, batch), dst_grid(div_up((long long)npix, 256), batch);
+    hipLaunchKernelGGL(k_zb_clear, dim3(div_up((long long)(npix * batch), 256)), dim3(256), 0, st, keys_ws, owner_ws,
+                       npix * batch);
+    hipLaunchKernelGGL((k_reproject_pass<false>), src_grid, dim3(256), 0, st, depth2, depth_stride, g, Ki, M, Km, w1, h1,
+                       keys_ws, owner_ws);
+    hipLaunchKernelGGL((k_reproject_pass<true>), src_grid, dim3(256), 0, st, depth2, depth_stride, g, Ki, M, Km, w1, h1,
+                       keys_ws, owner_ws);
+    hipLaunchKernelGGL(k_reproject_emit, dst_grid, dim3(256), 0, st, owner_ws, g.gw, g.rate, npix, -1.0f, mapx, mapy,
+                       map_stride);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, const double K[9], int w, int h,
+                              const void* values, int channels, int value_type, double bg_value, void* out,
+                              unsigned long long* keys_ws, uint32_t* owner_ws, void* stream)
+{
+    if (!K || !out || !keys_ws || !owner_ws || w <= 0 || h <= 0 || point_stride < 3 || channels < 1 ||
+        (n && (!points || !values))) {
+        set_error("camd_point_cloud_to_arr2d: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (value_type != CAMD_VALUE_F64 && value_type != CAMD_VALUE_F32 && value_type != CAMD_VALUE_U8) {
+        set_error("camd_point_cloud_to_arr2d: value_type %d is none of float64 / float32 / uint8", value_type);
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (value_type == CAMD_VALUE_U8 && !(bg_value >= 0.0 && bg_value <= 255.0 && bg_value == (double)(uint8_t)bg_value)) {
+        set_error("camd_point_cloud_to_arr2d: bg_value %g is not a uint8", bg_value);
+        return CAMD_ERR_BAD_ARG;
+    }
+    if ((unsigned long long)n >= 0xffffffffull) {
+        set_error("camd_point_cloud_to_arr2d: %zu points do not fit the 32-bit owner index", n);
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npix = (size_t)w * h;
+    Mat33 Km;
+    for (int i = 0; i < 9; i++) Km.m[i] = K[i];
+    const dim3 src_grid(div_up((long long)n, 256)), dst_grid(div_up((long long)npix, 256));
+    hipLaunchKernelGGL(k_zb_clear, dst_grid, dim3(256), 0, st, keys_ws, owner_ws, npix);
+    if (n) {
+        hipLaunchKernelGGL(k_pc_scatter, src_grid, dim3(256), 0, st, points, n, point_stride, Km, w, h, keys_ws);
+        hipLaunchKernelGGL(k_pc_owner, src_grid, dim3(256), 0, st, points, n, point_stride, Km, w, h, keys_ws, owner_ws);
+    }
+    if (value_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_arr2d_gather<double>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const double*)values,
+                           channels, bg_value, (double*)out);
+    else if (value_type == CAMD_VALUE_F32)
+        hipLaunchKernelGGL((k_arr2d_gather<float>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const float*)values,
+                           channels, (float)bg_value, (float*)out);
+    else
+        hipLaunchKernelGGL((k_arr2d_gather<uint8_t>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const uint8_t*)values,
+                           channels, (uint8_t)bg_value, (uint8_t*)out);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }

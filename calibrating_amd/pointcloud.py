@@ -3,6 +3,11 @@
 (/root/reference/calibrating/utils.py:152-161, 213-318) and the interpolation-rate rule of
 ``utils._get_appropriate_interpolation_rate`` (:201-210).  float64 like the reference's NumPy.
 NumPy in -> NumPy out, torch CUDA tensors in -> tensors out.
+
+The payload half -- ``point_cloud_to_arr2d`` with values (:254-317), ``get_reproject_remap`` (:332-344) and the
+``cv2.remap(img2, mapx, mapy, INTER_LINEAR)`` after it (camera.py:322-342, here ``reproject_img``) -- runs through a
+z-buffer that remembers its winner.  Points that share a pixel and have bit-equal z: the larger index wins
+(INTEGRATION.md section D).
 """
 import ctypes
 
@@ -120,3 +125,176 @@ def project_depth(depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
                                               _native.current_stream())
     _native.check(rc, "project_depth")
     return hostio.to_host(depth1) if was_np else depth1
+
+
+# ---- the z-buffer with a payload -----------------------------------------------------------------------------------
+_VALUE_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32, "uint8": _native.VALUE_U8}
+
+
+def _dtype_name(a):
+    return str(a.dtype).replace("torch.", "")
+
+
+def _check_array(a, what):
+    """ndarray or CUDA tensor, checked without touching the device."""
+    if isinstance(a, np.ndarray):
+        return
+    if not (hasattr(a, "is_cuda") and hasattr(a, "data_ptr")):
+        raise TypeError("%s must be a NumPy array or a torch CUDA tensor, got %s" % (what, type(a).__name__))
+    if not a.is_cuda:
+        raise ValueError("tensor inputs must live on the GPU (%s)" % what)
+
+
+def _check_xy(xy, what="xy"):
+    w, h = int(xy[0]), int(xy[1])
+    if w <= 0 or h <= 0:
+        raise ValueError("%s must be a positive (width, height), got %s" % (what, (xy[0], xy[1])))
+    return w, h
+
+
+def _same_device(a, b, what):
+    if not isinstance(a, np.ndarray) and not isinstance(b, np.ndarray) and a.device != b.device:
+        raise ValueError("%s live on different devices: %s and %s" % (what, a.device, b.device))
+
+
+def _keep_dtype_to_dev(a, device=None):
+    import torch
+    if isinstance(a, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        return t.cuda() if device is None else t.to(device)
+    return a.contiguous()
+
+
+def point_cloud_to_arr2d(points, K, xy, values=None, bg_value=0):
+    """Image (xy[1], xy[0][, C]) of what the nearest point per pixel carries (utils.py:254-317): ``values`` (N,) or
+    (N, 1) -> (h, w); (N, C >= 2) -> (h, w, C); float64, float32 or uint8, the result has the values' dtype and
+    ``bg_value`` where no point lands.  ``values=None`` is ``point_cloud_to_depth``.  The coloured-cloud path is
+    ``values = img[mask]``.  Points with bit-equal z on one pixel: the later row wins."""
+    if values is None:
+        return point_cloud_to_depth(points, K, xy, bg_value=bg_value)
+    _check_array(points, "points")
+    _check_array(values, "values")
+    if len(points.shape) != 2 or points.shape[1] < 3:
+        raise ValueError("points must be (N, >=3), got %s" % (tuple(points.shape),))
+    n = int(points.shape[0])
+    vshape = tuple(values.shape)
+    if len(vshape) not in (1, 2) or vshape[0] != n or (len(vshape) == 2 and vshape[1] < 1):
+        raise ValueError("values must be (N,) or (N, C) with N = %d points, got %s" % (n, vshape))
+    name = _dtype_name(values)
+    if name not in _VALUE_TYPES:
+        raise ValueError("values must be float64, float32 or uint8, got %s" % name)
+    bg = float(bg_value)
+    if name == "uint8" and not (0 <= bg <= 255 and bg == int(bg)):
+        raise ValueError("bg_value %r is not a uint8" % (bg_value,))
+    _same_device(points, values, "points and values")
+    w, h = _check_xy(xy)
+    Km = _mat(np.asarray(K, np.float64)[:3, :3], 9)
+    channels = vshape[1] if len(vshape) == 2 else 1
+    import torch
+    p, _ = _to_dev(points, torch.float64)
+    v = _keep_dtype_to_dev(values, p.device)
+    was_np = isinstance(values, np.ndarray)
+    with torch.cuda.device(p.device):
+        out = torch.empty((h, w, channels) if channels >= 2 else (h, w), dtype=v.dtype, device=p.device)
+        keys = torch.empty((h, w), dtype=torch.int64, device=p.device)
+        owner = torch.empty((h, w), dtype=torch.int32, device=p.device)
+        rc = _native.lib().camd_point_cloud_to_arr2d(p.data_ptr(), n, p.shape[1], Km.ctypes.data, w, h, v.data_ptr(),
+                                                     channels, _VALUE_TYPES[name], bg, out.data_ptr(), keys.data_ptr(),
+                                                     owner.data_ptr(), _native.current_stream())
+    _native.check(rc, "point_cloud_to_arr2d")
+    return hostio.to_host(out) if was_np else out
+
+
+def _check_depth2(depth2):
+    _check_array(depth2, "depth2")
+    if len(depth2.shape) not in (2, 3) or 0 in tuple(depth2.shape):
+        raise ValueError("depth2 must be (h2, w2) or (n, h2, w2), got %s" % (tuple(depth2.shape),))
+    name = _dtype_name(depth2)
+    if name not in ("float64", "float32", "uint16"):
+        raise ValueError("depth2 must be float64, float32 or uint16 (millimetres), got %s" % name)
+    return name
+
+
+def _depth_to_dev(depth2, name):
+    """float64 CUDA tensor of the depth in metres; uint16 is millimetres through float32 (utils.py:218-219)."""
+    import torch
+    if isinstance(depth2, np.ndarray):
+        if name == "uint16":
+            depth2 = np.float32(depth2 / 1000.0)
+        _native.require_device()
+        return torch.from_numpy(np.ascontiguousarray(depth2, dtype=np.float64)).cuda()
+    if name == "uint16":
+        depth2 = (depth2.to(torch.float64) / 1000.0).to(torch.float32)
+    return depth2.to(torch.float64).contiguous()
+
+
+def _reproject_args(K1, K2, T_2in1, xy1, interpolation_rate):
+    w1, h1 = _check_xy(xy1, "xy1")
+    rate = float(interpolation_rate)
+    if not (rate > 0 and np.isfinite(rate)):
+        raise ValueError("interpolation_rate must be positive and finite, got %r" % (interpolation_rate,))
+    K2m = np.asarray(K2, np.float64)
+    if K2m.ndim != 2 or K2m.shape[0] < 3 or K2m.shape[1] < 3:
+        raise ValueError("K2 must be a 3x3 matrix, got shape %s" % (K2m.shape,))
+    K2inv = np.ascontiguousarray(np.linalg.inv(K2m[:3, :3])).reshape(9)
+    K1m = np.asarray(K1, np.float64)
+    if K1m.ndim != 2 or K1m.shape[0] < 3 or K1m.shape[1] < 3:
+        raise ValueError("K1 must be a 3x3 matrix, got shape %s" % (K1m.shape,))
+    return w1, h1, rate, K2inv, _mat(T_2in1, 16), _mat(K1m[:3, :3], 9)
+
+
+def _reproject_maps(d, w1, h1, rate, K2inv, Tm, K1m):
+    """(n, 2, h1, w1) float32 CUDA tensor of a float64 (n, h2, w2) CUDA depth."""
+    import torch
+    n, h2, w2 = d.shape
+    with torch.cuda.device(d.device):
+        maps = torch.empty((n, 2, h1, w1), dtype=torch.float32, device=d.device)
+        keys = torch.empty((n, h1, w1), dtype=torch.int64, device=d.device)
+        owner = torch.empty((n, h1, w1), dtype=torch.int32, device=d.device)
+        rc = _native.lib().camd_reproject_remap(d.data_ptr(), w2, h2, h2 * w2, K2inv.ctypes.data, Tm.ctypes.data,
+                                                K1m.ctypes.data, rate, w1, h1, maps.data_ptr(),
+                                                maps.data_ptr() + 4 * h1 * w1, 2 * h1 * w1, keys.data_ptr(),
+                                                owner.data_ptr(), n, _native.current_stream())
+    _native.check(rc, "get_reproject_remap")
+    return maps
+
+
+def get_reproject_remap(K1, K2, T_2in1, depth2, xy1, interpolation_rate=1):
+    """(mapx, mapy) = (2, h1, w1) float32: where each pixel of camera 1 finds itself in camera 2's image, through
+    camera 2's depth; -1 where nothing landed (utils.py:332-344).  ``depth2`` (n, h2, w2) -> (n, 2, h1, w1).
+    uint16 depth is millimetres."""
+    name = _check_depth2(depth2)
+    args = _reproject_args(K1, K2, T_2in1, xy1, interpolation_rate)
+    was_np = isinstance(depth2, np.ndarray)
+    d = _depth_to_dev(depth2, name)
+    batched = d.dim() == 3
+    maps = _reproject_maps(d if batched else d[None], *args)
+    maps = maps if batched else maps[0]
+    return hostio.to_host(maps) if was_np else maps
+
+
+def reproject_img(img2, depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
+    """Camera 2's image in camera 1's frame: ``get_reproject_remap`` then ``cv2.remap(img2, mapx, mapy,
+    cv2.INTER_LINEAR)`` (camera.py:333-341).  ``img2`` uint8 (h2, w2) or (h2, w2, 3) with ``depth2`` (h2, w2); a batch
+    is ``depth2`` (n, h2, w2) with ``img2`` (n, h2, w2) or (n, h2, w2, 3).  Pixels nothing reaches are 0."""
+    from . import imgproc
+    name = _check_depth2(depth2)
+    _check_array(img2, "img2")
+    if _dtype_name(img2) != "uint8":
+        raise ValueError("img2 must be uint8, got %s" % _dtype_name(img2))
+    batched = len(depth2.shape) == 3
+    ishape, dshape = tuple(img2.shape), tuple(depth2.shape)
+    if not (ishape == dshape or ishape == dshape + (3,)):
+        raise ValueError("img2 %s does not match depth2 %s: expected the depth's shape, or that with 3 channels"
+                         % (ishape, dshape))
+    _same_device(img2, depth2, "img2 and depth2")
+    args = _reproject_args(K1, K2, T_2in1, xy1, interpolation_rate)
+    was_np = isinstance(img2, np.ndarray)
+    import torch
+    d = _depth_to_dev(depth2, name)
+    img = _keep_dtype_to_dev(img2, d.device)
+    maps = _reproject_maps(d if batched else d[None], *args)
+    imgs = img if batched else img[None]
+    out = torch.stack([imgproc.remap(imgs[i], maps[i, 0], maps[i, 1], imgproc.INTER_LINEAR) for i in range(len(imgs))])
+    out = out if batched else out[0]
+    return hostio.to_host(out) if was_np else out

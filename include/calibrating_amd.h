@@ -257,6 +257,35 @@ int camd_point_cloud_to_depth(const double* points, size_t n, int point_stride, 
 int camd_project_depth(const double* depth2, int w2, int h2, const double K2inv_host[9],
                        const double T_2in1_host[16], const double K1_host[9], double rate, int w1, int h1,
                        double* depth1, unsigned long long* keys_ws, void* stream);
+/* ---- the z-buffer with a payload: what the nearest point CARRIES arrives in the pixel ---------------------------
+ * Both entry points below run three passes over scratch the caller provides: keys_ws (8 bytes per target pixel and
+ * image: atomicMin of an order-preserving key of the projected z), owner_ws (4 bytes per target pixel and image:
+ * atomicMax of 1 + the index of the sources that hold that key), then one gather per target pixel.  Points that
+ * share a pixel AND have bit-equal z: the larger index wins (index = row-major cell of the sampling grid / row of the
+ * point array) -- a stable far-to-near sort followed by the reference's last-write-wins; np.argsort's default sort
+ * leaves that case to its internals.  Identical calls give identical bits.
+ *
+ * replaces utils.get_reproject_remap (utils.py:332-344): depth_to_point_cloud(return_xyzuv) -> apply_T_to_point_cloud
+ * -> point_cloud_to_arr2d(values = np.float32(uv), bg_value = -1), without materialising the cloud.  depth2: f64
+ * [batch][h2][w2], image b at depth2 + b * depth_stride (doubles); K2inv, T_2in1 (4x4), K1: row-major host doubles
+ * shared by the batch; rate: the interpolation rate of camd_point_cloud_grid.  mapx / mapy: f32 [h1][w1] planes, image
+ * b at + b * map_stride (floats): where camera 1's pixel finds its colour in camera 2's image (feed them to
+ * camd_remap_u8(..., CAMD_INTER_LINEAR), camera.py:341), -1 where nothing landed.  keys_ws: batch * w1 * h1 * 8 bytes,
+ * owner_ws: batch * w1 * h1 * 4 bytes.  batch <= 65535; a sampling grid of >= 2^32 - 1 cells is CAMD_ERR_BAD_ARG.   */
+int camd_reproject_remap(const double* depth2, int w2, int h2, size_t depth_stride, const double K2inv_host[9],
+                         const double T_2in1_host[16], const double K1_host[9], double rate, int w1, int h1,
+                         float* mapx, float* mapy, size_t map_stride, unsigned long long* keys_ws,
+                         uint32_t* owner_ws, int batch, void* stream);
+/* replaces utils.point_cloud_to_arr2d with values (utils.py:254-288, scatter in uvzs_to_arr2d :291-317): project with
+ * K, round half-to-even to a pixel, the values row of the nearest point wins.  points: f64 rows of point_stride >= 3
+ * doubles, n < 2^32 - 1; NaN / inf / out-of-image projections are dropped.
+ * values: [n][channels] of value_type, channels >= 1, contiguous; out: [h][w][channels] of the same type; pixels
+ * nobody reaches get bg_value cast to that type (for CAMD_VALUE_U8 it must be an integer in 0..255).
+ * keys_ws: w * h * 8 bytes, owner_ws: w * h * 4 bytes.                                                            */
+enum { CAMD_VALUE_F64 = 0, CAMD_VALUE_F32 = 1, CAMD_VALUE_U8 = 2 };
+int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, const double K_host[9], int w, int h,
+                              const void* values, int channels, int value_type, double bg_value, void* out,
+                              unsigned long long* keys_ws, uint32_t* owner_ws, void* stream);
 
 #ifdef __cplusplus
 }
