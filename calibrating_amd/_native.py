@@ -32,7 +32,8 @@ MODE_HH4 = 3
 INTER_NEAREST = 0
 INTER_LINEAR = 1
 INTER_LANCZOS4 = 4
-VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_arr2d
+VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_arr2d / camd_uvzs_to_arr2d
+NEAREST_MAX_RADIUS = 32  # CAMD_NEAREST_MAX_RADIUS
 
 
 class SgbmParams(ctypes.Structure):
@@ -86,6 +87,23 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
     "camd_point_cloud_to_arr2d": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                           c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_uvzs_to_arr2d": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double, c_int, c_void_p,
+                                   c_void_p, c_void_p]),
+    "camd_arr2d_to_uvzs": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_arr2d_mask_workspace_bytes": (c_size_t, [c_int]),
+    "camd_arr2d_to_uvzs_masked": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                          c_void_p]),
+    "camd_sparse_bin_grid": (c_int, [c_int, c_int, c_double] + [ctypes.POINTER(c_int)] * 3),
+    "camd_sparse_bin_count": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_void_p, c_void_p]),
+    "camd_sparse_bin_fill": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_void_p]),
+    "camd_nearest_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int,
+                                  c_int, c_void_p]),
+    "camd_plane_sums_blocks": (c_int, [c_size_t]),
+    "camd_plane_sums": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "camd_plane_eval": (c_int, [c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p]),
+    "camd_matched_uvs_to_zs": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
     "camd_set_global_option": (c_int, [c_int, c_int]),
     "camd_lanczos4_table_host": (c_int, [c_void_p]),
     "camd_bilinear_table_host": (c_int, [c_void_p]),

@@ -1,0 +1,562 @@
+// sparse.hip -- sparse (u, v, z) samples <-> dense images: the family behind the reference's FeatureMatchingAsStereoMatching
+// (stereo_matching.py:113-142) and MatchingByBoard:
+//   utils.uvzs_to_arr2d        (utils.py:291-317)   scatter with NumPy's last-write-wins
+//   utils.arr2d_to_uvzs        (utils.py:320-329)   image -> (x, y, value) rows, all pixels or the masked ones
+//   utils.interpolate_uvzs     (utils.py:356-415)   "nearest": SciPy KDTree.query per pixel  -> bins + bounded window search
+//                                                    "lstsq":   np.linalg.lstsq plane       -> nine sums + evaluation
+//   epipolar_geometry.matched_xyz_normals_to_zs (:88-97) with uvs_to_xyz_noramls (:84-85): depth of matches along both rays
+// float64 like the reference's NumPy; products and sums are individually rounded (-ffp-contract=off) except where a
+// fused multiply-add is written out.  Nothing here depends on the order in which atomics are served: the scatter keeps
+// an integer maximum, the bins are filled in any order and searched by the key (distance, index), the plane sums are
+// reduced in a fixed order without float atomics.
+#include "common.hpp"
+
+#include <cmath>
+
+namespace camd {
+
+constexpr int SP_MAX_RADIUS = CAMD_NEAREST_MAX_RADIUS;
+constexpr int PL_MAX_BLOCKS = 1024;
+
+// ---- a. scatter ------------------------------------------------------------------------------------------------------
+// xs, ys = np.int32(uvs.round()) (half to even); rows outside the image -- NaN and inf among them -- are dropped (:312-313)
+__device__ __forceinline__ bool sp_pixel(const double* __restrict__ uv, size_t i, int stride, int w, int h, size_t* pix)
+{
+    const double ru = rint(uv[i * stride]), rv = rint(uv[i * stride + 1]);
+    if (!(ru >= 0.0 && ru < (double)w && rv >= 0.0 && rv < (double)h)) return false;
+    *pix = (size_t)(int)rv * w + (int)ru;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_sp_clear_u32(uint32_t* __restrict__ p, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = 0u;
+}
+
+// owner[pix] = 1 + the largest row index landing there: arr2d[ys, xs] = values assigns in row order, the last one stays
+__global__ __launch_bounds__(256) void k_sp_owner(const double* __restrict__ uv, size_t n, int stride, int w, int h,
+                                                  uint32_t* __restrict__ owner)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    size_t pix;
+    if (sp_pixel(uv, i, stride, w, h, &pix)) atomicMax(owner + pix, (uint32_t)i + 1u);
+}
+
+// keep != 0: a caller's arr2d is updated in place, pixels nobody reaches are left alone
+template <typename V>
+__global__ __launch_bounds__(256) void k_sp_gather(const uint32_t* __restrict__ owner, size_t npix,
+                                                   const V* __restrict__ values, int channels, V bg, int keep,
+                                                   V* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npix) return;
+    const uint32_t o = owner[i];
+    if (o) {
+        const V* src = values + (size_t)(o - 1u) * channels;
+        for (int c = 0; c < channels; c++) out[i * channels + c] = src[c];
+    } else if (!keep) {
+        for (int c = 0; c < channels; c++) out[i * channels + c] = bg;
+    }
+}
+
+// ---- b. arr2d_to_uvzs ------------------------------------------------------------------------------------------------
+// np.array([xs, ys, arr2d]).T.reshape(-1, 3): row r = x * h + y holds (x, y, arr2d[y, x]).  O = double or int64: what
+// NumPy's promotion of the int64 grids with arr2d gives; the caller hands arr2d over in that type.
+template <typename O>
+__global__ __launch_bounds__(256) void k_sp_all_rows(const O* __restrict__ arr, int w, int h, O* __restrict__ rows)
+{
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= (size_t)w * h) return;
+    const int x = (int)(r / (size_t)h), y = (int)(r % (size_t)h);
+    rows[r * 3 + 0] = (O)x;
+    rows[r * 3 + 1] = (O)y;
+    rows[r * 3 + 2] = arr[(size_t)y * w + x];
+}
+
+__global__ __launch_bounds__(256) void k_sp_mask_count(const uint8_t* __restrict__ mask, int w, uint32_t* __restrict__ rowcount)
+{
+    __shared__ uint32_t part[4];
+    const int y = blockIdx.x;
+    uint32_t c = 0;
+    for (int x = threadIdx.x; x < w; x += 256) c += mask[(size_t)y * w + x] ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) rowcount[y] = part[0] + part[1] + part[2] + part[3];
+}
+
+// exclusive scan of the row counts (one workgroup; rows <= a few thousand)
+__global__ __launch_bounds__(256) void k_sp_mask_scan(const uint32_t* __restrict__ rowcount, int n,
+                                                      unsigned long long* __restrict__ rowoff,
+                                                      unsigned long long* __restrict__ total)
+{
+    __shared__ unsigned long long carry;
+    __shared__ unsigned long long wsum[4];
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + threadIdx.x;
+        unsigned long long v = i < n ? rowcount[i] : 0ull, incl = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            unsigned long long t = __shfl_up(incl, o);
+            if ((threadIdx.x & 63) >= o) incl += t;
+        }
+        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) before += wsum[k];
+        if (i < n) rowoff[i] = before + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 255) carry = before + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// np.array([xs[mask], ys[mask], arr2d[mask]]).T: the masked pixels in row-major order
+template <typename O>
+__global__ __launch_bounds__(256) void k_sp_mask_emit(const O* __restrict__ arr, const uint8_t* __restrict__ mask, int w,
+                                                      const unsigned long long* __restrict__ rowoff, O* __restrict__ rows,
+                                                      size_t capacity)
+{
+    __shared__ uint32_t wcnt[4];
+    __shared__ unsigned long long run;
+    const int y = blockIdx.x;
+    if (threadIdx.x == 0) run = rowoff[y];
+    __syncthreads();
+    for (int base = 0; base < w; base += 256) {
+        const int x = base + threadIdx.x;
+        const bool on = x < w && mask[(size_t)y * w + x] != 0;
+        const unsigned long long bal = __ballot(on);
+        const uint32_t below = __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
+        if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(bal);
+        __syncthreads();
+        unsigned long long pos = run + below;
+        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) pos += wcnt[k];
+        if (on && pos < capacity) {
+            rows[pos * 3 + 0] = (O)x;
+            rows[pos * 3 + 1] = (O)y;
+            rows[pos * 3 + 2] = arr[(size_t)y * w + x];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+// ---- c. nearest fill -------------------------------------------------------------------------------------------------
+// A sample (u, v) lies in the integer cell (floor(u), floor(v)).  A pixel x can only be nearer than `distance` <= R to
+// samples with x - R < u < x + R, i.e. cells x - R .. x + R - 1 (the float64 difference x - u is monotonic in u and R is
+// representable, so rounding cannot move a sample across that bound).  Cells -R .. w + R - 2 therefore serve every pixel
+// of a w-wide grid: bins_w = w + 2R - 1, bins_h = h + 2R - 1; samples in no such cell cannot be anybody's answer.
+struct SpBins {
+    int w, h, R, bw, bh;
+};
+
+__device__ __forceinline__ bool sp_cell(const double* __restrict__ uv, size_t i, int stride, const SpBins& b, uint32_t* cell)
+{
+    const double fu = floor(uv[i * stride]), fv = floor(uv[i * stride + 1]);
+    if (!(fu >= (double)-b.R && fu <= (double)(b.w + b.R - 2) && fv >= (double)-b.R && fv <= (double)(b.h + b.R - 2)))
+        return false;  // (also NaN / inf)
+    *cell = (uint32_t)((int)fv + b.R) * (uint32_t)b.bw + (uint32_t)((int)fu + b.R);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_sp_bin_count(const double* __restrict__ uv, size_t n, int stride, SpBins b,
+                                                      uint32_t* __restrict__ counts)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t cell;
+    if (sp_cell(uv, i, stride, b, &cell)) atomicAdd(counts + cell, 1u);
+}
+
+// cursor starts as the exclusive scan of the counts; the slot order inside a cell is whatever the atomics give
+__global__ __launch_bounds__(256) void k_sp_bin_fill(const double* __restrict__ uv, size_t n, int stride, SpBins b,
+                                                     uint32_t* __restrict__ cursor, size_t capacity,
+                                                     double* __restrict__ sorted_uv, uint32_t* __restrict__ sorted_idx)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t cell;
+    if (!sp_cell(uv, i, stride, b, &cell)) return;
+    const uint32_t slot = atomicAdd(cursor + cell, 1u);
+    if (slot >= capacity) return;
+    sorted_uv[(size_t)slot * 2 + 0] = uv[i * stride];
+    sorted_uv[(size_t)slot * 2 + 1] = uv[i * stride + 1];
+    sorted_idx[slot] = (uint32_t)i;
+}
+
+struct SpOut {
+    int ow, oh;        // the image written; == the grid unless upsized
+    int scaled;
+    double ifx, ify;   // cv2.resize(INTER_NEAREST): sx = min(floor(x * ifx), w - 1), as pc_sample in pointcloud.hip
+    float mul, div;    // stereo_matching.py:139: disparity * hw[1] / resize_shape[1], two float32 roundings
+};
+
+// One thread per output pixel, a wave = 64 consecutive pixels of a row: neighbouring lanes walk the same cells.  The
+// 2R cells of one bin row that a pixel needs are adjacent, so each bin row is one contiguous run of sorted samples.
+// Both loops are bounded by input sizes (2R rows, the samples binned into them).
+template <typename Z>
+__global__ __launch_bounds__(256) void k_sp_nearest(const double* __restrict__ sorted_uv, const uint32_t* __restrict__ sorted_idx,
+                                                    const uint32_t* __restrict__ start, const Z* __restrict__ z, SpBins b,
+                                                    double distance, SpOut o, float* __restrict__ out)
+{
+    const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
+    if (X >= o.ow) return;
+    int x = X, y = Y;
+    if (o.scaled) {
+        x = min((int)floor(X * o.ifx), b.w - 1);
+        y = min((int)floor(Y * o.ify), b.h - 1);
+    }
+    const double px = (double)x, py = (double)y;
+    double best = INFINITY;
+    uint32_t best_i = 0xffffffffu;
+    for (int r = 0; r < 2 * b.R; r++) {
+        const size_t row = (size_t)(y + r) * b.bw;  // bin row of cell y - R + r
+        const uint32_t s = start[row + x], e = start[row + x + 2 * b.R];
+        for (uint32_t k = s; k < e; k++) {
+            const double dx = px - sorted_uv[(size_t)k * 2], dy = py - sorted_uv[(size_t)k * 2 + 1];
+            const double d = __dsqrt_rn(dx * dx + dy * dy);
+            const uint32_t i = sorted_idx[k];
+            if (d < best || (d == best && i < best_i)) { best = d; best_i = i; }
+        }
+    }
+    float v = 0.0f;
+    if (best < distance) v = (float)z[best_i];
+    if (o.scaled) v = __fdiv_rn(__fmul_rn(v, o.mul), o.div);
+    out[(size_t)Y * o.ow + X] = v;
+}
+
+// ---- d. plane fit ----------------------------------------------------------------------------------------------------
+// sums: 0 uu  1 uv  2 u  3 vv  4 v  5 n  6 uz  7 vz  8 z.  Thread t of block g adds rows g*256+t, +G*256, ... in that
+// order; the block adds its 256 threads by a fixed tree; k_sp_plane_final adds the G partials in index order.
+template <typename Z>
+__global__ __launch_bounds__(256) void k_sp_plane_partials(const double* __restrict__ uv, int stride, const Z* __restrict__ z,
+                                                           size_t n, double* __restrict__ partials)
+{
+    __shared__ double sh[256];
+    double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const double u = uv[i * stride], v = uv[i * stride + 1], zz = (double)z[i];
+        s[0] += u * u; s[1] += u * v; s[2] += u;
+        s[3] += v * v; s[4] += v;     s[5] += 1.0;
+        s[6] += u * zz; s[7] += v * zz; s[8] += zz;
+    }
+    for (int q = 0; q < 9; q++) {
+        sh[threadIdx.x] = s[q];
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) partials[(size_t)blockIdx.x * 9 + q] = sh[0];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(64) void k_sp_plane_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
+{
+    if (threadIdx.x >= 9) return;
+    double a = 0.0;
+    for (int g = 0; g < nblocks; g++) a += partials[(size_t)g * 9 + threadIdx.x];
+    sums[threadIdx.x] = a;
+}
+
+// utils.py:394-396: float32 of the float64 product (x, y, 1) @ abc
+__global__ __launch_bounds__(256) void k_sp_plane_eval(double a, double bb, double c, int w, float* __restrict__ out)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    out[(size_t)y * w + x] = (float)__fma_rn(1.0, c, __fma_rn((double)y, bb, __dmul_rn((double)x, a)));
+}
+
+// ---- e. triangulation of matches -------------------------------------------------------------------------------------
+struct SpTri {
+    double k1[9], k2[9], R[9], t[3];
+};
+
+// a * b - c * d with the rounding error of c * d carried along (Kahan): exact to ~1.5 ulp without cancellation loss
+__device__ __forceinline__ double diff_of_products(double a, double b, double c, double d)
+{
+    const double w = c * d;
+    const double e = __fma_rn(-c, d, w);
+    const double f = __fma_rn(a, b, -w);
+    return f + e;
+}
+__device__ __forceinline__ void cross3(const double* p, const double* q, double* r)
+{
+    r[0] = diff_of_products(p[1], q[2], p[2], q[1]);
+    r[1] = diff_of_products(p[2], q[0], p[0], q[2]);
+    r[2] = diff_of_products(p[0], q[1], p[1], q[0]);
+}
+
+// X2 z2 = R X1 z1 + t  ->  [a, b] (z1, z2)^T = t with a = -R X1, b = X2.  The 2x2 normal equations
+//   (a.a) z1 + (a.b) z2 = a.t,  (a.b) z1 + (b.b) z2 = b.t
+// have, by Lagrange's identity, the closed form z1 = (a x b).(t x b) / |a x b|^2, z2 = (a x b).(a x t) / |a x b|^2.
+// That form is evaluated: for the near-parallel rays of a stereo rig the determinant (a.a)(b.b) - (a.b)^2 loses
+// sin^-2 of the angle between the rays in digits, the cross product only sin^-1.
+__global__ __launch_bounds__(256) void k_sp_triangulate(const double* __restrict__ uv1, const double* __restrict__ uv2,
+                                                        size_t n, SpTri m, double* __restrict__ zs1, double* __restrict__ zs2)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double u1 = uv1[i * 2], v1 = uv1[i * 2 + 1], u2 = uv2[i * 2], v2 = uv2[i * 2 + 1];
+    double x1[3], a[3], b[3], axb[3], txb[3], axt[3];
+    for (int r = 0; r < 3; r++) {
+        x1[r] = __fma_rn(m.k1[r * 3 + 2], 1.0, __fma_rn(m.k1[r * 3 + 1], v1, m.k1[r * 3] * u1));
+        b[r] = __fma_rn(m.k2[r * 3 + 2], 1.0, __fma_rn(m.k2[r * 3 + 1], v2, m.k2[r * 3] * u2));
+    }
+    for (int r = 0; r < 3; r++)
+        a[r] = -__fma_rn(m.R[r * 3 + 2], x1[2], __fma_rn(m.R[r * 3 + 1], x1[1], m.R[r * 3] * x1[0]));
+    cross3(a, b, axb);
+    cross3(m.t, b, txb);
+    cross3(a, m.t, axt);
+    const double den = __fma_rn(axb[2], axb[2], __fma_rn(axb[1], axb[1], axb[0] * axb[0]));
+    zs1[i] = __fma_rn(axb[2], txb[2], __fma_rn(axb[1], txb[1], axb[0] * txb[0])) / den;
+    zs2[i] = __fma_rn(axb[2], axt[2], __fma_rn(axb[1], axt[1], axb[0] * axt[0])) / den;
+}
+
+static int make_bins(SpBins* b, int w, int h, double distance, const char* who)
+{
+    if (w <= 0 || h <= 0) { set_error("%s: bad grid size %d x %d", who, w, h); return CAMD_ERR_BAD_ARG; }
+    if (!(distance == distance) || distance > (double)SP_MAX_RADIUS) {
+        set_error("%s: distance %g needs a search window beyond the supported %d cells each way (distance <= %d)", who,
+                  distance, SP_MAX_RADIUS, SP_MAX_RADIUS);
+        return CAMD_ERR_UNSUPPORTED;
+    }
+    int R = distance > 1.0 ? (int)ceil(distance) : 1;  // (distance <= 0: nothing is ever nearer, the window may be minimal)
+    b->w = w; b->h = h; b->R = R; b->bw = w + 2 * R - 1; b->bh = h + 2 * R - 1;
+    if ((unsigned long long)b->bw * (unsigned long long)b->bh >= 0x7fffffffull || h > 65535) {
+        set_error("%s: a %d x %d grid is beyond the 32-bit cell index / 65535 rows", who, w, h);
+        return CAMD_ERR_UNSUPPORTED;
+    }
+    return CAMD_OK;
+}
+
+static bool value_type_ok(int t) { return t == CAMD_VALUE_F64 || t == CAMD_VALUE_F32 || t == CAMD_VALUE_U8; }
+
+}  // namespace camd
+
+using namespace camd;
+
+extern "C" {
+
+int camd_uvzs_to_arr2d(const double* uv, size_t n, int uv_stride, int w, int h, const void* values, int channels,
+                       int value_type, double bg_value, int keep, void* out, uint32_t* owner_ws, void* stream)
+{
+    if (!out || !owner_ws || w <= 0 || h <= 0 || uv_stride < 2 || channels < 1 || (n && (!uv || !values))) {
+        set_error("camd_uvzs_to_arr2d: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (!value_type_ok(value_type)) {
+        set_error("camd_uvzs_to_arr2d: value_type %d is none of float64 / float32 / uint8", value_type);
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (value_type == CAMD_VALUE_U8 && !keep && !(bg_value >= 0.0 && bg_value <= 255.0 && bg_value == (double)(uint8_t)bg_value)) {
+        set_error("camd_uvzs_to_arr2d: bg_value %g is not a uint8", bg_value);
+        return CAMD_ERR_BAD_ARG;
+    }
+    if ((unsigned long long)n >= 0xffffffffull) {
+        set_error("camd_uvzs_to_arr2d: %zu rows do not fit the 32-bit owner index", n);
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npix = (size_t)w * h;
+    const dim3 dst_grid(div_up((long long)npix, 256));
+    hipLaunchKernelGGL(k_sp_clear_u32, dst_grid, dim3(256), 0, st, owner_ws, npix);
+    if (n) hipLaunchKernelGGL(k_sp_owner, dim3(div_up((long long)n, 256)), dim3(256), 0, st, uv, n, uv_stride, w, h, owner_ws);
+    if (value_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_sp_gather<double>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const double*)values, channels,
+                           bg_value, keep, (double*)out);
+    else if (value_type == CAMD_VALUE_F32)
+        hipLaunchKernelGGL((k_sp_gather<float>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const float*)values, channels,
+                           (float)bg_value, keep, (float*)out);
+    else
+        hipLaunchKernelGGL((k_sp_gather<uint8_t>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const uint8_t*)values, channels,
+                           keep ? (uint8_t)0 : (uint8_t)bg_value, keep, (uint8_t*)out);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_arr2d_to_uvzs(const void* arr2d, int w, int h, int as_int64, void* rows, void* stream)
+{
+    if (!arr2d || !rows || w <= 0 || h <= 0) { set_error("camd_arr2d_to_uvzs: bad arguments"); return CAMD_ERR_BAD_ARG; }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    const dim3 grid(div_up((long long)w * h, 256));
+    if (as_int64)
+        hipLaunchKernelGGL((k_sp_all_rows<long long>), grid, dim3(256), 0, (hipStream_t)stream, (const long long*)arr2d, w, h,
+                           (long long*)rows);
+    else
+        hipLaunchKernelGGL((k_sp_all_rows<double>), grid, dim3(256), 0, (hipStream_t)stream, (const double*)arr2d, w, h,
+                           (double*)rows);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+size_t camd_arr2d_mask_workspace_bytes(int h) { return h > 0 ? (size_t)h * (4 + 8) + 64 : 0; }
+
+int camd_arr2d_to_uvzs_masked(const void* arr2d, const uint8_t* mask, int w, int h, int as_int64, void* rows,
+                              size_t capacity, unsigned long long* count, void* workspace, void* stream)
+{
+    if (!arr2d || !mask || !rows || !count || !workspace || w <= 0 || h <= 0) {
+        set_error("camd_arr2d_to_uvzs_masked: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* rowoff = reinterpret_cast<unsigned long long*>(workspace);
+    uint32_t* rowcount = reinterpret_cast<uint32_t*>(rowoff + h);
+    hipLaunchKernelGGL(k_sp_mask_count, dim3(h), dim3(256), 0, st, mask, w, rowcount);
+    hipLaunchKernelGGL(k_sp_mask_scan, dim3(1), dim3(256), 0, st, rowcount, h, rowoff, count);
+    if (as_int64)
+        hipLaunchKernelGGL((k_sp_mask_emit<long long>), dim3(h), dim3(256), 0, st, (const long long*)arr2d, mask, w, rowoff,
+                           (long long*)rows, capacity);
+    else
+        hipLaunchKernelGGL((k_sp_mask_emit<double>), dim3(h), dim3(256), 0, st, (const double*)arr2d, mask, w, rowoff,
+                           (double*)rows, capacity);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_sparse_bin_grid(int w, int h, double distance, int* radius, int* bins_w, int* bins_h)
+{
+    SpBins b;
+    int rc = make_bins(&b, w, h, distance, "camd_sparse_bin_grid");
+    if (rc != CAMD_OK) return rc;
+    if (radius) *radius = b.R;
+    if (bins_w) *bins_w = b.bw;
+    if (bins_h) *bins_h = b.bh;
+    return CAMD_OK;
+}
+
+int camd_sparse_bin_count(const double* uv, size_t n, int uv_stride, int w, int h, double distance, uint32_t* counts,
+                          void* stream)
+{
+    SpBins b;
+    int rc = make_bins(&b, w, h, distance, "camd_sparse_bin_count");
+    if (rc != CAMD_OK) return rc;
+    if (!counts || uv_stride < 2 || (n && !uv) || (unsigned long long)n >= 0xffffffffull) {
+        set_error("camd_sparse_bin_count: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ncell = (size_t)b.bw * b.bh;
+    hipLaunchKernelGGL(k_sp_clear_u32, dim3(div_up((long long)ncell, 256)), dim3(256), 0, st, counts, ncell);
+    if (n) hipLaunchKernelGGL(k_sp_bin_count, dim3(div_up((long long)n, 256)), dim3(256), 0, st, uv, n, uv_stride, b, counts);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_sparse_bin_fill(const double* uv, size_t n, int uv_stride, int w, int h, double distance, uint32_t* cursor,
+                         size_t capacity, double* sorted_uv, uint32_t* sorted_idx, void* stream)
+{
+    SpBins b;
+    int rc = make_bins(&b, w, h, distance, "camd_sparse_bin_fill");
+    if (rc != CAMD_OK) return rc;
+    if (!cursor || uv_stride < 2 || (n && (!uv || !sorted_uv || !sorted_idx)) || (unsigned long long)n >= 0xffffffffull) {
+        set_error("camd_sparse_bin_fill: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (n == 0) return CAMD_OK;
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_sp_bin_fill, dim3(div_up((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, uv, n, uv_stride, b,
+                       cursor, capacity, sorted_uv, sorted_idx);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_nearest_fill(const double* sorted_uv, const uint32_t* sorted_idx, const uint32_t* start, const void* z, int z_type,
+                      int w, int h, double distance, float* out, int out_w, int out_h, void* stream)
+{
+    SpBins b;
+    int rc = make_bins(&b, w, h, distance, "camd_nearest_fill");
+    if (rc != CAMD_OK) return rc;
+    if (!start || !out || out_w <= 0 || out_h <= 0 || out_h > 65535 || (z_type != CAMD_VALUE_F64 && z_type != CAMD_VALUE_F32)) {
+        set_error("camd_nearest_fill: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    SpOut o;
+    o.ow = out_w; o.oh = out_h;
+    o.scaled = (out_w != w || out_h != h) ? 1 : 0;
+    o.ifx = 1.0 / ((double)out_w / w);  // cv2.resize: inv_scale = dsize / ssize, ifx = 1 / inv_scale
+    o.ify = 1.0 / ((double)out_h / h);
+    o.mul = (float)out_w; o.div = (float)w;
+    const dim3 grid(div_up(out_w, 256), out_h);
+    if (z_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_sp_nearest<double>), grid, dim3(256), 0, (hipStream_t)stream, sorted_uv, sorted_idx, start,
+                           (const double*)z, b, distance, o, out);
+    else
+        hipLaunchKernelGGL((k_sp_nearest<float>), grid, dim3(256), 0, (hipStream_t)stream, sorted_uv, sorted_idx, start,
+                           (const float*)z, b, distance, o, out);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_plane_sums_blocks(size_t n)
+{
+    const long long g = (long long)((n + 255) / 256);
+    return (int)(g < 1 ? 1 : g > PL_MAX_BLOCKS ? PL_MAX_BLOCKS : g);
+}
+
+int camd_plane_sums(const double* uv, int uv_stride, const void* z, int z_type, size_t n, double* partials_ws, double* sums,
+                    void* stream)
+{
+    if (!uv || !z || !partials_ws || !sums || n == 0 || uv_stride < 2 || (z_type != CAMD_VALUE_F64 && z_type != CAMD_VALUE_F32)) {
+        set_error("camd_plane_sums: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int g = camd_plane_sums_blocks(n);
+    if (z_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_sp_plane_partials<double>), dim3(g), dim3(256), 0, st, uv, uv_stride, (const double*)z, n, partials_ws);
+    else
+        hipLaunchKernelGGL((k_sp_plane_partials<float>), dim3(g), dim3(256), 0, st, uv, uv_stride, (const float*)z, n, partials_ws);
+    hipLaunchKernelGGL(k_sp_plane_final, dim3(1), dim3(64), 0, st, partials_ws, g, sums);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_plane_eval(double a, double b, double c, int w, int h, float* out, void* stream)
+{
+    if (!out || w <= 0 || h <= 0 || h > 65535) { set_error("camd_plane_eval: bad arguments"); return CAMD_ERR_BAD_ARG; }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_sp_plane_eval, dim3(div_up(w, 256), h), dim3(256), 0, (hipStream_t)stream, a, b, c, w, out);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_matched_uvs_to_zs(const double* uv1, const double* uv2, size_t n, const double K1inv[9], const double K2inv[9],
+                           const double T_1to2[16], double* zs1, double* zs2, void* stream)
+{
+    if (!K1inv || !K2inv || !T_1to2 || (n && (!uv1 || !uv2 || !zs1 || !zs2))) {
+        set_error("camd_matched_uvs_to_zs: NULL argument");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (n == 0) return CAMD_OK;
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    SpTri m;
+    for (int i = 0; i < 9; i++) { m.k1[i] = K1inv[i]; m.k2[i] = K2inv[i]; m.R[i] = T_1to2[(i / 3) * 4 + i % 3]; }
+    for (int i = 0; i < 3; i++) m.t[i] = T_1to2[i * 4 + 3];
+    hipLaunchKernelGGL(k_sp_triangulate, dim3(div_up((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, uv1, uv2, n, m,
+                       zs1, zs2);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@ the bodies are this package's own: rig geometry lives in ``geometry.py`` as pure
   rectify                             :216-242   -> imgproc.remap (Lanczos-4 kernel, x-shift fused)
   set_stereo_matching                 :466-489
   get_depth                           :492-533   -> kernels, every intermediate stays in HBM
+  get_depth_by_matched_uvs            :535-540   -> sparse.matched_uvs_to_zs
   disparity_to_depth                  :408-413
   unrectify_depth                     :415-428   -> imgproc.unrectify_depth
   undistort_img                       :430-431   -> imgproc.remap_fixed_bilinear
@@ -528,8 +529,12 @@ class Stereo:
             sdisp16, _ = plugin.compute_disp16(rectify_img1, rectify_img2)
             disparity, rectify_depth = self._fused_depth(plugin, sdisp16, tb, rectify_img1.shape[:2])
         else:
-            # foreign plugin: the reference's contract is NumPy in, NumPy (or dict) out
-            disparity = plugin(*hostio.to_host(rectify_img1, rectify_img2))
+            if getattr(plugin, "accepts_device_tensors", False):
+                # opt-in (stereo_matching.py): the plugin takes the rectified CUDA tensors and may answer with one
+                disparity = plugin(rectify_img1, rectify_img2)
+            else:
+                # foreign plugin: the reference's contract is NumPy in, NumPy (or dict) out
+                disparity = plugin(*hostio.to_host(rectify_img1, rectify_img2))
             if isinstance(disparity, dict):
                 result.update({k: v for k, v in disparity.items() if k != "disparity"})
                 disparity = disparity["disparity"]
@@ -555,6 +560,17 @@ class Stereo:
             if isinstance(plugin, SemiGlobalBlockMatching):
                 plugin.stereo_sgbm.status()  # collect() synchronised: surface device-side timeouts at no extra cost
         return result
+
+    def get_depth_by_matched_uvs(self, uvs1, uvs2):
+        """``dict(zs1, zs2)``: the depth of matched pixels ``uvs1`` (camera 1) / ``uvs2`` (camera 2), (n, 2) each, along
+        their rays -- ``sparse.matched_uvs_to_zs(uvs1, uvs2, cam1.K, cam2.K, [R | t])`` with the rig's full-precision
+        ``R``, ``t`` (not ``Stereo.T``, whose R went through float32).  The reference's method (:535-540) raises
+        ``TypeError`` as written: it calls ``matched_xyz_normals_to_zs`` without its third argument, ``T_1to2``; this is
+        what that callee's signature implies."""
+        from . import sparse
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = self.R, np.asarray(self.t, np.float64).reshape(3)
+        return sparse.matched_uvs_to_zs(uvs1, uvs2, self.cam1.K, self.cam2.K, T)
 
     def get_depth_batch(self, imgs1, imgs2, return_unrectify_depth=True, keys=None, return_distort_depth=False):
         """``get_depth`` for ``n`` pairs of the same rig at once: ``imgs1`` / ``imgs2`` are ``(n, h, w, 3)``

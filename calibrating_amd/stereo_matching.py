@@ -5,6 +5,10 @@
 ``(h, w, 3)`` images; returns ``disparity (h, w)`` in pixels of the input resolution or a dict
 containing ``"disparity"`` (extra keys are merged into ``Stereo.get_depth``'s result,
 stereo_camera.py:506-509).
+
+A plugin whose class sets ``accepts_device_tensors = True`` (not in the reference) is handed the rectified pair as
+torch CUDA tensors by ``Stereo.get_depth`` and may return a CUDA tensor (or a dict holding one); every other plugin
+gets NumPy arrays, as in the reference.  ``FeatureMatchingAsStereoMatching`` (:113-142) is such a plugin.
 """
 import numpy as np
 
@@ -89,3 +93,43 @@ class SemiGlobalBlockMatching(MetaStereoMatching):
         sdisp16, sw = self.compute_disp16(img1, img2)
         disparity = self._disparity_from_disp16(sdisp16, tuple(img1.shape[:2]), sw)
         return hostio.to_host(disparity) if is_np else disparity
+
+
+class FeatureMatchingAsStereoMatching(MetaStereoMatching):
+    """Sparse matches made dense (stereo_matching.py:113-142): ``feature_matching(img1, img2)`` returns a dict with
+    normalised ``uvs1``, ``uvs2`` (n, 2) in [0, 1); they are scaled to the grid ``cfg.get("shape", hw) // downscale``,
+    (u1, v1, u1 - u2) is filled with ``sparse.interpolate_uvzs(..., inter_type="nearest")`` and, when the grid is not
+    the image, blown up to ``hw`` by nearest-neighbour times ``hw[1] / grid[1]`` -- one kernel writes the full-size image.
+    Returns ``dict(disparity=float32 (h, w), matched=<the matcher's dict>)``.
+
+    ``downscale`` (not in the reference, which hard-codes 8 because its KDTree fill took 44 s at full resolution):
+    ``downscale=1`` fills at full resolution.  ``uvs*`` may be NumPy arrays or CUDA tensors; tensors stay on the device
+    and the disparity comes back as a tensor."""
+
+    accepts_device_tensors = True
+
+    def __init__(self, feature_matching, downscale=8):
+        self.feature_matching = feature_matching
+        self.downscale = int(downscale)
+        if self.downscale < 1:
+            raise ValueError("downscale must be a positive integer, got %r" % (downscale,))
+
+    def __call__(self, img1, img2):
+        from . import sparse
+        matched = self.feature_matching(img1, img2)
+        hw = tuple(int(v) for v in img1.shape[:2])
+        resize_shape = self.feature_matching.cfg.get("shape", hw)
+        resize_shape = (resize_shape[0] // self.downscale, resize_shape[1] // self.downscale)
+        uvs1, uvs2 = matched["uvs1"], matched["uvs2"]
+        if isinstance(uvs1, np.ndarray):
+            uvs1, uvs2 = uvs1 * resize_shape[::-1], np.asarray(uvs2) * resize_shape[::-1]
+            uvds = np.concatenate((uvs1, (uvs1 - uvs2)[:, :1]), 1)
+        else:
+            import torch
+            scale = torch.tensor(resize_shape[::-1], dtype=torch.float64, device=uvs1.device)
+            uvs1 = uvs1.to(torch.float64) * scale  # (float64 like NumPy's float * int tuple)
+            uvs2 = torch.as_tensor(uvs2, device=uvs1.device).to(torch.float64) * scale
+            uvds = torch.cat((uvs1, (uvs1 - uvs2)[:, :1]), 1)
+        disparity = sparse.interpolate_uvzs(uvds, resize_shape, constrained_type=None, inter_type="nearest",
+                                            resize_hw=hw if resize_shape != hw else None)
+        return dict(disparity=disparity, matched=matched)

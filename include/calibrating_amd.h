@@ -287,6 +287,59 @@ int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, 
                               const void* values, int channels, int value_type, double bg_value, void* out,
                               unsigned long long* keys_ws, uint32_t* owner_ws, void* stream);
 
+/* ---- sparse samples <-> dense images (csrc/sparse.hip) ----------------------------------------------
+ * The reference's utils.uvzs_to_arr2d / arr2d_to_uvzs / interpolate_uvzs (utils.py:291-415) and
+ * epipolar_geometry.matched_xyz_normals_to_zs (:88-97).  uv: float64 rows of uv_stride >= 2 doubles (u, v, ...).
+ *
+ * replaces uvzs_to_arr2d: pixel = int32(round-half-even(u, v)); rows outside w x h (NaN / inf too) are dropped; of
+ * several rows on one pixel the LARGEST row index wins (NumPy's fancy assignment).  values / out as in
+ * camd_point_cloud_to_arr2d.  keep != 0: out is a caller's image updated in place (pixels nobody reaches are left
+ * alone, bg_value is unused); keep == 0: they get bg_value.  owner_ws: w * h * 4 bytes.  n < 2^32 - 1.        */
+int camd_uvzs_to_arr2d(const double* uv, size_t n, int uv_stride, int w, int h, const void* values, int channels,
+                       int value_type, double bg_value, int keep, void* out, uint32_t* owner_ws, void* stream);
+/* replaces arr2d_to_uvzs without a mask: rows[x * h + y] = (x, y, arr2d[y][x]) -- x outer, y inner, like
+ * np.array([xs, ys, arr2d]).T.reshape(-1, 3).  arr2d and rows are 8-byte elements: float64, or int64 when as_int64.  */
+int camd_arr2d_to_uvzs(const void* arr2d, int w, int h, int as_int64, void* rows, void* stream);
+/* ... with a mask (bytes, non-zero = taken): the masked pixels in row-major order; *count (device) = how many;
+ * rows beyond capacity are not written.  workspace: camd_arr2d_mask_workspace_bytes(h) bytes.                    */
+size_t camd_arr2d_mask_workspace_bytes(int h);
+int camd_arr2d_to_uvzs_masked(const void* arr2d, const uint8_t* mask, int w, int h, int as_int64, void* rows,
+                              size_t capacity, unsigned long long* count, void* workspace, void* stream);
+/* replaces interpolate_uvzs(inter_type="nearest", distance) (KDTree.query per pixel): samples are binned into the
+ * integer cells (floor u, floor v); a pixel searches the cells within R = max(1, ceil(distance)) of it.
+ * distance <= CAMD_NEAREST_MAX_RADIUS, else CAMD_ERR_UNSUPPORTED.  Three calls around ONE exclusive scan that the
+ * caller provides (any scan: it is plumbing):
+ *   camd_sparse_bin_grid  -> R and the bin grid bins_w x bins_h (= w + 2R - 1, h + 2R - 1)
+ *   camd_sparse_bin_count -> counts[bins_w * bins_h] (cleared here)
+ *   caller: start[0] = 0, start[c + 1] = start[c] + counts[c]  (bins_w * bins_h + 1 entries); cursor = copy of start
+ *   camd_sparse_bin_fill  -> sorted_uv [capacity][2], sorted_idx [capacity], capacity >= start[last]; consumes cursor
+ *   camd_nearest_fill     -> out[y][x] = float32(z[i]) of the sample i nearest to (x, y) in float64
+ *                            sqrt(dx*dx + dy*dy) if that is < distance, else 0; equal distances: the LOWEST i.
+ * z: [n] of z_type CAMD_VALUE_F64 / CAMD_VALUE_F32.  out_w x out_h != w x h: the image is the
+ * cv2.resize(INTER_NEAREST) of the w x h fill times out_w / w (float32: * out_w, then / w), written once.
+ * h, out_h <= 65535.                                                                                            */
+enum { CAMD_NEAREST_MAX_RADIUS = 32 };
+int camd_sparse_bin_grid(int w, int h, double distance, int* radius, int* bins_w, int* bins_h);
+int camd_sparse_bin_count(const double* uv, size_t n, int uv_stride, int w, int h, double distance, uint32_t* counts,
+                          void* stream);
+int camd_sparse_bin_fill(const double* uv, size_t n, int uv_stride, int w, int h, double distance, uint32_t* cursor,
+                         size_t capacity, double* sorted_uv, uint32_t* sorted_idx, void* stream);
+int camd_nearest_fill(const double* sorted_uv, const uint32_t* sorted_idx, const uint32_t* start, const void* z,
+                      int z_type, int w, int h, double distance, float* out, int out_w, int out_h, void* stream);
+/* the plane fit of interpolate_uvzs(inter_type="lstsq"): sums[9] (device) = sum of uu, uv, u, vv, v, 1, uz, vz, z over
+ * the n >= 1 samples, reduced in a fixed order (no float atomics: two runs give the same bits).
+ * partials_ws: camd_plane_sums_blocks(n) * 9 doubles.  The caller solves the 3x3 system on the host.             */
+int camd_plane_sums_blocks(size_t n);
+int camd_plane_sums(const double* uv, int uv_stride, const void* z, int z_type, size_t n, double* partials_ws,
+                    double* sums, void* stream);
+/* out[y][x] = float32(x * a + y * b + c) in float64; h <= 65535 */
+int camd_plane_eval(double a, double b, double c, int w, int h, float* out, void* stream);
+/* replaces matched_xyz_normals_to_zs(uvs_to_xyz_noramls(uv1, K1), uvs_to_xyz_noramls(uv2, K2), T_1to2): per match the
+ * least-squares (z1, z2) of [-R X1, X2] (z1, z2)^T = t, X = Kinv (u, v, 1).  uv1, uv2: [n][2] float64 contiguous.  */
+int camd_matched_uvs_to_zs(const double* uv1, const double* uv2, size_t n, const double K1inv_host[9],
+                           const double K2inv_host[9], const double T_1to2_host[16], double* zs1, double* zs2,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
