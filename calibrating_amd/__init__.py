@@ -11,7 +11,10 @@ from .camera import Cam
 from .sgbm import MODE_HH, MODE_HH4, MODE_SGBM, MODE_SGBM_3WAY, StereoSGBM, StereoSGBM_create
 from .stereo_matching import FeatureMatchingAsStereoMatching, MetaStereoMatching, SemiGlobalBlockMatching
 from .stereo_camera import Stereo
+from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, filter_overlap_uvs, flow_abs_to_normal,
+                                flow_normal_to_abs, flow_to_matched_uvs, matching_uvs_in_one_img)
 
 __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "StereoSGBM",
            "StereoSGBM_create", "MODE_SGBM", "MODE_HH", "MODE_SGBM_3WAY", "MODE_HH4", "__version__",
-           "FeatureMatchingAsStereoMatching"]
+           "FeatureMatchingAsStereoMatching", "EssentialMatrixStereo", "filter_overlap_uvs", "matching_uvs_in_one_img",
+           "flow_abs_to_normal", "flow_normal_to_abs", "flow_to_matched_uvs", "build_set2ds_by_flowds"]

@@ -104,6 +104,25 @@ SIGNATURES = {
     "camd_plane_eval": (c_int, [c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p]),
     "camd_matched_uvs_to_zs": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "camd_cell_first_index": (c_int, [c_void_p, c_int, c_size_t, c_int, c_double, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p]),
+    "camd_cell_population": (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_cell_intersect_count": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "camd_cell_intersect_emit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                         c_void_p]),
+    "camd_overlap_blocks": (c_int, [c_size_t]),
+    "camd_overlap_keep": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "camd_overlap_emit": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p, c_void_p]),
+    "camd_epipolar_sums_blocks": (c_int, [c_size_t]),
+    "camd_epipolar_sums": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_vector_sum_blocks": (c_int, [c_size_t]),
+    "camd_vector_sum": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "camd_flow_to_matched_uvs": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p,
+                                         c_void_p, c_void_p]),
+    "camd_flow_abs_to_normal": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_flow_normal_to_abs": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     "camd_set_global_option": (c_int, [c_int, c_int]),
     "camd_lanczos4_table_host": (c_int, [c_void_p]),
     "camd_bilinear_table_host": (c_int, [c_void_p]),

@@ -1,0 +1,587 @@
+// epipolar.hip -- the device side of calibrating_amd/epipolar_geometry.py: what the reference's epipolar_geometry.py,
+// flow_utils.py and ReconstructionExtrinsics.build_set2ds_by_flowds do per point or per pixel in NumPy
+//   matching_uvs_in_one_img   np.unique(cells, axis=0, return_index=True) x2 + np.intersect1d -> first-index grids + intersection
+//   filter_overlap_uvs        np.unique(..., return_counts, return_inverse) x2 + uvs[mask]    -> population grids + compaction
+//   EssentialMatrixStereo     the mean depth of every match under each of the four candidate poses -> one fused pass
+//   align_scale_with          zs[idx].mean()                                                  -> gathered fixed-order sum
+//   build_set2ds_by_flowds    xys_abs[mask], (flow_abs + xys_abs)[mask]                       -> masked compaction
+//   flow_abs_to_normal / flow_normal_to_abs
+// Integer atomics only (min / add commute, so the grids do not depend on the order they are served in); every float sum
+// is reduced in a fixed order.  Compactions are count -> exclusive scan -> emit; where the header says so the scan is the
+// caller's.  Products and sums are individually rounded (-ffp-contract=off).
+#include "common.hpp"
+#include "triangulate.hpp"
+
+#include <cmath>
+
+namespace camd {
+
+constexpr int EP_MAX_BLOCKS = 1024;            // partials of a fixed-order sum; the final block adds four per thread
+constexpr uint32_t EP_EMPTY = 0xffffffffu;
+constexpr unsigned long long EP_MAX_CELLS = 1ull << 28;
+
+struct EpWin {
+    int cu0, cv0, cw, ch;  // cells cu0 .. cu0 + cw - 1, cv0 .. cv0 + ch - 1; stored u-major: [(cu - cu0) * ch + (cv - cv0)]
+};
+
+__device__ __forceinline__ double ep_div(double a, double b) { return __ddiv_rn(a, b); }
+__device__ __forceinline__ float ep_div(float a, float b) { return __fdiv_rn(a, b); }
+
+// np.int32((uv / d).round()): the division in the rows' own type, round half to even.  rintf(x) == rint((double)x).
+template <typename T>
+__device__ __forceinline__ bool ep_cell(const T* __restrict__ uv, size_t i, int stride, T d, const EpWin& w, size_t* cell)
+{
+    const double ru = rint((double)ep_div(uv[i * stride], d)), rv = rint((double)ep_div(uv[i * stride + 1], d));
+    if (!(ru >= (double)w.cu0 && ru < (double)w.cu0 + (double)w.cw && rv >= (double)w.cv0 && rv < (double)w.cv0 + (double)w.ch))
+        return false;  // (also NaN / inf)
+    *cell = (size_t)((long long)ru - w.cu0) * (size_t)w.ch + (size_t)((long long)rv - w.cv0);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_ep_fill_u32(uint32_t* __restrict__ p, size_t n, uint32_t v, unsigned long long* zero)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+    if (i == 0 && zero) *zero = 0ull;
+}
+
+// FIRST: grid[cell] = min(row index) -- np.unique(return_index=True) reports the first occurrence, the smallest index.
+// !FIRST: grid[cell] += 1 -- np.unique(return_counts=True)[inverse].
+template <typename T, bool FIRST>
+__global__ __launch_bounds__(256) void k_ep_cells(const T* __restrict__ uv, size_t n, int stride, T d, EpWin w,
+                                                  uint32_t* __restrict__ grid, unsigned long long* __restrict__ outside)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    size_t cell;
+    if (!ep_cell(uv, i, stride, d, w, &cell)) { atomicAdd(outside, 1ull); return; }
+    if (FIRST) atomicMin(grid + cell, (uint32_t)i);
+    else atomicAdd(grid + cell, 1u);
+}
+
+// ---- the intersection --------------------------------------------------------------------------------------------------
+// np.unique(axis=0) sorts the (u, v) cell rows lexicographically as signed integers and np.intersect1d keeps that order:
+// ascending u cell, then v cell -- the linear order of the u-major grid.  One workgroup per u column.
+__global__ __launch_bounds__(256) void k_ep_isect_count(const uint32_t* __restrict__ f1, const uint32_t* __restrict__ f2, int ch,
+                                                        uint32_t* __restrict__ colcount)
+{
+    __shared__ uint32_t part[4];
+    const size_t base = (size_t)blockIdx.x * ch;
+    uint32_t c = 0;
+    for (int v = threadIdx.x; v < ch; v += 256) c += (f1[base + v] != EP_EMPTY && f2[base + v] != EP_EMPTY) ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) colcount[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// position of this thread's element among the `on` elements of the block's current 256, after `run`
+__device__ __forceinline__ unsigned long long ep_slot(bool on, unsigned long long run, uint32_t* wcnt)
+{
+    const unsigned long long bal = __ballot(on);
+    const uint32_t below = __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
+    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    unsigned long long pos = run + below;
+    for (int k = 0; k < (int)(threadIdx.x >> 6); k++) pos += wcnt[k];
+    return pos;
+}
+
+__global__ __launch_bounds__(256) void k_ep_isect_emit(const uint32_t* __restrict__ f1, const uint32_t* __restrict__ f2, int ch,
+                                                       const long long* __restrict__ start, long long* __restrict__ idx1,
+                                                       long long* __restrict__ idx2, size_t capacity,
+                                                       unsigned long long* __restrict__ count)
+{
+    __shared__ uint32_t wcnt[4];
+    __shared__ unsigned long long run;
+    const size_t base = (size_t)blockIdx.x * ch;
+    if (threadIdx.x == 0) {
+        run = (unsigned long long)start[blockIdx.x];
+        if (blockIdx.x == 0) *count = (unsigned long long)start[gridDim.x];
+    }
+    __syncthreads();
+    for (int v0 = 0; v0 < ch; v0 += 256) {
+        const int v = v0 + threadIdx.x;
+        uint32_t a = EP_EMPTY, b = EP_EMPTY;
+        if (v < ch) { a = f1[base + v]; b = f2[base + v]; }
+        const bool on = a != EP_EMPTY && b != EP_EMPTY;
+        const unsigned long long pos = ep_slot(on, run, wcnt);
+        if (on && pos < capacity) { idx1[pos] = (long long)a; idx2[pos] = (long long)b; }
+        __syncthreads();
+        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+// ---- the overlap filter ------------------------------------------------------------------------------------------------
+// keep[i] = both pixels of match i are hit once; blockcount[b] = how many of rows 256 b .. 256 b + 255 are kept
+template <typename T>
+__global__ __launch_bounds__(256) void k_ep_overlap_keep(const T* __restrict__ uv1, const T* __restrict__ uv2, size_t n, int stride,
+                                                         EpWin w, const uint32_t* __restrict__ cnt1,
+                                                         const uint32_t* __restrict__ cnt2, uint8_t* __restrict__ keep,
+                                                         uint32_t* __restrict__ blockcount)
+{
+    __shared__ uint32_t part[4];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    bool on = false;
+    if (i < n) {
+        size_t c1, c2;
+        on = ep_cell(uv1, i, stride, (T)1, w, &c1) && ep_cell(uv2, i, stride, (T)1, w, &c2) && cnt1[c1] <= 1u && cnt2[c2] <= 1u;
+        keep[i] = on ? 1 : 0;
+    }
+    const unsigned long long bal = __ballot(on);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) blockcount[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// uvs[mask]: the kept rows in their own order
+template <typename T>
+__global__ __launch_bounds__(256) void k_ep_overlap_emit(const T* __restrict__ uv1, const T* __restrict__ uv2, size_t n, int stride,
+                                                         const uint8_t* __restrict__ keep, const long long* __restrict__ start,
+                                                         T* __restrict__ out1, T* __restrict__ out2, size_t capacity,
+                                                         unsigned long long* __restrict__ count)
+{
+    __shared__ uint32_t wcnt[4];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *count = (unsigned long long)start[gridDim.x];
+    const bool on = i < n && keep[i] != 0;
+    const unsigned long long pos = ep_slot(on, (unsigned long long)start[blockIdx.x], wcnt);
+    if (on && pos < capacity) {
+        out1[pos * 2] = uv1[i * stride]; out1[pos * 2 + 1] = uv1[i * stride + 1];
+        out2[pos * 2] = uv2[i * stride]; out2[pos * 2 + 1] = uv2[i * stride + 1];
+    }
+}
+
+// ---- fixed-order sums --------------------------------------------------------------------------------------------------
+// Q running sums per thread; thread t of block g adds rows g*256+t, +G*256, ... in that order (at most
+// m = ceil(n / (256 G)) terms); the block adds its 256 threads by a binary tree (8 levels) and stores Q partials;
+// k_ep_final: thread t adds partials t, t+256, t+512, t+768 as (p0 + p1) + (p2 + p3) (2 levels; absent ones are 0), then
+// the same 8-level tree: d = 18 levels above the serial part, whatever n is.
+template <int Q>
+__device__ __forceinline__ void ep_block_tree(const double* s, double* sh, double* __restrict__ dst)
+{
+    for (int q = 0; q < Q; q++) {
+        sh[threadIdx.x] = s[q];
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) dst[q] = sh[0];
+        __syncthreads();
+    }
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
+{
+    __shared__ double sh[256];
+    double s[Q];
+    for (int q = 0; q < Q; q++) {
+        double p[4];
+        for (int k = 0; k < 4; k++) {
+            const int g = (int)threadIdx.x + 256 * k;
+            p[k] = g < nblocks ? partials[(size_t)g * Q + q] : 0.0;
+        }
+        s[q] = (p[0] + p[1]) + (p[2] + p[3]);
+    }
+    ep_block_tree<Q>(s, sh, sums);
+}
+
+struct EpPoses {
+    double k1[9], k2[9], R[4][9], t[4][3];
+};
+
+// sums[c * 2 + 0 / 1] = sum of zs1 / zs2 over all matches under candidate c: each match is read once
+__global__ __launch_bounds__(256) void k_ep_pose_partials(const double* __restrict__ uv1, const double* __restrict__ uv2, size_t n,
+                                                          EpPoses m, double* __restrict__ partials)
+{
+    __shared__ double sh[256];
+    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        double x1[3], b[3];
+        tri_rays(m.k1, m.k2, uv1[i * 2], uv1[i * 2 + 1], uv2[i * 2], uv2[i * 2 + 1], x1, b);
+        for (int c = 0; c < 4; c++) {
+            double z1, z2;
+            tri_solve(x1, b, m.R[c], m.t[c], &z1, &z2);
+            s[c * 2] += z1;
+            s[c * 2 + 1] += z2;
+        }
+    }
+    ep_block_tree<8>(s, sh, partials + (size_t)blockIdx.x * 8);
+}
+
+// s[0] = sum of z[i] (idx == NULL) or of z[idx[i]]; s[1] = how many idx[i] lie outside [0, z_len) (they add nothing)
+__global__ __launch_bounds__(256) void k_ep_vector_partials(const double* __restrict__ z, const long long* __restrict__ idx, size_t n,
+                                                            size_t z_len, double* __restrict__ partials)
+{
+    __shared__ double sh[256];
+    double s[2] = {0, 0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        if (!idx) { s[0] += z[i]; continue; }
+        const long long j = idx[i];
+        if (j >= 0 && (unsigned long long)j < z_len) s[0] += z[j];
+        else s[1] += 1.0;
+    }
+    ep_block_tree<2>(s, sh, partials + (size_t)blockIdx.x * 2);
+}
+
+// ---- flow ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ep_mask_count(const uint8_t* __restrict__ mask, int w, uint32_t* __restrict__ rowcount)
+{
+    __shared__ uint32_t part[4];
+    const int y = blockIdx.x;
+    uint32_t c = 0;
+    for (int x = threadIdx.x; x < w; x += 256) c += mask[(size_t)y * w + x] ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) rowcount[y] = part[0] + part[1] + part[2] + part[3];
+}
+
+// exclusive scan of the row counts (one workgroup; rows <= a few thousand)
+__global__ __launch_bounds__(256) void k_ep_mask_scan(const uint32_t* __restrict__ rowcount, int n,
+                                                      unsigned long long* __restrict__ rowoff,
+                                                      unsigned long long* __restrict__ total)
+{
+    __shared__ unsigned long long carry;
+    __shared__ unsigned long long wsum[4];
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + threadIdx.x;
+        unsigned long long v = i < n ? rowcount[i] : 0ull, incl = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            unsigned long long t = __shfl_up(incl, o);
+            if ((threadIdx.x & 63) >= o) incl += t;
+        }
+        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) before += wsum[k];
+        if (i < n) rowoff[i] = before + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 255) carry = before + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// xys_abs = (np.mgrid[:h, :w] + 0.5 - 1e-8)[::-1]: the float64 sum (x + 0.5) - 1e-8; uvs_to = float64(flow) + xys_abs
+template <typename F>
+__global__ __launch_bounds__(256) void k_ep_flow_emit(const F* __restrict__ flow, const uint8_t* __restrict__ mask, int w,
+                                                      const unsigned long long* __restrict__ rowoff, double* __restrict__ from,
+                                                      double* __restrict__ to, size_t capacity)
+{
+    __shared__ uint32_t wcnt[4];
+    __shared__ unsigned long long run;
+    const int y = blockIdx.x;
+    if (threadIdx.x == 0) run = rowoff[y];
+    __syncthreads();
+    const double fy = ((double)y + 0.5) - 1e-8;
+    for (int base = 0; base < w; base += 256) {
+        const int x = base + threadIdx.x;
+        const bool on = x < w && mask[(size_t)y * w + x] != 0;
+        const unsigned long long pos = ep_slot(on, run, wcnt);
+        if (on && pos < capacity) {
+            const double fx = ((double)x + 0.5) - 1e-8;
+            const size_t p = ((size_t)y * w + x) * 2;
+            from[pos * 2] = fx;
+            from[pos * 2 + 1] = fy;
+            to[pos * 2] = (double)flow[p] + fx;
+            to[pos * 2 + 1] = (double)flow[p + 1] + fy;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+// np.float32(flow_abs.transpose(2, 0, 1) / [[[w]], [[h]]]): the quotient in float64, then the cast
+template <typename F>
+__global__ __launch_bounds__(256) void k_ep_flow_abs_to_normal(const F* __restrict__ flow, int w, int h, float* __restrict__ out)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x, npix = (size_t)w * h;
+    if (p >= npix) return;
+    out[p] = (float)__ddiv_rn((double)flow[p * 2], (double)w);
+    out[npix + p] = (float)__ddiv_rn((double)flow[p * 2 + 1], (double)h);
+}
+
+// (flow * [[[tw]], [[th]]]).transpose(1, 2, 0): float64 products
+template <typename F>
+__global__ __launch_bounds__(256) void k_ep_flow_normal_to_abs(const F* __restrict__ flow, int w, int h, double tw, double th,
+                                                               double* __restrict__ out)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x, npix = (size_t)w * h;
+    if (p >= npix) return;
+    out[p * 2] = (double)flow[p] * tw;
+    out[p * 2 + 1] = (double)flow[npix + p] * th;
+}
+
+static int make_window(EpWin* w, int cu0, int cv0, int cells_w, int cells_h, const char* who)
+{
+    if (cells_w <= 0 || cells_h <= 0 || (unsigned long long)cells_w * (unsigned long long)cells_h > EP_MAX_CELLS) {
+        set_error("%s: a window of %d x %d cells is empty or beyond 2^28 cells", who, cells_w, cells_h);
+        return CAMD_ERR_BAD_ARG;
+    }
+    if ((long long)cu0 + cells_w > 0x7fffffffll || (long long)cv0 + cells_h > 0x7fffffffll) {
+        set_error("%s: the window leaves the int32 cell range", who);
+        return CAMD_ERR_BAD_ARG;
+    }
+    w->cu0 = cu0; w->cv0 = cv0; w->cw = cells_w; w->ch = cells_h;
+    return CAMD_OK;
+}
+
+static bool uv_type_ok(int t) { return t == CAMD_VALUE_F64 || t == CAMD_VALUE_F32; }
+
+template <bool FIRST>
+static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, int uv_stride, double d, int cu0, int cv0,
+                       int cells_w, int cells_h, uint32_t* grid, unsigned long long* outside, void* stream)
+{
+    EpWin w;
+    int rc = make_window(&w, cu0, cv0, cells_w, cells_h, who);
+    if (rc != CAMD_OK) return rc;
+    if (!grid || !outside || uv_stride < 2 || (n && !uv) || !uv_type_ok(uv_type) || !(d > 0.0) || (unsigned long long)n >= 0xffffffffull) {
+        set_error("%s: bad arguments", who);
+        return CAMD_ERR_BAD_ARG;
+    }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ncell = (size_t)cells_w * cells_h;
+    hipLaunchKernelGGL(k_ep_fill_u32, dim3(div_up((long long)ncell, 256)), dim3(256), 0, st, grid, ncell, FIRST ? EP_EMPTY : 0u,
+                       outside);
+    if (n) {
+        const dim3 g(div_up((long long)n, 256));
+        if (uv_type == CAMD_VALUE_F64)
+            hipLaunchKernelGGL((k_ep_cells<double, FIRST>), g, dim3(256), 0, st, (const double*)uv, n, uv_stride, d, w, grid, outside);
+        else
+            hipLaunchKernelGGL((k_ep_cells<float, FIRST>), g, dim3(256), 0, st, (const float*)uv, n, uv_stride, (float)d, w, grid,
+                               outside);
+    }
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+static int sum_blocks(size_t n)
+{
+    const long long g = (long long)((n + 255) / 256);
+    return (int)(g < 1 ? 1 : g > EP_MAX_BLOCKS ? EP_MAX_BLOCKS : g);
+}
+
+}  // namespace camd
+
+using namespace camd;
+
+extern "C" {
+
+int camd_cell_first_index(const void* uv, int uv_type, size_t n, int uv_stride, double max_distance, int cu0, int cv0,
+                          int cells_w, int cells_h, uint32_t* first, unsigned long long* outside, void* stream)
+{
+    return cells_entry<true>("camd_cell_first_index", uv, uv_type, n, uv_stride, max_distance, cu0, cv0, cells_w, cells_h, first,
+                             outside, stream);
+}
+
+int camd_cell_population(const void* uv, int uv_type, size_t n, int uv_stride, int cu0, int cv0, int cells_w, int cells_h,
+                         uint32_t* population, unsigned long long* outside, void* stream)
+{
+    return cells_entry<false>("camd_cell_population", uv, uv_type, n, uv_stride, 1.0, cu0, cv0, cells_w, cells_h, population,
+                              outside, stream);
+}
+
+int camd_cell_intersect_count(const uint32_t* first1, const uint32_t* first2, int cells_w, int cells_h, uint32_t* colcount,
+                              void* stream)
+{
+    EpWin w;
+    int rc = make_window(&w, 0, 0, cells_w, cells_h, "camd_cell_intersect_count");
+    if (rc != CAMD_OK) return rc;
+    if (!first1 || !first2 || !colcount) { set_error("camd_cell_intersect_count: NULL argument"); return CAMD_ERR_BAD_ARG; }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_ep_isect_count, dim3(cells_w), dim3(256), 0, (hipStream_t)stream, first1, first2, cells_h, colcount);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_cell_intersect_emit(const uint32_t* first1, const uint32_t* first2, int cells_w, int cells_h, const long long* start,
+                             long long* idx1, long long* idx2, size_t capacity, unsigned long long* count, void* stream)
+{
+    EpWin w;
+    int rc = make_window(&w, 0, 0, cells_w, cells_h, "camd_cell_intersect_emit");
+    if (rc != CAMD_OK) return rc;
+    if (!first1 || !first2 || !start || !count || (capacity && (!idx1 || !idx2))) {
+        set_error("camd_cell_intersect_emit: NULL argument");
+        return CAMD_ERR_BAD_ARG;
+    }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_ep_isect_emit, dim3(cells_w), dim3(256), 0, (hipStream_t)stream, first1, first2, cells_h, start, idx1, idx2,
+                       capacity, count);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_overlap_blocks(size_t n) { return div_up((long long)n, 256); }
+
+int camd_overlap_keep(const void* uv1, const void* uv2, int uv_type, size_t n, int uv_stride, int cu0, int cv0, int cells_w,
+                      int cells_h, const uint32_t* population1, const uint32_t* population2, uint8_t* keep,
+                      uint32_t* blockcount, void* stream)
+{
+    EpWin w;
+    int rc = make_window(&w, cu0, cv0, cells_w, cells_h, "camd_overlap_keep");
+    if (rc != CAMD_OK) return rc;
+    if (!population1 || !population2 || uv_stride < 2 || !uv_type_ok(uv_type) || (unsigned long long)n >= 0xffffffffull ||
+        (n && (!uv1 || !uv2 || !keep || !blockcount))) {
+        set_error("camd_overlap_keep: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (n == 0) return CAMD_OK;
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    const dim3 g(camd_overlap_blocks(n));
+    if (uv_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_ep_overlap_keep<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)uv1, (const double*)uv2,
+                           n, uv_stride, w, population1, population2, keep, blockcount);
+    else
+        hipLaunchKernelGGL((k_ep_overlap_keep<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)uv1, (const float*)uv2, n,
+                           uv_stride, w, population1, population2, keep, blockcount);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_overlap_emit(const void* uv1, const void* uv2, int uv_type, size_t n, int uv_stride, const uint8_t* keep,
+                      const long long* start, void* out1, void* out2, size_t capacity, unsigned long long* count, void* stream)
+{
+    if (!count || uv_stride < 2 || !uv_type_ok(uv_type) || (unsigned long long)n >= 0xffffffffull ||
+        (n && (!uv1 || !uv2 || !keep || !start)) || (capacity && (!out1 || !out2))) {
+        set_error("camd_overlap_emit: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        hipLaunchKernelGGL(k_ep_fill_u32, dim3(1), dim3(256), 0, st, (uint32_t*)nullptr, (size_t)0, 0u, count);
+    } else {
+        const dim3 g(camd_overlap_blocks(n));
+        if (uv_type == CAMD_VALUE_F64)
+            hipLaunchKernelGGL((k_ep_overlap_emit<double>), g, dim3(256), 0, st, (const double*)uv1, (const double*)uv2, n, uv_stride,
+                               keep, start, (double*)out1, (double*)out2, capacity, count);
+        else
+            hipLaunchKernelGGL((k_ep_overlap_emit<float>), g, dim3(256), 0, st, (const float*)uv1, (const float*)uv2, n, uv_stride,
+                               keep, start, (float*)out1, (float*)out2, capacity, count);
+    }
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_epipolar_sums_blocks(size_t n) { return sum_blocks(n); }
+
+int camd_epipolar_sums(const double* uv1, const double* uv2, size_t n, const double K1inv[9], const double K2inv[9],
+                       const double T_1to2[64], double* partials_ws, double* sums, void* stream)
+{
+    if (!uv1 || !uv2 || !K1inv || !K2inv || !T_1to2 || !partials_ws || !sums || n == 0) {
+        set_error("camd_epipolar_sums: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    EpPoses m;
+    for (int i = 0; i < 9; i++) { m.k1[i] = K1inv[i]; m.k2[i] = K2inv[i]; }
+    for (int c = 0; c < 4; c++) {
+        for (int i = 0; i < 9; i++) m.R[c][i] = T_1to2[c * 16 + (i / 3) * 4 + i % 3];
+        for (int i = 0; i < 3; i++) m.t[c][i] = T_1to2[c * 16 + i * 4 + 3];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int g = sum_blocks(n);
+    hipLaunchKernelGGL(k_ep_pose_partials, dim3(g), dim3(256), 0, st, uv1, uv2, n, m, partials_ws);
+    hipLaunchKernelGGL((k_ep_final<8>), dim3(1), dim3(256), 0, st, partials_ws, g, sums);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_vector_sum_blocks(size_t n) { return sum_blocks(n); }
+
+int camd_vector_sum(const double* z, size_t z_len, const long long* idx, size_t n, double* partials_ws, double* sums,
+                    void* stream)
+{
+    if (!z || !partials_ws || !sums || n == 0 || (!idx && n > z_len)) {
+        set_error("camd_vector_sum: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int g = sum_blocks(n);
+    hipLaunchKernelGGL(k_ep_vector_partials, dim3(g), dim3(256), 0, st, z, idx, n, z_len, partials_ws);
+    hipLaunchKernelGGL((k_ep_final<2>), dim3(1), dim3(256), 0, st, partials_ws, g, sums);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_flow_to_matched_uvs(const void* flow_abs, int flow_type, const uint8_t* mask, int w, int h, double* uvs_from,
+                             double* uvs_to, size_t capacity, unsigned long long* count, void* workspace, void* stream)
+{
+    if (!flow_abs || !mask || !count || !workspace || w <= 0 || h <= 0 || !uv_type_ok(flow_type) ||
+        (capacity && (!uvs_from || !uvs_to))) {
+        set_error("camd_flow_to_matched_uvs: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* rowoff = reinterpret_cast<unsigned long long*>(workspace);
+    uint32_t* rowcount = reinterpret_cast<uint32_t*>(rowoff + h);
+    hipLaunchKernelGGL(k_ep_mask_count, dim3(h), dim3(256), 0, st, mask, w, rowcount);
+    hipLaunchKernelGGL(k_ep_mask_scan, dim3(1), dim3(256), 0, st, rowcount, h, rowoff, count);
+    if (flow_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_ep_flow_emit<double>), dim3(h), dim3(256), 0, st, (const double*)flow_abs, mask, w, rowoff, uvs_from,
+                           uvs_to, capacity);
+    else
+        hipLaunchKernelGGL((k_ep_flow_emit<float>), dim3(h), dim3(256), 0, st, (const float*)flow_abs, mask, w, rowoff, uvs_from,
+                           uvs_to, capacity);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, float* flow_normal, void* stream)
+{
+    if (!flow_abs || !flow_normal || w <= 0 || h <= 0 || !uv_type_ok(flow_type)) {
+        set_error("camd_flow_abs_to_normal: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    const dim3 g(div_up((long long)w * h, 256));
+    if (flow_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_ep_flow_abs_to_normal<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)flow_abs, w, h,
+                           flow_normal);
+    else
+        hipLaunchKernelGGL((k_ep_flow_abs_to_normal<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)flow_abs, w, h,
+                           flow_normal);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h, double target_w, double target_h,
+                            double* flow_abs, void* stream)
+{
+    if (!flow_normal || !flow_abs || w <= 0 || h <= 0 || !uv_type_ok(flow_type)) {
+        set_error("camd_flow_normal_to_abs: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    const dim3 g(div_up((long long)w * h, 256));
+    if (flow_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_ep_flow_normal_to_abs<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)flow_normal, w, h,
+                           target_w, target_h, flow_abs);
+    else
+        hipLaunchKernelGGL((k_ep_flow_normal_to_abs<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)flow_normal, w, h,
+                           target_w, target_h, flow_abs);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+}  // extern "C"

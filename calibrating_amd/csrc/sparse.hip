@@ -10,6 +10,7 @@
 // an integer maximum, the bins are filled in any order and searched by the key (distance, index), the plane sums are
 // reduced in a fixed order without float atomics.
 #include "common.hpp"
+#include "triangulate.hpp"
 
 #include <cmath>
 
@@ -278,45 +279,16 @@ struct SpTri {
     double k1[9], k2[9], R[9], t[3];
 };
 
-// a * b - c * d with the rounding error of c * d carried along (Kahan): exact to ~1.5 ulp without cancellation loss
-__device__ __forceinline__ double diff_of_products(double a, double b, double c, double d)
-{
-    const double w = c * d;
-    const double e = __fma_rn(-c, d, w);
-    const double f = __fma_rn(a, b, -w);
-    return f + e;
-}
-__device__ __forceinline__ void cross3(const double* p, const double* q, double* r)
-{
-    r[0] = diff_of_products(p[1], q[2], p[2], q[1]);
-    r[1] = diff_of_products(p[2], q[0], p[0], q[2]);
-    r[2] = diff_of_products(p[0], q[1], p[1], q[0]);
-}
-
-// X2 z2 = R X1 z1 + t  ->  [a, b] (z1, z2)^T = t with a = -R X1, b = X2.  The 2x2 normal equations
-//   (a.a) z1 + (a.b) z2 = a.t,  (a.b) z1 + (b.b) z2 = b.t
-// have, by Lagrange's identity, the closed form z1 = (a x b).(t x b) / |a x b|^2, z2 = (a x b).(a x t) / |a x b|^2.
-// That form is evaluated: for the near-parallel rays of a stereo rig the determinant (a.a)(b.b) - (a.b)^2 loses
-// sin^-2 of the angle between the rays in digits, the cross product only sin^-1.
+// the per-match solve lives in triangulate.hpp: camd_epipolar_sums (epipolar.hip) evaluates the same function
 __global__ __launch_bounds__(256) void k_sp_triangulate(const double* __restrict__ uv1, const double* __restrict__ uv2,
                                                         size_t n, SpTri m, double* __restrict__ zs1, double* __restrict__ zs2)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double u1 = uv1[i * 2], v1 = uv1[i * 2 + 1], u2 = uv2[i * 2], v2 = uv2[i * 2 + 1];
-    double x1[3], a[3], b[3], axb[3], txb[3], axt[3];
-    for (int r = 0; r < 3; r++) {
-        x1[r] = __fma_rn(m.k1[r * 3 + 2], 1.0, __fma_rn(m.k1[r * 3 + 1], v1, m.k1[r * 3] * u1));
-        b[r] = __fma_rn(m.k2[r * 3 + 2], 1.0, __fma_rn(m.k2[r * 3 + 1], v2, m.k2[r * 3] * u2));
-    }
-    for (int r = 0; r < 3; r++)
-        a[r] = -__fma_rn(m.R[r * 3 + 2], x1[2], __fma_rn(m.R[r * 3 + 1], x1[1], m.R[r * 3] * x1[0]));
-    cross3(a, b, axb);
-    cross3(m.t, b, txb);
-    cross3(a, m.t, axt);
-    const double den = __fma_rn(axb[2], axb[2], __fma_rn(axb[1], axb[1], axb[0] * axb[0]));
-    zs1[i] = __fma_rn(axb[2], txb[2], __fma_rn(axb[1], txb[1], axb[0] * txb[0])) / den;
-    zs2[i] = __fma_rn(axb[2], axt[2], __fma_rn(axb[1], axt[1], axb[0] * axt[0])) / den;
+    double x1[3], b[3];
+    tri_rays(m.k1, m.k2, u1, v1, u2, v2, x1, b);
+    tri_solve(x1, b, m.R, m.t, zs1 + i, zs2 + i);
 }
 
 static int make_bins(SpBins* b, int w, int h, double distance, const char* who)

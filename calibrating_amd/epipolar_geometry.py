@@ -1,0 +1,446 @@
+"""A rig's pose from matched points on the GPU -- same names and argument meanings as the reference's
+``epipolar_geometry.py`` (``EssentialMatrixStereo``, ``filter_overlap_uvs``, ``matching_uvs_in_one_img``), ``flow_utils``
+(``flow_abs_to_normal`` / ``flow_normal_to_abs``) and the flow-to-matches step of
+``ReconstructionExtrinsics.build_set2ds_by_flowds`` (reconstruction_epipolar_geometry.py:256-295).  NumPy in -> NumPy out,
+torch CUDA tensors in -> tensors out on the same device (csrc/epipolar.hip; DESIGN.md "Epipolar path").
+
+Where the work runs.  Everything that touches every match or every pixel is a kernel: the cell grids and their
+intersection, the overlap filter, the depth of every match under all four candidate poses, the gathered means, the flow
+compaction and conversions.  The essential matrix itself is an SVD of at most 199 x 9 numbers (the reference subsamples
+``[:: n // 100]``) followed by 3 x 3 algebra: init-time work on the host in NumPy float64, fed with the strided subsample
+only.
+
+Arguments are checked before the device is touched.  Deviations from the reference:
+``precise=True`` is refused, ``xy1`` / ``xy2`` are required, non-finite coordinates and cell windows beyond 2^28 cells
+raise ``ValueError``.
+"""
+import numpy as np
+
+from . import _native, geometry, hostio, sparse
+from .sparse import _check_array, _dev, _dtype_name, _is_np, matched_uvs_to_zs  # noqa: F401  (matched_uvs_to_zs: re-export)
+from .stereo_camera import Stereo
+
+MAX_CELLS = 1 << 28  # the most one cell window may hold: two uint32 grids of it are 2 GiB
+_UV_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32}
+
+
+def _float_rows(a, what, other=None):
+    """(n, 2) rows as they take part in NumPy's arithmetic: float32 stays, everything else becomes float64."""
+    _check_array(a, what)
+    if len(a.shape) != 2 or a.shape[1] != 2:
+        raise ValueError("%s must be (n, 2), got %s" % (what, tuple(a.shape)))
+    if int(a.shape[0]) >= 2 ** 32 - 1:
+        raise ValueError("%s: %d rows do not fit the 32-bit row index" % (what, a.shape[0]))
+    if other is not None and _is_np(a) != _is_np(other):
+        raise TypeError("%s: pass both point sets as ndarrays or both as CUDA tensors" % what)
+    return "float32" if _dtype_name(a) == "float32" else "float64"
+
+
+def _min_max(a):
+    """[min u, min v, max u, max v] as float64 on the host.  Tensors are reduced on the device and four numbers read back.
+    ndarrays are reduced on the host BEFORE they are uploaded: non-finite input and an oversized window are then refused
+    without touching the device (one pass over host memory that a device-resident caller does not pay)."""
+    if _is_np(a):
+        return np.concatenate([a.min(0), a.max(0)]).astype(np.float64)
+    import torch
+    return torch.cat([a.amin(0), a.amax(0)]).to(torch.float64).cpu().numpy()
+
+
+def _window(bounds, what, hint):
+    """(cu0, cv0, cells_w, cells_h) holding the rounded ``bounds`` = rows of [min u, min v, max u, max v] cells."""
+    b = np.asarray(bounds, np.float64)
+    if not np.isfinite(b).all():
+        raise ValueError("%s: u, v must be finite" % what)
+    lo, hi = np.rint(b[:, :2]).min(0), np.rint(b[:, 2:]).max(0)
+    if lo.min() < -2 ** 31 or hi.max() >= 2 ** 31 - 1:
+        raise ValueError("%s: cells leave the int32 range%s" % (what, hint))
+    cw, ch = (int(v) for v in hi - lo + 1)
+    if cw * ch > MAX_CELLS:
+        raise ValueError("%s: the points span %d x %d cells, more than 2^28%s" % (what, cw, ch, hint))
+    return int(lo[0]), int(lo[1]), cw, ch
+
+
+# ---- small helpers -----------------------------------------------------------------------------------------------------
+def uvs_to_xyz_noramls(uvs, K):
+    """Rays (x, y, 1) of pixels: ``(u, v, 1) @ inv(K).T`` (epipolar_geometry.py:84-85; the spelling is the reference's)."""
+    Kinv_T = np.linalg.inv(np.asarray(K)).T
+    if _is_np(uvs):
+        return np.pad(uvs, ((0, 0), (0, 1)), constant_values=1) @ Kinv_T
+    import torch
+    _check_array(uvs, "uvs")
+    ones = torch.ones((uvs.shape[0], 1), dtype=uvs.dtype, device=uvs.device)
+    return torch.cat([uvs, ones], 1).to(torch.float64) @ torch.from_numpy(np.ascontiguousarray(Kinv_T, np.float64)).to(uvs.device)
+
+
+uvs_to_xyz_normals = uvs_to_xyz_noramls
+
+
+def compute_essential_matrix(xyzs1, xyzs2):
+    """Eight-point essential matrix of matched rays (:12-43), host NumPy float64: every ``n // 100``-th pair when there
+    are more than 100, the null vector of the n x 9 system by SVD, then the smallest singular value forced to 0."""
+    xyzs1, xyzs2 = np.asarray(xyzs1), np.asarray(xyzs2)
+    if xyzs1.shape != xyzs2.shape:
+        raise ValueError("the two point sets must have the same shape, got %s and %s" % (xyzs1.shape, xyzs2.shape))
+    n = xyzs1.shape[0]
+    if n < 8:
+        raise ValueError("at least 8 point pairs are required, got %d" % n)
+    if n > 100:
+        xyzs1, xyzs2 = xyzs1[:: n // 100], xyzs2[:: n // 100]
+    (x1, y1, z1), (x2, y2, z2) = xyzs1.T[:3], xyzs2.T[:3]
+    A = np.stack([x1 * x2, x2 * y1, z1 * x2, x1 * y2, y1 * y2, z1 * y2, x1 * z2, y1 * z2, z1 * z2], 1).astype(np.float64)
+    E = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    U, S, Vt = np.linalg.svd(E)
+    S[2] = 0
+    return np.dot(U, np.dot(np.diag(S), Vt))
+
+
+def decompose_essential_matrix(E):
+    """The four candidate poses of an essential matrix as 4x4 ``T_1to2`` (:46-62), in the reference's order: (Ra, +u),
+    (Rb, -u), (Ra, -u), (Rb, +u) with u the last left singular vector and Ra / Rb = U W Vt / U W^T Vt, each made a proper
+    rotation.  Like the reference's ``R_t_to_T`` the rotations are rounded through float32.  (The products keep the
+    reference's association, U (W Vt): the candidates are compared with its numbers.)"""
+    U, _, Vt = np.linalg.svd(E)
+    quarter_turn = np.array([[0, -1, 0], [1, 0, 0], [0, 0, 1]])
+    rotations = []
+    for W in (quarter_turn, quarter_turn.T):
+        R = np.dot(U, np.dot(W, Vt))
+        rotations.append(-R if np.linalg.det(R) < 0 else R)
+    u = U[:, 2]
+    order = ((0, u), (1, -u), (0, -u), (1, u))
+    return tuple(geometry.R_t_to_T(rotations[k], t) for k, t in order)
+
+
+def _host_subsample(uvs, n):
+    """Every ``n // 100``-th row (all of them up to 100) on the host: the only rows the essential matrix reads."""
+    rows = uvs[:: n // 100] if n > 100 else uvs
+    return rows if _is_np(rows) else rows.cpu().numpy()
+
+
+def _pose_candidates(uvs1, uvs2, K1, K2, baseline):
+    """(E, four T_1to2 with |t| = baseline) from the host subsample of the matches."""
+    n = int(uvs1.shape[0])
+    E = compute_essential_matrix(uvs_to_xyz_noramls(_host_subsample(uvs1, n), K1),
+                                 uvs_to_xyz_noramls(_host_subsample(uvs2, n), K2))
+    Ts = decompose_essential_matrix(E)
+    for T in Ts:
+        T[:3, 3] *= baseline / np.linalg.norm(T[:3, 3])
+    return E, Ts
+
+
+def _candidate_means(a, b, K1, K2, Ts):
+    """(4, 2) mean zs1 / zs2 of the matches under each candidate: one pass over device-resident (n, 2) float64 rows."""
+    import torch
+    lib, n = _native.lib(), int(a.shape[0])
+    Kinv = [np.ascontiguousarray(np.linalg.inv(K)).reshape(9) for K in (K1, K2)]
+    T4 = np.ascontiguousarray(np.stack(Ts), np.float64).reshape(64)
+    with torch.cuda.device(a.device):
+        partials = torch.empty(lib.camd_epipolar_sums_blocks(n) * 8, dtype=torch.float64, device=a.device)
+        sums = torch.empty(8, dtype=torch.float64, device=a.device)
+        rc = lib.camd_epipolar_sums(a.data_ptr(), b.data_ptr(), n, Kinv[0].ctypes.data, Kinv[1].ctypes.data, T4.ctypes.data,
+                                    partials.data_ptr(), sums.data_ptr(), _native.current_stream())
+    _native.check(rc, "EssentialMatrixStereo")
+    return sums.cpu().numpy().reshape(4, 2) / n
+
+
+def _mean(z, idx=None, what="mean"):
+    """``z.mean()`` / ``z[idx].mean()`` of a float64 vector through the fixed-order reduction (one number read back)."""
+    import torch
+    zd = _dev(z, dtype="float64")
+    lib = _native.lib()
+    n = int(zd.shape[0]) if idx is None else int(idx.shape[0])
+    if n == 0:
+        raise ValueError("%s of no elements" % what)
+    with torch.cuda.device(zd.device):
+        i = None if idx is None else _dev(idx, zd.device, dtype="int64")
+        partials = torch.empty(lib.camd_vector_sum_blocks(n) * 2, dtype=torch.float64, device=zd.device)
+        sums = torch.empty(2, dtype=torch.float64, device=zd.device)
+        rc = lib.camd_vector_sum(zd.data_ptr(), int(zd.shape[0]), None if i is None else i.data_ptr(), n, partials.data_ptr(),
+                                 sums.data_ptr(), _native.current_stream())
+    _native.check(rc, what)
+    total, bad = sums.cpu().numpy()
+    if bad:
+        raise IndexError("%s: %d indices lie outside the %d depths" % (what, int(bad), int(zd.shape[0])))
+    return float(total) / n
+
+
+# ---- filter_overlap_uvs ------------------------------------------------------------------------------------------------
+def filter_overlap_uvs(uvs1, uvs2):
+    """The matches whose pixel ``int32(round(u, v))`` is hit by no other match, in image 1 and in image 2 (:205-216):
+    ``(uvs1[mask], uvs2[mask])``, order and dtype kept."""
+    import torch
+    name = _float_rows(uvs1, "uvs1")
+    if _float_rows(uvs2, "uvs2", uvs1) != name or _dtype_name(uvs1) not in _UV_TYPES or _dtype_name(uvs2) != _dtype_name(uvs1):
+        raise ValueError("uvs1, uvs2 must both be float64 or both float32, got %s and %s" % (_dtype_name(uvs1), _dtype_name(uvs2)))
+    n = int(uvs1.shape[0])
+    if int(uvs2.shape[0]) != n:
+        raise ValueError("uvs1, uvs2 must have the same number of rows, got %d and %d" % (n, uvs2.shape[0]))
+    was_np = _is_np(uvs1)
+    if n == 0:
+        return (uvs1.copy(), uvs2.copy()) if was_np else (uvs1.clone(), uvs2.clone())
+    cu0, cv0, cw, ch = _window([_min_max(uvs1), _min_max(uvs2)], "filter_overlap_uvs", "")
+    a = _dev(uvs1)
+    b = _dev(uvs2, a.device)
+    lib, st, t = _native.lib(), _native.current_stream, _UV_TYPES[name]
+    with torch.cuda.device(a.device):
+        pop = torch.empty((2, cw * ch), dtype=torch.int32, device=a.device)
+        counters = torch.zeros(3, dtype=torch.int64, device=a.device)  # kept rows, rows outside the window of set 1 / 2
+        for k, uv in enumerate((a, b)):
+            _native.check(lib.camd_cell_population(uv.data_ptr(), t, n, 2, cu0, cv0, cw, ch, pop[k].data_ptr(),
+                                                   counters[1 + k:].data_ptr(), st()), "filter_overlap_uvs")
+        blocks = lib.camd_overlap_blocks(n)
+        keep = torch.empty(n, dtype=torch.uint8, device=a.device)
+        blockcount = torch.empty(blocks, dtype=torch.int32, device=a.device)
+        _native.check(lib.camd_overlap_keep(a.data_ptr(), b.data_ptr(), t, n, 2, cu0, cv0, cw, ch, pop[0].data_ptr(),
+                                            pop[1].data_ptr(), keep.data_ptr(), blockcount.data_ptr(), st()), "filter_overlap_uvs")
+        start = torch.zeros(blocks + 1, dtype=torch.int64, device=a.device)
+        torch.cumsum(blockcount, 0, dtype=torch.int64, out=start[1:])  # the exclusive scan between count and emit
+        out = torch.empty((2, n, 2), dtype=a.dtype, device=a.device)
+        _native.check(lib.camd_overlap_emit(a.data_ptr(), b.data_ptr(), t, n, 2, keep.data_ptr(), start.data_ptr(),
+                                            out[0].data_ptr(), out[1].data_ptr(), n, counters.data_ptr(), st()), "filter_overlap_uvs")
+    count, out1, out2 = (int(v) for v in counters.cpu().numpy())  # synchronises: the output length is data dependent
+    if out1 or out2:
+        raise RuntimeError("filter_overlap_uvs: %d rows fell outside the window sized from the data" % (out1 + out2))
+    res = out[0, :count], out[1, :count]
+    return tuple(hostio.to_host_list(*res)) if was_np else res
+
+
+# ---- matching_uvs_in_one_img -------------------------------------------------------------------------------------------
+def matching_uvs_in_one_img(uvs1, uvs2, MAX_DISTANCE=1, MIN_MATCHED_PIXELS=10, precise=False):
+    """Points of two sets that fall into the same ``MAX_DISTANCE`` cell of one image (:241-271): ``dict(uv_match_idx1,
+    uv_match_idx2)`` int64 -- per shared cell the first row of each set landing there, cells in ascending (u, v) order --
+    or ``{}`` when fewer than ``MIN_MATCHED_PIXELS`` cells are shared.  ``precise=True`` (SciPy KDTree + argpartition,
+    whose choice among equal distances is undefined) is refused."""
+    import torch
+    if precise:
+        raise NotImplementedError("precise=True keeps the k smallest distances through np.argpartition, whose choice among "
+                                  "equal distances is undefined: there is nothing to pin -- use precise=False")
+    names = [_float_rows(uvs1, "uvs1"), _float_rows(uvs2, "uvs2", uvs1)]
+    d = float(MAX_DISTANCE)
+    if not (d > 0 and np.isfinite(d)):
+        raise ValueError("MAX_DISTANCE must be a positive number, got %r" % (MAX_DISTANCE,))
+    n1, n2 = int(uvs1.shape[0]), int(uvs2.shape[0])
+    if n1 == 0 or n2 == 0:
+        raise ValueError("matching_uvs_in_one_img needs at least one point in each set")
+    # the quotient's dtype is NumPy's: float32 rows stay float32 unless MAX_DISTANCE itself is a wider NumPy scalar
+    names = [(np.zeros(1, nm) / MAX_DISTANCE).dtype.name for nm in names]
+    hint = " -- raise MAX_DISTANCE (%r)" % (MAX_DISTANCE,)
+    with np.errstate(over="ignore", invalid="ignore"):
+        bounds = [_min_max(uv).astype(nm) / np.dtype(nm).type(d) for uv, nm in zip((uvs1, uvs2), names)]
+    cu0, cv0, cw, ch = _window(bounds, "matching_uvs_in_one_img", hint)
+    was_np = _is_np(uvs1)
+    a = _dev(uvs1, dtype=names[0])
+    b = _dev(uvs2, a.device, dtype=names[1])
+    lib, st = _native.lib(), _native.current_stream
+    with torch.cuda.device(a.device):
+        first = torch.empty((2, cw * ch), dtype=torch.int32, device=a.device)
+        counters = torch.zeros(3, dtype=torch.int64, device=a.device)  # shared cells, rows outside the window of set 1 / 2
+        for k, (uv, nm) in enumerate(zip((a, b), names)):
+            _native.check(lib.camd_cell_first_index(uv.data_ptr(), _UV_TYPES[nm], int(uv.shape[0]), 2, d, cu0, cv0, cw, ch,
+                                                    first[k].data_ptr(), counters[1 + k:].data_ptr(), st()),
+                          "matching_uvs_in_one_img")
+        colcount = torch.empty(cw, dtype=torch.int32, device=a.device)
+        _native.check(lib.camd_cell_intersect_count(first[0].data_ptr(), first[1].data_ptr(), cw, ch, colcount.data_ptr(), st()),
+                      "matching_uvs_in_one_img")
+        start = torch.zeros(cw + 1, dtype=torch.int64, device=a.device)
+        torch.cumsum(colcount, 0, dtype=torch.int64, out=start[1:])  # the exclusive scan between count and emit
+        cap = min(n1, n2)
+        idx = torch.empty((2, cap), dtype=torch.int64, device=a.device)
+        _native.check(lib.camd_cell_intersect_emit(first[0].data_ptr(), first[1].data_ptr(), cw, ch, start.data_ptr(),
+                                                   idx[0].data_ptr(), idx[1].data_ptr(), cap, counters.data_ptr(), st()),
+                      "matching_uvs_in_one_img")
+    count, out1, out2 = (int(v) for v in counters.cpu().numpy())  # synchronises: the output length is data dependent
+    if out1 or out2:
+        raise RuntimeError("matching_uvs_in_one_img: %d rows fell outside the window sized from the data" % (out1 + out2))
+    if count < MIN_MATCHED_PIXELS:
+        return {}
+    i1, i2 = idx[0, :count], idx[1, :count]
+    if was_np:
+        i1, i2 = hostio.to_host_list(i1, i2)
+    return dict(uv_match_idx1=i1, uv_match_idx2=i2)
+
+
+# ---- flow ------------------------------------------------------------------------------------------------------------
+def _flow(flow, what, channel_axis):
+    _check_array(flow, what)
+    if len(flow.shape) != 3 or flow.shape[channel_axis] != 2:
+        want = "(h, w, 2)" if channel_axis == 2 else "(2, h, w)"
+        raise ValueError("%s must be %s, got %s" % (what, want, tuple(flow.shape)))
+    name = _dtype_name(flow)
+    if name not in _UV_TYPES:
+        raise ValueError("%s must be float32 or float64, got %s" % (what, name))
+    hw = [int(s) for i, s in enumerate(flow.shape) if i != channel_axis]
+    if min(hw) <= 0:
+        raise ValueError("%s is empty: %s" % (what, tuple(flow.shape)))
+    return name, hw[0], hw[1]
+
+
+def flow_abs_to_normal(flow_abs):
+    """(h, w, 2) flow in pixels -> float32 (2, h, w) in image widths / heights (flow_utils.py:83-86)."""
+    import torch
+    name, h, w = _flow(flow_abs, "flow_abs", 2)
+    was_np = _is_np(flow_abs)
+    f = _dev(flow_abs)
+    with torch.cuda.device(f.device):
+        out = torch.empty((2, h, w), dtype=torch.float32, device=f.device)
+        rc = _native.lib().camd_flow_abs_to_normal(f.data_ptr(), _UV_TYPES[name], w, h, out.data_ptr(), _native.current_stream())
+    _native.check(rc, "flow_abs_to_normal")
+    return hostio.to_host(out) if was_np else out
+
+
+def flow_normal_to_abs(flow, hw=None):
+    """(2, h, w) normalised flow -> float64 (h, w, 2) in pixels of an image of ``hw`` (default: the flow's own size)
+    (flow_utils.py:89-95; float64 is NumPy's promotion of its ``flow * [[[w]], [[h]]]``)."""
+    import torch
+    name, h, w = _flow(flow, "flow", 0)
+    th, tw = (h, w) if hw is None else hw
+    was_np = _is_np(flow)
+    f = _dev(flow)
+    with torch.cuda.device(f.device):
+        out = torch.empty((h, w, 2), dtype=torch.float64, device=f.device)
+        rc = _native.lib().camd_flow_normal_to_abs(f.data_ptr(), _UV_TYPES[name], w, h, float(tw), float(th), out.data_ptr(),
+                                                   _native.current_stream())
+    _native.check(rc, "flow_normal_to_abs")
+    return hostio.to_host(out) if was_np else out
+
+
+def flow_to_matched_uvs(flow_abs, mask):
+    """``(uvs_from, uvs_to)``, float64 (n, 2): the masked pixels' centres ``(x + 0.5 - 1e-8, y + 0.5 - 1e-8)`` in row-major
+    order and where the flow takes them -- one direction of ``build_set2ds_by_flowds`` (:276-282)."""
+    import torch
+    name, h, w = _flow(flow_abs, "flow_abs", 2)
+    _check_array(mask, "mask")
+    if tuple(mask.shape) != (h, w):
+        raise ValueError("mask %s does not match flow_abs %s" % (tuple(mask.shape), (h, w)))
+    was_np = _is_np(flow_abs)
+    f = _dev(flow_abs)
+    m = _dev(np.asarray(mask != 0) if _is_np(mask) else (mask != 0), f.device).view(torch.uint8)
+    lib = _native.lib()
+    with torch.cuda.device(f.device):
+        rows = torch.empty((2, h * w, 2), dtype=torch.float64, device=f.device)
+        count = torch.zeros(1, dtype=torch.int64, device=f.device)
+        ws = torch.empty(lib.camd_arr2d_mask_workspace_bytes(h), dtype=torch.uint8, device=f.device)
+        rc = lib.camd_flow_to_matched_uvs(f.data_ptr(), _UV_TYPES[name], m.data_ptr(), w, h, rows[0].data_ptr(), rows[1].data_ptr(),
+                                          h * w, count.data_ptr(), ws.data_ptr(), _native.current_stream())
+    _native.check(rc, "flow_to_matched_uvs")
+    n = int(count.item())  # synchronises: the output length is data dependent
+    res = rows[0, :n], rows[1, :n]
+    return tuple(hostio.to_host_list(*res)) if was_np else res
+
+
+def _cat(parts):
+    if _is_np(parts[0]):
+        return np.concatenate(parts)
+    import torch
+    return torch.cat(parts)
+
+
+def build_set2ds_by_flowds(viewds, flowds):
+    """Matched points of every pair of views from optical flow (reconstruction_epipolar_geometry.py:256-295): ``{frozenset
+    ({i, j}): dict(uvs_ij_i, uvs_ij_j, uvs_ji_j, uvs_ji_i, uvs_i, uvs_j)}`` with i < j.  ``flowds[(a, b)]`` holds
+    ``common_fov_mask`` and ``flow_abs`` (h, w, 2) or ``flow_normal`` (2, h, w); a direction whose mask has <= 10 pixels is
+    skipped.  A ``flow_normal`` is scaled to the target view's ``mask`` shape when ``viewds`` has one, else to its own
+    (h, w) (the reference passes the whole 3-tuple there and fails on it)."""
+    set2ds = {}
+    for set2 in set(map(frozenset, flowds)):
+        ij = tuple(sorted(set2))
+        set2d = {}
+        for xx, name in ((ij, "ij"), (ij[::-1], "ji")):
+            if xx not in flowds:
+                continue
+            mask = flowds[xx]["common_fov_mask"]
+            if not int((mask != 0).sum()) > 10:
+                continue
+            flow_abs = flowds[xx].get("flow_abs")
+            if flow_abs is None:
+                flow_normal = flowds[xx]["flow_normal"]
+                target = viewds[xx[-1]]["mask"].shape if "mask" in viewds[xx[-1]] else tuple(flow_normal.shape)[-2:]
+                flow_abs = flow_normal_to_abs(flow_normal, tuple(target)[:2])
+            set2d["uvs_%s_%s" % (name, name[0])], set2d["uvs_%s_%s" % (name, name[1])] = flow_to_matched_uvs(flow_abs, mask)
+        if set2d:
+            set2d["uvs_i"] = _cat([set2d[k] for k in set2d if k in ("uvs_ij_i", "uvs_ji_i")])
+            set2d["uvs_j"] = _cat([set2d[k] for k in list(set2d) if k in ("uvs_ij_j", "uvs_ji_j")])
+            set2ds[set2] = set2d
+    return set2ds
+
+
+# ---- EssentialMatrixStereo ---------------------------------------------------------------------------------------------
+class EssentialMatrixStereo(Stereo):
+    """A ``Stereo`` whose pose comes from matched pixels: 8-point essential matrix, four candidate poses, the first whose
+    mean depths in both cameras are positive (:100-150).  ``self.epipolar`` holds ``zs1, zs2, uvs1, uvs2`` (arrays of the
+    caller's kind), ``E`` (3x3 ndarray) and ``z1, z2`` (the winner's mean depths, floats)."""
+
+    def __init__(self, uvs1=None, uvs2=None, K1=None, K2=None, baseline=1, xy1=None, xy2=None, name1="cam1", name2="cam2"):
+        import torch
+        if uvs1 is None:  # (type(self)() as Stereo.copy makes it)
+            super().__init__()
+            return
+        if K2 is None:
+            K2 = K1
+        if name1 == name2:
+            raise ValueError("the two cameras need different names, got %r twice" % (name1,))
+        if xy1 is None or xy2 is None:
+            raise ValueError("xy1 and xy2 (width, height of each camera) are required: the reference's fallback reads column 3 "
+                             "of a 3x3 K and cannot work")
+        _float_rows(uvs1, "uvs1")
+        _float_rows(uvs2, "uvs2", uvs1)
+        n = int(uvs1.shape[0])
+        if int(uvs2.shape[0]) != n or n < 8:
+            raise ValueError("uvs1, uvs2 must hold the same number (>= 8) of matches, got %d and %d" % (n, uvs2.shape[0]))
+        K1, K2 = np.asarray(K1, np.float64), np.asarray(K2, np.float64)
+        if K1.shape != (3, 3) or K2.shape != (3, 3):
+            raise ValueError("K1, K2 must be 3x3")
+        E, Ts = _pose_candidates(uvs1, uvs2, K1, K2, baseline)
+        a = _dev(uvs1, dtype="float64")
+        b = _dev(uvs2, a.device, dtype="float64")
+        means = _candidate_means(a, b, K1, K2, Ts)
+        # the first candidate with both means positive; if none is, the last one, as the reference's loop leaves it
+        self.candidate = next((c for c in range(4) if means[c, 0] > 0 and means[c, 1] > 0), 3)
+        T = Ts[self.candidate]
+        with torch.cuda.device(a.device):
+            zs = matched_uvs_to_zs(a, b, K1, K2, T)
+        if _is_np(uvs1):
+            zs["zs1"], zs["zs2"] = hostio.to_host_list(zs["zs1"], zs["zs2"])
+        super().__init__()
+        self.load(dict(R=T[:3, :3], t=T[:3, 3], cam1=dict(xy=list(xy1), K=K1, name=str(name1)),
+                       cam2=dict(xy=list(xy2), K=K2, name=str(name2))))
+        self.epipolar = dict(zs, E=E, uvs1=uvs1, uvs2=uvs2, z1=float(means[self.candidate, 0]), z2=float(means[self.candidate, 1]))
+
+    @classmethod
+    def from_stereo(cls, uvs1, uvs2, stereo, baseline=None):
+        """The pose re-estimated from matches for an existing rig: everything of ``stereo``'s record is kept (distortion
+        included), ``R`` and ``t`` are replaced (:152-166).  ``baseline=None``: the rig's own."""
+        self = cls(uvs1, uvs2, K1=stereo.cam1.K, K2=stereo.cam2.K, xy1=stereo.cam1.xy, xy2=stereo.cam2.xy,
+                   baseline=baseline or stereo.baseline)
+        rec = stereo.dump(return_dict=True)
+        rec["R"], rec["t"] = self.R, self.t
+        self.load(rec)
+        return self
+
+    def set_scale(self, rate):
+        """Scale the translation (hence ``baseline``) and every depth of ``epipolar`` by ``rate`` (:194-202).  The
+        rectifying rotations and maps depend on the direction of ``t`` only; ``min_disparity``, which
+        ``set_stereo_matching`` derived from the baseline, is brought up to date."""
+        rate = float(rate)
+        self.t = self.t * rate
+        for key in ("z1", "z2", "zs1", "zs2"):
+            self.epipolar[key] *= rate
+        if hasattr(self, "min_disparity"):
+            self.min_disparity = int(self.cam1.K[0, 0] * self.baseline / self.max_depth)
+        return self
+
+    def align_scale_with(stereo1, stereo2, matched=None):
+        """Bring this rig to the scale of ``stereo2``, which shares exactly one camera (by name) with it (:168-192): the
+        ratio of the mean depths, in the shared camera, of the points both rigs matched."""
+        mine, other = [stereo1.cam1.name, stereo1.cam2.name], [stereo2.cam1.name, stereo2.cam2.name]
+        for pair in (mine, other):
+            assert pair[0] != pair[1], "a rig needs two different camera names, got %s" % (pair,)
+        shared = [nm for nm in mine if nm in other]
+        assert len(shared) != 2, "names1=%s and names2=%s are the same pair of cameras" % (mine, other)
+        assert len(shared) != 0, "names1=%s and names2=%s share no camera" % (mine, other)
+        s1, s2 = str(mine.index(shared[0]) + 1), str(other.index(shared[0]) + 1)
+        if matched is None:
+            matched = matching_uvs_in_one_img(stereo1.epipolar["uvs" + s1], stereo2.epipolar["uvs" + s2])
+        assert len(matched.get("uv_match_idx1", ())) > 10, "more than 10 points matched by both rigs are needed"
+        z_mine = _mean(stereo1.epipolar["zs" + s1], matched["uv_match_idx1"], "align_scale_with")
+        z_other = _mean(stereo2.epipolar["zs" + s2], matched["uv_match_idx2"], "align_scale_with")
+        return stereo1.set_scale(z_other / z_mine)

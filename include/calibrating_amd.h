@@ -340,6 +340,76 @@ int camd_matched_uvs_to_zs(const double* uv1, const double* uv2, size_t n, const
                            const double K2inv_host[9], const double T_1to2_host[16], double* zs1, double* zs2,
                            void* stream);
 
+/* ---- pose from matched points: the epipolar path (csrc/epipolar.hip) -----------------------------------------
+ * The device side of calibrating_amd/epipolar_geometry.py (the reference's epipolar_geometry.py, flow_utils.py and
+ * ReconstructionExtrinsics.build_set2ds_by_flowds).  Integer atomics only and fixed-order float sums: identical calls
+ * give identical bits.  uv rows: uv_type CAMD_VALUE_F64 / CAMD_VALUE_F32, uv_stride >= 2 elements (u, v, ...), n < 2^32 - 1.
+ * A cell window is cells cu0 .. cu0 + cells_w - 1 by cv0 .. cv0 + cells_h - 1, at most 2^28 cells, stored U-MAJOR:
+ * grid[(cu - cu0) * cells_h + (cv - cv0)].  *outside (device u64, cleared by the entry point) counts the rows that
+ * fall outside the window (NaN / inf among them); the caller sizes the window from the data, so it must read 0.
+ *
+ * replaces np.unique(np.int32((uv / max_distance).round()), axis=0, return_index=True): cell = int32(rint(u / d)),
+ * int32(rint(v / d)) -- the division in the rows' own type, half to even -- and first[cell] = the smallest row index
+ * landing there, 0xFFFFFFFF where none does (first is cleared here).  max_distance > 0.                          */
+int camd_cell_first_index(const void* uv, int uv_type, size_t n, int uv_stride, double max_distance, int cu0, int cv0,
+                          int cells_w, int cells_h, uint32_t* first, unsigned long long* outside, void* stream);
+/* ... return_counts=True instead, for max_distance = 1: population[cell] = how many rows land there (cleared here) */
+int camd_cell_population(const void* uv, int uv_type, size_t n, int uv_stride, int cu0, int cv0, int cells_w, int cells_h,
+                         uint32_t* population, unsigned long long* outside, void* stream);
+/* replaces np.intersect1d of the two sorted cell lists: the cells set in both grids, as (first1, first2) pairs in
+ * ascending (u cell, v cell) order -- u the major key, signed -- which is the linear order of the u-major grid.
+ *   camd_cell_intersect_count -> colcount[cells_w]: shared cells per u column
+ *   caller: start[0] = 0, start[c + 1] = start[c] + colcount[c]  (cells_w + 1 int64 entries; any scan: it is plumbing)
+ *   camd_cell_intersect_emit  -> idx1 / idx2 [capacity] int64, *count (device u64) = start[cells_w]
+ * Both launch ONE WORKGROUP PER u COLUMN (cells_w of them) and the scan has cells_w entries: sized for image-shaped
+ * windows.  A window that is wide in u and short in v (up to 2^28 x 1) is computed correctly but costs up to 2^28
+ * nearly empty workgroups.                                                                                       */
+int camd_cell_intersect_count(const uint32_t* first1, const uint32_t* first2, int cells_w, int cells_h, uint32_t* colcount,
+                              void* stream);
+int camd_cell_intersect_emit(const uint32_t* first1, const uint32_t* first2, int cells_w, int cells_h, const long long* start,
+                             long long* idx1, long long* idx2, size_t capacity, unsigned long long* count, void* stream);
+/* replaces filter_overlap_uvs (epipolar_geometry.py:205-216): keep[i] = the pixel int32(rint(u, v)) of uv1[i] is hit by
+ * no other row of uv1 AND the same for uv2[i] (population1 / population2: camd_cell_population of each set over one
+ * window), then uvs[mask] -- the kept rows in their own order, dtype kept.
+ *   camd_overlap_keep -> keep[n] bytes, blockcount[camd_overlap_blocks(n)]: kept rows per 256 rows
+ *   caller: start[0] = 0, start[b + 1] = start[b] + blockcount[b]  (blocks + 1 int64 entries)
+ *   camd_overlap_emit -> out1 / out2 [capacity][2] of uv_type, *count (device u64) = start[blocks]                */
+int camd_overlap_blocks(size_t n);
+int camd_overlap_keep(const void* uv1, const void* uv2, int uv_type, size_t n, int uv_stride, int cu0, int cv0, int cells_w,
+                      int cells_h, const uint32_t* population1, const uint32_t* population2, uint8_t* keep,
+                      uint32_t* blockcount, void* stream);
+int camd_overlap_emit(const void* uv1, const void* uv2, int uv_type, size_t n, int uv_stride, const uint8_t* keep,
+                      const long long* start, void* out1, void* out2, size_t capacity, unsigned long long* count, void* stream);
+/* The cheirality test of EssentialMatrixStereo.__init__ (:121-130) for all four candidate poses in one pass: every
+ * match is read once and solved for (z1, z2) under each T_1to2[c] (four 4x4 row-major host matrices, t already scaled
+ * to the baseline) by the very function camd_matched_uvs_to_zs evaluates.  sums[c * 2 + 0 / 1] (device, 8 doubles) =
+ * sum of zs1 / zs2 under candidate c; the caller divides by n.  uv1, uv2: [n][2] float64 contiguous, n >= 1.
+ * REDUCTION SHAPE (no float atomics): G = camd_epipolar_sums_blocks(n) = clamp(ceil(n / 256), 1, 1024) workgroups of 256
+ * threads; a thread adds its rows serially, at most m = ceil(n / (256 G)) terms; above that a binary tree of
+ * d = 8 (workgroup) + 2 (four partials per thread of the final workgroup) + 8 (final workgroup) = 18 levels.
+ * partials_ws: G * 8 doubles.                                                                                    */
+int camd_epipolar_sums_blocks(size_t n);
+int camd_epipolar_sums(const double* uv1, const double* uv2, size_t n, const double K1inv_host[9], const double K2inv_host[9],
+                       const double T_1to2_host[64], double* partials_ws, double* sums, void* stream);
+/* sums[0] (device) = sum of z[i], i < n (idx == NULL, n <= z_len) or of z[idx[i]] (idx: [n] int64) -- the numerator of
+ * zs.mean() / zs[idx].mean() in align_scale_with (:189-191); sums[1] = how many idx[i] lie outside [0, z_len) (they add
+ * nothing; must read 0).  Same reduction shape as camd_epipolar_sums: m = ceil(n / (256 G)), d = 18, G =
+ * camd_vector_sum_blocks(n); partials_ws: G * 2 doubles.  n >= 1.                                                */
+int camd_vector_sum_blocks(size_t n);
+int camd_vector_sum(const double* z, size_t z_len, const long long* idx, size_t n, double* partials_ws, double* sums,
+                    void* stream);
+/* replaces the flow-to-matches step of build_set2ds_by_flowds (reconstruction_epipolar_geometry.py:276-282): for the
+ * masked pixels (bytes, non-zero = taken) in row-major order uvs_from = ((x + 0.5) - 1e-8, (y + 0.5) - 1e-8) and
+ * uvs_to = float64(flow) + uvs_from, both [capacity][2] float64.  flow_abs: [h][w][2] of flow_type.  *count (device u64)
+ * = how many; rows beyond capacity are not written.  workspace: camd_arr2d_mask_workspace_bytes(h) bytes.         */
+int camd_flow_to_matched_uvs(const void* flow_abs, int flow_type, const uint8_t* mask, int w, int h, double* uvs_from,
+                             double* uvs_to, size_t capacity, unsigned long long* count, void* workspace, void* stream);
+/* replaces flow_utils.flow_abs_to_normal: [h][w][2] -> float32 [2][h][w], float32(float64(flow) / (w, h))          */
+int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, float* flow_normal, void* stream);
+/* replaces flow_utils.flow_normal_to_abs: [2][h][w] -> float64 [h][w][2], float64(flow) * (target_w, target_h)    */
+int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h, double target_w, double target_h,
+                            double* flow_abs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
