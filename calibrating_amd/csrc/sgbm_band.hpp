@@ -34,23 +34,11 @@
 
 namespace camd {
 
-// 7 compute waves + 1 helper wave = 8 waves per workgroup: two workgroups fill a CU's 16 wave slots at
-// <= 128 VGPRs (nine waves would leave room for only one).
-//   CAMD_BAND_MERGED 1 (measurement build; rounds 3 and 6): all 8 waves compute (bands of 8 * 64 / LANES rows) and wave
-//       CAMD_BAND_DUTY_WAVE runs the helper's few instructions every CPB steps on the side, so that every SIMD carries
-//       four compute waves instead of 4, 4, 3, 3.  Bit-exact, and no faster: first pass 15.07 against 15.05 ms per 64
-//       pairs, MODE_SGBM last pass 11.4 / 11.6, MODE_HH last pass 23.0 against 19.1 (122 / 128 VGPRs, the latter with
-//       100 bytes of scratch) -- profiles/r06_band_ab.txt.  The pass is not bound by its busiest SIMDs: half the
-//       arithmetic (MODE_HH4's two directions) takes 12.4 ms, no S stores 12.9, both 8.5 (profiles/r06_band_probe.txt).
-#ifndef CAMD_BAND_MERGED
-#define CAMD_BAND_MERGED 0
-#endif
-#ifndef CAMD_BAND_COMPUTE_WAVES
-#define CAMD_BAND_COMPUTE_WAVES (CAMD_BAND_MERGED ? 8 : 7)
-#endif
-#ifndef CAMD_BAND_HELPER_WAVE
-#define CAMD_BAND_HELPER_WAVE CAMD_BAND_COMPUTE_WAVES    // !MERGED: which wave of the workgroup is the helper (default: the last)
-#endif
+// 7 compute waves + 1 helper wave (the last of the workgroup) = 8 waves per workgroup: two workgroups fill a CU's 16
+// wave slots at <= 128 VGPRs (nine waves would leave room for only one).
+// (all 8 waves computing, the helper's duty merged into one of them: no faster, MODE_HH slower: profiles/r06_band_ab.txt)
+// (the edge flags raised two steps late behind a counted s_waitcnt vmcnt(N): 15.17 vs 15.26 ms, profiles/r06_flag_delay.txt)
+// (the row-parallel pass of k_band with its would-be helper wave computing too: within the noise, profiles/r05_exp_rowpass.txt)
 // Cache policy of the volume accesses (bit 0: the C / S loads carry `nt`, bit 1: the S stores too).  Every volume byte is
 // read once per pass; streamed past the L2's replacement order the first pass takes 15.1 instead of 15.3 ms and the
 // row-parallel last pass 11.6 instead of 12.2 per 64 pairs (profiles/r06_band_nt.txt, three A/B repetitions).  `nt` on the
@@ -58,29 +46,18 @@ namespace camd {
 #ifndef CAMD_BAND_NT
 #define CAMD_BAND_NT 1
 #endif
-#ifndef CAMD_BAND_FLAG_DELAY
-#define CAMD_BAND_FLAG_DELAY 0                           // steps between a chunk's last column and its flag (0 = drain at once)
-#endif
 #ifndef CAMD_ROW_PERSIST_PRIO
 #define CAMD_ROW_PERSIST_PRIO 3                          // s_setprio of k_band_row_persist's waves (0 = leave it)
-#endif
-#ifndef CAMD_BAND_DUTY_WAVE
-#define CAMD_BAND_DUTY_WAVE 0                            // MERGED: the compute wave that also feeds the edge ring
 #endif
 #ifndef CAMD_BAND_MIN_WAVES
 #define CAMD_BAND_MIN_WAVES 4                            // occupancy target (waves per SIMD) of the D <= 128 instantiations
 #endif
-// the row-parallel (!FULL) pass has no helper duty: 1 = all eight waves of its workgroups compute (rows per workgroup =
-// BAND_BLOCK / LANES), 0 = the wave that would be the helper just exits (round 1-4)
-#ifndef CAMD_BAND_ROW_ALL_WAVES
-#define CAMD_BAND_ROW_ALL_WAVES 0
-#endif
 #ifndef CAMD_BAND_ROW_MIN_WAVES
 #define CAMD_BAND_ROW_MIN_WAVES CAMD_BAND_MIN_WAVES      // occupancy target of the row-parallel pass (it needs 66 VGPRs)
 #endif
-static constexpr int BAND_THREADS = 64 * CAMD_BAND_COMPUTE_WAVES;  // compute threads
-static constexpr int BAND_BLOCK = BAND_THREADS + (CAMD_BAND_MERGED ? 0 : 64);  // (+ one helper wave)
-static constexpr int BAND_HELPER_WAVE = CAMD_BAND_HELPER_WAVE;
+static constexpr int BAND_THREADS = 64 * 7;              // compute threads
+static constexpr int BAND_BLOCK = BAND_THREADS + 64;     // (+ one helper wave)
+static constexpr int BAND_HELPER_WAVE = 7;
 static constexpr int BAND_RING = 4;                      // C/S prefetch ring (xi .. xi+3)
 #ifndef BAND_RING_ROWS
 #define BAND_RING_ROWS 4                                 // ... of the row-parallel (!FULL) pass
@@ -284,7 +261,8 @@ __device__ __forceinline__ void band_wta_flush(const BandArgs& a, const Geom& g,
 // FULL: H, V, Dg, A of sweep (sx, sy), skew 2.  !FULL: H of sweep sx only (rows independent).
 // MODE: 0 = first pass (S written), 2 = final (S read, WTA; S stored only for the parity hook)
 // DIAG = false (MODE_HH4): the two diagonal directions are left out (their slots travel as zeros)
-// ALLW (row-parallel pass only): all waves of the workgroup compute (rows per ticket = BAND_BLOCK / LANES)
+// ALLW (row-parallel pass only, k_band_row_persist): all waves of the workgroup compute (rows per ticket = BAND_BLOCK / LANES);
+//   in k_band's row-parallel pass the helper wave just exits
 // ticket: the (pair, band) / run of rows this call works on (k_band: one per workgroup; k_band_row_persist: a loop)
 template <int LANES, int NR, bool FULL, int MODE, bool PAD, bool DIAG, bool TIE8, bool ALLW>
 __device__ __forceinline__ void band_body(const BandArgs& a, const Geom& g, const int ticket)
@@ -292,7 +270,6 @@ __device__ __forceinline__ void band_body(const BandArgs& a, const Geom& g, cons
     static_assert(!(FULL && ALLW), "the wavefront pass keeps its helper wave");
     constexpr int NQ = (NR + 3) / 4;  // 16-byte LDS slots / u64 edge-record pairs per lane and vector
     constexpr int NTH = (!FULL && ALLW) ? BAND_BLOCK : BAND_THREADS;  // compute threads of a workgroup
-    static_assert(!CAMD_BAND_MERGED || BAND_BLOCK == BAND_THREADS, "merged helper duty: every wave computes");
     constexpr int R = NTH / LANES;
     constexpr int EVEC = 6 * NQ;     // u64 per lane per column: V (2NQ), Dg (2NQ), A (2NQ)
     constexpr int CPB = 64 / LANES;  // columns the helper wave fetches per batch
@@ -315,13 +292,12 @@ __device__ __forceinline__ void band_body(const BandArgs& a, const Geom& g, cons
     // dependency (pair, b-1) always holds an earlier ticket)
     // (the row-parallel pass has no bands: its groups take consecutive rows of the whole batch -- see below)
     const int band = FULL ? ticket / a.npairs : 0;
-    // roles: wave BAND_HELPER_WAVE is the helper, the others are compute waves numbered in wave order (ctid =
-    // compute thread index).  Which wave helps decides which SIMD carries one compute wave less (see
-    // tools/microtests/wave_simd_placement.hip)
+    // roles: wave BAND_HELPER_WAVE is the helper, the others are compute waves (ctid = compute thread index).  Which wave
+    // helps decides which SIMD carries one compute wave less (see tools/microtests/wave_simd_placement.hip)
     const int wv = threadIdx.x >> 6;
-    const bool helper = !CAMD_BAND_MERGED && (FULL || !ALLW) && wv == BAND_HELPER_WAVE;  // wave-uniform
+    const bool helper = (FULL || !ALLW) && wv == BAND_HELPER_WAVE;  // wave-uniform
     if (!FULL && helper) return;
-    const int ctid = (CAMD_BAND_MERGED || (!FULL && ALLW)) ? (int)threadIdx.x
+    const int ctid = (!FULL && ALLW) ? (int)threadIdx.x
                      : helper ? (int)(threadIdx.x & 63) : (((wv > BAND_HELPER_WAVE ? wv - 1 : wv) << 6) | (int)(threadIdx.x & 63));
     const int grp = ctid / LANES, li = ctid % LANES;
     const int W1 = g.W1, H = g.H;
@@ -336,8 +312,7 @@ __device__ __forceinline__ void band_body(const BandArgs& a, const Geom& g, cons
     const int glast = min(R, H - band * R) - 1;
     const bool has_prev = FULL && band > 0, has_next = FULL && band + 1 < a.nbands;
     const bool producer = !helper && has_next && grp == glast;
-    // the wave that keeps the edge ring filled: the helper wave, or (MERGED) one compute wave on the side
-    const bool hduty = FULL && has_prev && (CAMD_BAND_MERGED ? __builtin_amdgcn_readfirstlane(wv) == CAMD_BAND_DUTY_WAVE : helper);
+    const bool hduty = FULL && has_prev && helper;  // the helper wave keeps the edge ring filled
 
     const uint32_t P1pk = dup16((uint32_t)g.P1), P2pk = dup16((uint32_t)g.P2);
     uint32_t keep[NR], sent[NR], dpk[NR];
@@ -509,10 +484,6 @@ __device__ __forceinline__ void band_body(const BandArgs& a, const Geom& g, cons
             const int t = t0 + u;
             const int xi = t - SK * grp;
             const bool act = rvalid && xi >= 0 && xi < W1;
-            if (CAMD_BAND_MERGED && FULL) {
-                // (wave-uniform; with CPB == RING a compile-time position in the unrolled body)
-                if ((CPB == RING ? u == 0 : (t % CPB) == 0) && hduty) duty_step(t);
-            }
             {
                 constexpr int UP = (RING - 1);
                 const int xp = min(max(xi + UP, 0), W1 - 1);
@@ -620,37 +591,12 @@ __device__ __forceinline__ void band_body(const BandArgs& a, const Geom& g, cons
                                            __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(q + 1, (unsigned long long)dAo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
-#if CAMD_BAND_FLAG_DELAY == 0
                     if ((xi % BAND_CHUNK) == BAND_CHUNK - 1 || xi == W1 - 1) {
                         // the write-through stores of the whole chunk must have landed before the flag is raised
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         if (li == 0)
                             __hip_atomic_store(Fout + xi / BAND_CHUNK, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
-#else
-                    // The write-through stores of a whole chunk must have landed before its flag is raised.  Waiting for
-                    // them right behind the chunk's last store (s_waitcnt vmcnt(0)) also drains this wave's C / S prefetch
-                    // ring and the stores just issued: one full memory latency every BAND_CHUNK steps during which the
-                    // other six waves stand at the barrier.  The memory counter retires in order, so the flag of a chunk is
-                    // raised FLAG_DELAY steps after its last column instead, behind a COUNTED wait: every step the producer
-                    // group is active in issues at least OPS vector-memory operations in this wave (the C load, the S store
-                    // or load, the edge-record stores), so once all but the newest FLAG_DELAY * OPS have retired, everything
-                    // up to the chunk's last store has.  The last column of the row drains and raises what is left.
-                    constexpr int FLAG_DELAY = CAMD_BAND_FLAG_DELAY;
-                    constexpr int OPS = 3 * ((NR + 1) / 2) + 2 + 2;  // (lower bound: edge vectors + 2 delta stores + C + S)
-                    static_assert(FLAG_DELAY * OPS <= 63, "vmcnt is a 6-bit counter");
-                    if (xi == W1 - 1) {
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        // chunks whose delayed raise (at column 16 m + 15 + FLAG_DELAY) lies before this column are up
-                        const int up = W1 - 2 - FLAG_DELAY - (BAND_CHUNK - 1) >= 0 ? (W1 - 2 - FLAG_DELAY - (BAND_CHUNK - 1)) / BAND_CHUNK + 1 : 0;
-                        if (li < a.nchunks - up)
-                            __hip_atomic_store(Fout + up + li, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else if (xi >= FLAG_DELAY && ((xi - FLAG_DELAY) % BAND_CHUNK) == BAND_CHUNK - 1) {
-                        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FLAG_DELAY * OPS) : "memory");
-                        if (li == 0)
-                            __hip_atomic_store(Fout + (xi - FLAG_DELAY) / BAND_CHUNK, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-#endif
                 }
                 // LDS-only barrier (a __syncthreads() would drain the C/S prefetch ring)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -671,7 +617,7 @@ __global__ __launch_bounds__(BAND_BLOCK, NR <= 4 ? (FULL ? CAMD_BAND_MIN_WAVES :
     __shared__ uint32_t s_ticket;
     if (threadIdx.x == 0) s_ticket = atomicAdd(a.ticket, 1u);
     __syncthreads();
-    band_body<LANES, NR, FULL, MODE, PAD, DIAG, TIE8, !FULL && CAMD_BAND_ROW_ALL_WAVES>(a, g, (int)s_ticket);
+    band_body<LANES, NR, FULL, MODE, PAD, DIAG, TIE8, false>(a, g, (int)s_ticket);
 }
 
 // The row-parallel last pass with a FIXED number of resident workgroups (grid = workgroups per CU x 256) that take runs

@@ -33,7 +33,7 @@
 
 namespace camd {
 
-static constexpr int COST_DL = 8;  // disparities per lane (the DL = 16 instantiations: two such octets, see k_cost)
+static constexpr int COST_DL = 8;  // disparities per lane (16 per lane: 98 VGPRs, 17.0 against 15.5 ms, profiles/r06_cost_ab.txt)
 // tunables (measured on MI355X)
 #ifndef CAMD_COST_MAX_WAVES_RGB
 #define CAMD_COST_MAX_WAVES_RGB 8    // waves per workgroup (x 8 disparities each)
@@ -44,23 +44,12 @@ static constexpr int COST_DL = 8;  // disparities per lane (the DL = 16 instanti
 #ifndef CAMD_COST_MIN_WAVES
 #define CAMD_COST_MIN_WAVES 6        // occupancy target (waves per SIMD) the register allocator works to
 #endif
-#ifndef CAMD_COST_MIN_WAVES_DL16
-#define CAMD_COST_MIN_WAVES_DL16 4   // ... of the 16-disparities-per-lane form (K rows x 8 ring registers)
-#endif
 // The per-cell tail of the BT cost (sum over the colour planes with the raw planes >> 2, then two cells per register):
-//   0  round 2-5: v_pk_lshrrev_b16 + v_dot2_u32_u16 per channel and cell, v_lshl_or + v_and per pair of cells --
-//      all of them in the class that issues at ~0.9 per cycle and CU (tools/microtests/valu_rate.hip)
-//   1  floor(x / 4) summed over the channels = (sum of (x & ~3)) >> 2: the mask rides in the v_bitop3_b32 that ORs the
-//      two saturating differences anyway, the channels are summed with plain v_add_u32 (no half can carry:
-//      3 * 255 < 2^16), and the gradient / raw halves of two cells are regrouped by two v_perm_b32 so that ONE plain
-//      shift + add finishes both cells.  Per RGB cell: 7 "slow-class" instructions -> 1, + 3.5 plain ones.
-#ifndef CAMD_COST_TAIL
-#define CAMD_COST_TAIL 1
-#endif
-// the staging arithmetic: 0 = round 2-5 form, 1 = round 6 form (see stage_entries)
-#ifndef CAMD_COST_STAGE
-#define CAMD_COST_STAGE 1
-#endif
+// floor(x / 4) summed over the channels = (sum of (x & ~3)) >> 2: the mask rides in the v_bitop3_b32 that ORs the two
+// saturating differences anyway, the channels are summed with plain v_add_u32 (no half can carry: 3 * 255 < 2^16), and
+// the gradient / raw halves of two cells are regrouped by two v_perm_b32 so that ONE plain shift + add finishes both
+// cells.  Per RGB cell one instruction of the class that issues at ~0.9 per cycle and CU (tools/microtests/valu_rate.hip)
+// + 3.5 plain ones; the round 2-5 tail and staging (seven per cell): profiles/r06_cost_ab.txt.
 #ifndef CAMD_COST_LDS_FLOOR_RGB
 #define CAMD_COST_LDS_FLOOR_RGB (41 * 1024)
 #endif
@@ -74,16 +63,7 @@ static constexpr int COST_DL = 8;  // disparities per lane (the DL = 16 instanti
 #ifndef CAMD_COST_TSTORE
 #define CAMD_COST_TSTORE 1
 #endif
-// 1 (measurement build): the C stores carry `nt`.  A pixel's 256-byte disparity vector is written 16 bytes at a time by
-// 16 waves of two workgroups; streamed past the L2 those pieces reach HBM as partial lines: 72 instead of 16 ms
-// (profiles/r06_band_nt.txt).  The L2's write combining is what makes the "lanes = columns" store pattern affordable.
-#ifndef CAMD_COST_NT
-#define CAMD_COST_NT 0
-#endif
-// 1: RGB at blockSize <= 5 runs 16 disparities per lane (sgbm.hip: the launch); 2: gray too; 0: 8 everywhere
-#ifndef CAMD_COST_DL16
-#define CAMD_COST_DL16 0
-#endif
+// (`nt` on the C stores defeats the L2's write combining, 72 instead of 16 ms: profiles/r06_band_nt.txt)
 
 // n applications of the one-lane wave shift (lane i <- lane i-1, lane 0 <- 0)
 template <int N>
@@ -122,29 +102,8 @@ __device__ __forceinline__ uint32_t lane_window_sum(uint32_t p)
     return p + wave_shr<1>(w10);
 }
 
-// The same window as a difference of wave-wide inclusive prefix sums: six DPP adds (row_shr 1, 2, 4, 8, row_bcast 15 / 31)
-// + one ds_bpermute for P(l - K) instead of K - 1 single-lane shifts.  For K >= 9 (the reference's block 11: ten
-// shifts + five adds per packed register).  The halves cannot carry: a prefix over 64 lanes of pixel costs is at most
-// 64 * CN * (2 * CAMD_MAX_FTZERO + 63) < 65536.  `back` = byte address of lane l - K for ds_bpermute, `live` = l >= K.
-// Measured in round 5 on the reference's default matcher (block 11 x RGB, 64 pairs of 1000 x 562): 9.7 ms either way
-// (bit-exact; tools/gpu_default_batch.py) -- at block 11 the kernel is not bound by the count of its window operations
-// (four waves per SIMD at 128 VGPRs for the 11-row ring, 27 ds_read_b128 per row).  Off by default.
-#ifndef CAMD_COST_SCAN_WINDOW
-#define CAMD_COST_SCAN_WINDOW 0
-#endif
-static_assert(64 * 3 * (2 * CAMD_MAX_FTZERO + 63) < 65536, "a 64-lane prefix of pixel costs must fit a 16-bit half");
-__device__ __forceinline__ uint32_t lane_window_sum_scan(uint32_t p, int back, bool live)
-{
-    uint32_t s = p;
-    s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x111, 0xf, 0xf, false);  // row_shr:1
-    s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x112, 0xf, 0xf, false);  // row_shr:2
-    s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x114, 0xf, 0xf, false);  // row_shr:4
-    s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x118, 0xf, 0xf, false);  // row_shr:8
-    s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-    s += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-    const uint32_t prev = (uint32_t)__builtin_amdgcn_ds_bpermute(back, (int)s);
-    return s - (live ? prev : 0u);
-}
+// (the same window as a difference of wave-wide prefix sums, for K >= 9: 9.7 ms either way on the matcher of
+// profiles/r05_default_matcher.json, HISTORY.md round 5)
 
 // Row ranges the cost volume is built for.  Every mode but MODE_SGBM_3WAY has ONE range, the image; 3WAY has one per
 // stripe (cv2 computes its stripes independently: the vertical box window is clamped at the stripe's first row, and
@@ -158,12 +117,12 @@ struct CostRanges {
 // C leaves the kernel through LDS (CAMD_COST_TSTORE bit 0: gray, bit 1: RGB) when the waves of the workgroup divide the
 // strip's 64 columns: see the store in cost_body
 constexpr bool cost_tstore(int cn) { return (CAMD_COST_TSTORE & (cn == 1 ? 1 : 2)) != 0; }
-static inline bool cost_tstore_shape(int cn, int nwaves, int dl) { return cost_tstore(cn) && dl == COST_DL && 64 % nwaves == 0; }
-static inline size_t cost_lds_bytes(int cn, int nwaves, int dl = COST_DL)
+static inline bool cost_tstore_shape(int cn, int nwaves) { return cost_tstore(cn) && 64 % nwaves == 0; }
+static inline size_t cost_lds_bytes(int cn, int nwaves)
 {
-    const int es = cn == 1 ? 4 : 12, dw = nwaves * dl;
+    const int es = cn == 1 ? 4 : 12, dw = nwaves * COST_DL;
     const int nr = 64 + dw - 1, nl = 64;
-    const size_t need = (size_t)2 * (nr + nl) * es * 4 + (cost_tstore_shape(cn, nwaves, dl) ? (size_t)2 * 64 * (nwaves + 1) * 16 : 0);
+    const size_t need = (size_t)2 * (nr + nl) * es * 4 + (cost_tstore_shape(cn, nwaves) ? (size_t)2 * 64 * (nwaves + 1) * 16 : 0);
     // RGB at 8 waves: the kernel needs 64 VGPRs, so FOUR workgroups would fit a CU and fill every wave slot -- which leaves
     // the other batch in flight (bench.py's second stream) no room beside it.  Asking for a third of the LDS keeps it at three.
     return (cn == 3 && nwaves == 8 && need < CAMD_COST_LDS_FLOOR_RGB) ? (size_t)CAMD_COST_LDS_FLOOR_RGB : need;
@@ -177,14 +136,11 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // The register ring of the vertical box sum holds K rows of 4 registers: from blockSize 9 on the kernel does not fit the
 // 80 registers of six waves per SIMD (blockSize 11 RGB, the reference's default: 40 spilled, 10.5 ms per 64 pairs of
 // 1000 x 562, D = 218); allowed 96 / 128 it runs without scratch traffic on fewer waves: 9.7 / 9.6 ms.
-constexpr int cost_min_waves(int K, int DL = COST_DL)
-{
-    return DL > 8 ? CAMD_COST_MIN_WAVES_DL16 : (K >= 11 ? 4 : (K >= 9 ? 5 : CAMD_COST_MIN_WAVES));
-}
+constexpr int cost_min_waves(int K) { return K >= 11 ? 4 : (K >= 9 ? 5 : CAMD_COST_MIN_WAVES); }
 
 // the work of one (strip bx, row chunk x disparity block by, volume bz) -- k_cost's workgroup, or one item of a
 // persistent workgroup (k_cost_persist)
-template <int CN, int K, bool SAT, int DL>
+template <int CN, int K, bool SAT>
 __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
                                           size_t pitch, size_t image_stride, uint16_t* __restrict__ Cout,
                                           const Geom& g, int rb, int nchunks, size_t vol_stride, const CostRanges& cr,
@@ -193,6 +149,7 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
 {
     constexpr int ES = CN == 1 ? 4 : 12;  // dwords per staged entry: (p, lo, hi) per channel, padded to 16 bytes
     constexpr int EV = ES / 4;
+    constexpr int DL = COST_DL;
     constexpr int NP = DL / 2;            // packed cost registers per lane
     constexpr int SW2 = K / 2;
     constexpr int XS = 64 - (K - 1);      // output columns per strip
@@ -308,7 +265,7 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
             }
         }
     };
-    // The entry arithmetic, round 6 form (CAMD_COST_STAGE 1): everything that can be a plain 32-bit operation is one
+    // The entry arithmetic: everything that can be a plain 32-bit operation is one
     // (tools/microtests/valu_rate.hip: they issue at ~1.55 per cycle and CU, the packed / DPP / three-operand forms at
     // ~0.9).  Vertical Sobel part on the even and the odd bytes of the pixel dwords, two channels per register:
     //     sE = (s0 | s2 << 16),  sO = (s1 | junk << 16),   s = I(y-1) + 2 I(y) + I(y+1) <= 1020
@@ -316,67 +273,38 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
     // packed max / min against (1024 -+ ftz), re-based by a plain subtraction; one v_perm_b32 per channel pairs it with
     // the raw byte.  The half-pixel interval uses  min(u, (u+l)/2, (u+r)/2) = (u + min(u, l, r)) / 2  (t -> (u+t)/2 is
     // monotone; likewise max), the halving sum of two 8-bit values in 16-bit fields being one v_lerp_u8.
-    // Per staged RGB column 35 of the slower class + 20 plain instead of 55 + 11 (round 2-5 form: CAMD_COST_STAGE 0).
+    // Per staged RGB column 35 of the slower class + 20 plain (the round 2-5 form took 55 + 11).
+    static_assert(2 * CAMD_MAX_FTZERO <= 255, "v_lerp_u8 halves 8-bit fields: a clipped gradient + ftzero must fit one");
     const uint32_t st_keep = st_inside ? 0xffffffffu : 0u, st_fill = st_inside ? 0u : ftz2;
     const uint32_t clip_lo = dup16(1024u - (uint32_t)ftz), clip_hi = dup16(1024u + (uint32_t)ftz);
     auto stage_entries = [&](int buf) {
         if (stager) {  // wave-uniform up to the last staging wave
             uint32_t u[CN], lo[CN], hi[CN];
             const uint32_t a = rowA >> st_shift, b = rowB >> st_shift, c = rowC >> st_shift;
-            if (CAMD_COST_STAGE == 0) {
+            uint32_t vc[2];  // clipped gradients + ftz: (ch0 | ch2 << 16), (ch1 | junk << 16)
 #pragma unroll
-                for (int ch = 0; ch < CN; ch++) {
-                    // vertical part of the x-Sobel: s = I(y-1) + 2 I(y) + I(y+1) -- the three rows of this channel
-                    // gathered into one dword, then one dot product with (1, 2, 1)
-                    const uint32_t t = __builtin_amdgcn_perm(b, a, 0x0c0c0400u + 0x00000101u * ch);      // (a.ch, b.ch, 0, 0)
-                    const uint32_t t3 = __builtin_amdgcn_perm(c, t, 0x0c040100u + 0x00010000u * ch);     // (a.ch, b.ch, c.ch, 0)
-                    const uint32_t sv = __builtin_amdgcn_udot4(t3, 0x00010201u, 0u, false);
-                    // gradient = s(x+1) - s(x-1), clipped to [-ftz, ftz], + ftz;  p = gradient | raw << 16
-                    // (the subtrahend passes through an empty asm so that the DPP move is NOT folded into the subtraction:
-                    // the folded form, v_subrev_u32_dpp, measured wrong on gfx950 -- it returned shr(src1) - src0)
-                    uint32_t sl = dpp_perm<DPP_WAVE_SHR1>(sv);
-                    asm volatile("" : "+v"(sl));
-                    const int gq = (int)dpp_perm<DPP_WAVE_SHL1>(sv) - (int)sl;
-                    const uint32_t gc = (uint32_t)(min(max(gq, -ftz), ftz) + ftz);
-                    const uint32_t raw = (b >> (8 * ch)) & 0xffu;
-                    u[ch] = st_inside ? (gc | (raw << 16)) : ftz2;
-                }
+            for (int eo = 0; eo < (CN == 1 ? 1 : 2); eo++) {
+                const uint32_t M = CN == 1 ? 0xffu : 0x00ff00ffu;
+                const uint32_t ea = (eo ? a >> 8 : a) & M, eb = (eo ? b >> 8 : b) & M, ec = (eo ? c >> 8 : c) & M;
+                const uint32_t sv = ea + ec + eb + eb;
+                // (the subtrahend passes through an empty asm so that its DPP move is NOT folded into the
+                // subtraction: the folded form, v_subrev_u32_dpp, measured wrong on gfx950)
+                uint32_t sl = dpp_perm<DPP_WAVE_SHR1>(sv);
+                asm volatile("" : "+v"(sl));
+                const uint32_t gq = dpp_perm<DPP_WAVE_SHL1>(sv) - sl + 0x04000400u;  // 1024 + gradient per half
+                vc[eo] = pk_min_u16(pk_max_u16(gq, clip_lo), clip_hi) - clip_lo;
+            }
 #pragma unroll
-                for (int ch = 0; ch < CN; ch++) {
-                    // half-pixel interval: columns outside the image carry ftz2 like the border columns, so the
-                    // "no neighbour at the image edge" rule (use p itself) needs no special case
-                    const uint32_t l = dpp_perm<DPP_WAVE_SHR1>(u[ch]), r = dpp_perm<DPP_WAVE_SHL1>(u[ch]);
-                    const uint32_t ul = pk_lshr_u16(pk_add_u16(u[ch], l), 0x00010001u);
-                    const uint32_t ur = pk_lshr_u16(pk_add_u16(u[ch], r), 0x00010001u);
-                    lo[ch] = pk_min_u16(pk_min_u16(ul, ur), u[ch]);
-                    hi[ch] = pk_max_u16(pk_max_u16(ul, ur), u[ch]);
-                }
-            } else {
-                uint32_t vc[2];  // clipped gradients + ftz: (ch0 | ch2 << 16), (ch1 | junk << 16)
+            for (int ch = 0; ch < CN; ch++) {
+                // (gradient of the channel | its raw byte << 16); columns 0 and W-1 (and beyond) hold tab[0]
+                const uint32_t sel = ch == 0 ? 0x0c040100u : (ch == 1 ? 0x0c050100u : 0x0c060302u);
+                u[ch] = (__builtin_amdgcn_perm(b, vc[ch & 1], sel) & st_keep) | st_fill;
+            }
 #pragma unroll
-                for (int eo = 0; eo < (CN == 1 ? 1 : 2); eo++) {
-                    const uint32_t M = CN == 1 ? 0xffu : 0x00ff00ffu;
-                    const uint32_t ea = (eo ? a >> 8 : a) & M, eb = (eo ? b >> 8 : b) & M, ec = (eo ? c >> 8 : c) & M;
-                    const uint32_t sv = ea + ec + eb + eb;
-                    // (the subtrahend passes through an empty asm so that its DPP move is NOT folded into the
-                    // subtraction: the folded form, v_subrev_u32_dpp, measured wrong on gfx950)
-                    uint32_t sl = dpp_perm<DPP_WAVE_SHR1>(sv);
-                    asm volatile("" : "+v"(sl));
-                    const uint32_t gq = dpp_perm<DPP_WAVE_SHL1>(sv) - sl + 0x04000400u;  // 1024 + gradient per half
-                    vc[eo] = pk_min_u16(pk_max_u16(gq, clip_lo), clip_hi) - clip_lo;
-                }
-#pragma unroll
-                for (int ch = 0; ch < CN; ch++) {
-                    // (gradient of the channel | its raw byte << 16); columns 0 and W-1 (and beyond) hold tab[0]
-                    const uint32_t sel = ch == 0 ? 0x0c040100u : (ch == 1 ? 0x0c050100u : 0x0c060302u);
-                    u[ch] = (__builtin_amdgcn_perm(b, vc[ch & 1], sel) & st_keep) | st_fill;
-                }
-#pragma unroll
-                for (int ch = 0; ch < CN; ch++) {
-                    const uint32_t l = dpp_perm<DPP_WAVE_SHR1>(u[ch]), r = dpp_perm<DPP_WAVE_SHL1>(u[ch]);
-                    lo[ch] = __builtin_amdgcn_lerp(u[ch], pk_min_u16(pk_min_u16(l, r), u[ch]), 0u);
-                    hi[ch] = __builtin_amdgcn_lerp(u[ch], pk_max_u16(pk_max_u16(l, r), u[ch]), 0u);
-                }
+            for (int ch = 0; ch < CN; ch++) {
+                const uint32_t l = dpp_perm<DPP_WAVE_SHR1>(u[ch]), r = dpp_perm<DPP_WAVE_SHL1>(u[ch]);
+                lo[ch] = __builtin_amdgcn_lerp(u[ch], pk_min_u16(pk_min_u16(l, r), u[ch]), 0u);
+                hi[ch] = __builtin_amdgcn_lerp(u[ch], pk_max_u16(pk_max_u16(l, r), u[ch]), 0u);
             }
             if (st_store) {
                 u32x4_t* d4 = reinterpret_cast<u32x4_t*>(st_dst + buf * esz);
@@ -415,14 +343,12 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
     uint16_t* const vol = Cout + (size_t)vpair * vol_stride;                 // (uniform)
     const uint32_t out_off = (uint32_t)((writer ? xo : 0) * g.Dp + d0);     // element offset of this lane inside a row of C
 
-    const int win_back = ((lane - K) & 63) << 2;
-    const bool win_live = lane >= K;
     const uint32_t p2 = dup16((uint32_t)g.P2);
     // the output tile (see CAMD_COST_TSTORE): [2][64 columns][NW + 1] quads behind the entry buffers; this lane writes
     // quad (lane, w) and later stores the quad (column tpx, piece tpc) -- NW consecutive lanes = one column's NW pieces
     // (uniform; the launch sized the LDS the same way.  Not for a disparity block with padding: its all-padding waves have
     // left, and with them the columns they would flush)
-    const bool tstore = cost_tstore(CN) && DL == COST_DL && 64 % NW == 0 && db + DW <= g.D;
+    const bool tstore = cost_tstore(CN) && 64 % NW == 0 && db + DW <= g.D;
     const int TP = NW + 1;
     uint4* const Tbuf = Ebuf + 2 * esz;
     const int tpx = w * (64 / NW) + lane / NW, tpc = lane % NW;
@@ -490,20 +416,11 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
                     for (int c = 0; c < CN; c++) {
                         // c0 = max(0, u - v1, v0 - u), c1 = max(0, v - u1, u0 - v): at most one term of each pair
                         // is non-zero, so OR of the saturating differences is their max
-                        if (CAMD_COST_TAIL == 0) {
-                            const uint32_t a = pk_subsat_u16(U[c], V1[c]) | pk_subsat_u16(V0[c], U[c]);
-                            const uint32_t b = pk_subsat_u16(V[c], U1[c]) | pk_subsat_u16(U0[c], V[c]);
-                            uint32_t m = pk_min_u16(a, b);
-                            m = pk_lshr_u16(m, 0x00020000u);  // raw plane: cost >> 2
-                            a32 = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, m),
-                                                         __builtin_bit_cast(u16x2_t, 0x00010001u), a32, false);
-                        } else {
-                            // the raw half rounded down to a multiple of 4 (min of the rounded = the rounded min); the
-                            // mask is the third input of the v_bitop3_b32 that ORs the differences
-                            const uint32_t a = (pk_subsat_u16(U[c], V1[c]) | pk_subsat_u16(V0[c], U[c])) & rawmask;
-                            const uint32_t b = (pk_subsat_u16(V[c], U1[c]) | pk_subsat_u16(U0[c], V[c])) & rawmask;
-                            a32 += pk_min_u16(a, b);  // gradient sum | raw sum << 16, plain add
-                        }
+                        // the raw half rounded down to a multiple of 4 (min of the rounded = the rounded min); the
+                        // mask is the third input of the v_bitop3_b32 that ORs the differences
+                        const uint32_t a = (pk_subsat_u16(U[c], V1[c]) | pk_subsat_u16(V0[c], U[c])) & rawmask;
+                        const uint32_t b = (pk_subsat_u16(V[c], U1[c]) | pk_subsat_u16(U0[c], V[c])) & rawmask;
+                        a32 += pk_min_u16(a, b);  // gradient sum | raw sum << 16, plain add
                     }
                     cost[j] = a32;
                 }
@@ -511,19 +428,14 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
                 uint32_t pp[NP];
 #pragma unroll
                 for (int k = 0; k < NP; k++) {
-                    if (CAMD_COST_TAIL == 0) {
-                        pp[k] = (cost[2 * k] | (cost[2 * k + 1] << 16)) & keep[k];
-                    } else {
-                        const uint32_t gq = __builtin_amdgcn_perm(cost[2 * k + 1], cost[2 * k], 0x05040100u);  // gradient sums
-                        const uint32_t rq = __builtin_amdgcn_perm(cost[2 * k + 1], cost[2 * k], 0x07060302u);  // raw sums (x 4)
-                        pp[k] = (gq + (rq >> 2)) & keep[k];  // bits 16, 17 of rq are zero: the plain shift is clean
-                    }
+                    const uint32_t gq = __builtin_amdgcn_perm(cost[2 * k + 1], cost[2 * k], 0x05040100u);  // gradient sums
+                    const uint32_t rq = __builtin_amdgcn_perm(cost[2 * k + 1], cost[2 * k], 0x07060302u);  // raw sums (x 4)
+                    pp[k] = (gq + (rq >> 2)) & keep[k];  // bits 16, 17 of rq are zero: the plain shift is clean
                 }
                 // horizontal window over lanes, vertical running sum
 #pragma unroll
                 for (int k = 0; k < NP; k++) {
-                    const uint32_t T = (CAMD_COST_SCAN_WINDOW && K >= 9) ? lane_window_sum_scan(pp[k], win_back, win_live)
-                                                                         : lane_window_sum<K>(pp[k]);
+                    const uint32_t T = lane_window_sum<K>(pp[k]);
                     const uint32_t old = ring[u][k];
                     ring[u][k] = T;
                     if (SAT) {
@@ -544,12 +456,7 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
                     uint16_t* const orow = vol + (size_t)y * W1 * g.Dp;
 #pragma unroll
                     for (int q = 0; q < NP / 4; q++) {
-                        if (tstore) {
-                        } else if (CAMD_COST_NT)
-                            __builtin_nontemporal_store(u32x4_t{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]},
-                                                        reinterpret_cast<u32x4_t*>(orow + out_off) + q);
-                        else
-                            store_c(orow, out_off + 8 * q, u32x4_t{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]});
+                        if (!tstore) store_c(orow, out_off + 8 * q, u32x4_t{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]});
                         if (SAT) neg_min = pk_min_i16(pk_min_i16(neg_min, pk_min_i16(acc[4 * q], acc[4 * q + 1])),
                                                       pk_min_i16(acc[4 * q + 2], acc[4 * q + 3]));
                         if (!SAT && ovf_thresh >= 0)  // (uniform)
@@ -574,14 +481,14 @@ __device__ __forceinline__ void cost_body(const uint8_t* __restrict__ left, cons
     if (SAT && neg && min((int)(int16_t)(neg_min & 0xffffu), (int)(int16_t)(neg_min >> 16)) < g.P2) atomicOr(neg + vpair, 1u);
 }
 
-template <int CN, int K, bool SAT, int DL = COST_DL>
-__global__ __launch_bounds__(1024, cost_min_waves(K, DL)) void k_cost(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+template <int CN, int K, bool SAT>
+__global__ __launch_bounds__(1024, cost_min_waves(K)) void k_cost(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
                                                size_t pitch, size_t image_stride, uint16_t* __restrict__ Cout,
                                                Geom g, int rb, int nchunks, size_t vol_stride, CostRanges cr,
                                                uint32_t* __restrict__ ovf, int ovf_thresh, uint32_t* __restrict__ neg)
 {
-    cost_body<CN, K, SAT, DL>(left, right, pitch, image_stride, Cout, g, rb, nchunks, vol_stride, cr, ovf, ovf_thresh, neg,
-                              (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+    cost_body<CN, K, SAT>(left, right, pitch, image_stride, Cout, g, rb, nchunks, vol_stride, cr, ovf, ovf_thresh, neg,
+                          (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // The same work handed out by a ticket to a FIXED number of resident workgroups (grid = workgroups per CU x 256): a
@@ -590,8 +497,8 @@ __global__ __launch_bounds__(1024, cost_min_waves(K, DL)) void k_cost(const uint
 // ordinary launches on two streams only overlap in their tails: the dispatcher drains the older grid first --
 // profiles/r06_corun.json.)  Items are numbered strip-fastest like k_cost's grid.  Only for launches in which no wave
 // leaves early (numDisparities a multiple of the workgroup's disparity block) and no per-volume early exit applies.
-template <int CN, int K, int DL = COST_DL>
-__global__ __launch_bounds__(1024, cost_min_waves(K, DL)) void k_cost_persist(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+template <int CN, int K>
+__global__ __launch_bounds__(1024, cost_min_waves(K)) void k_cost_persist(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
                                                size_t pitch, size_t image_stride, uint16_t* __restrict__ Cout,
                                                Geom g, int rb, int nchunks, size_t vol_stride, CostRanges cr,
                                                uint32_t* __restrict__ ticket, int nx, int ny, int nitems)
@@ -604,8 +511,8 @@ __global__ __launch_bounds__(1024, cost_min_waves(K, DL)) void k_cost_persist(co
         __syncthreads();
         if (item >= nitems) break;
         const int bx = item % nx, r = item / nx;
-        cost_body<CN, K, false, DL>(left, right, pitch, image_stride, Cout, g, rb, nchunks, vol_stride, cr, nullptr, -1, nullptr,
-                                    bx, r % ny, r / ny);
+        cost_body<CN, K, false>(left, right, pitch, image_stride, Cout, g, rb, nchunks, vol_stride, cr, nullptr, -1, nullptr,
+                                bx, r % ny, r / ny);
     }
 }
 

@@ -95,6 +95,137 @@ def test_argument_validation_without_gpu():
     assert lib.camd_sgbm_workspace_bytes(ctypes.byref(small), 64, 64, 1, 1) > 0
 
 
+# (mode, channels, numDisparities, width, height, max_batch, speckleWindowSize, blockSize, P2, minDisparity) -> bytes, with
+# P1 = P2 // 4 and speckleRange = 2.  Recorded from the library before the workspace got its one description
+# (plan_workspace in csrc/sgbm.hip): StereoSGBM's handle cache evicts by this figure, so it may not move by a byte.
+# The table reaches every term of the plan: all modes, gray / RGB, every lane shape (D 16 ... 512, with and without a
+# band instantiation), VGA / 1080p / 4K, the AUTO capacity of the per-direction volumes at max_batch 1 ... 64, the
+# speckle scratch, the exact path's volumes (blockSize 11 RGB can overflow int16, blockSize 5 cannot), W1 <= 0 (also
+# for MODE_SGBM_3WAY, where the report counts stripe images the handle never allocates) and the refused shapes.
+WORKSPACE_BYTES = [
+    ((0, 1, 16, 640, 480, 1, 0, 5, 800, 0), 69760228),
+    ((0, 3, 48, 1920, 1080, 1, 0, 5, 800, 0), 1843071136),
+    ((0, 1, 64, 3840, 2160, 4, 0, 5, 800, 0), 24512925544),
+    ((0, 3, 128, 640, 480, 4, 100, 5, 800, 0), 1810179112),
+    ((0, 1, 218, 1920, 1080, 16, 100, 5, 800, 0), 40883704264),
+    ((0, 3, 256, 3840, 2160, 16, 100, 5, 800, 0), 155720159368),
+    ((0, 1, 320, 640, 480, 64, 0, 5, 800, 0), 19857408520),
+    ((0, 3, 512, 1920, 1080, 64, 0, 5, 800, 0), 207364424200),
+    ((1, 1, 16, 3840, 2160, 1, 0, 5, 800, 0), 2713796456),
+    ((1, 3, 48, 640, 480, 1, 100, 5, 800, 0), 370772548),
+    ((1, 1, 64, 1920, 1080, 4, 100, 5, 800, 0), 10455077160),
+    ((1, 3, 128, 3840, 2160, 4, 100, 5, 800, 0), 67121916712),
+    ((1, 1, 218, 640, 480, 16, 0, 5, 800, 0), 8939677192),
+    ((1, 3, 256, 1920, 1080, 16, 0, 5, 800, 0), 82848216712),
+    ((1, 1, 320, 3840, 2160, 64, 0, 5, 800, 0), 795200717320),
+    ((1, 3, 512, 640, 480, 64, 100, 5, 800, 0), 12276204040),
+    ((2, 1, 16, 1920, 1080, 1, 100, 5, 800, 0), 187105032),
+    ((2, 3, 48, 3840, 2160, 1, 100, 5, 800, 0), 2541240088),
+    ((2, 1, 64, 640, 480, 4, 0, 5, 800, 0), 343088008),
+    ((2, 3, 128, 1920, 1080, 4, 0, 5, 800, 0), 4741682312),
+    ((2, 1, 218, 3840, 2160, 16, 0, 5, 800, 0), 151066022920),
+    ((2, 3, 256, 640, 480, 16, 100, 5, 800, 0), 3681516040),
+    ((2, 1, 320, 1920, 1080, 64, 100, 5, 800, 0), 190365698056),
+    ((2, 3, 512, 3840, 2160, 64, 100, 5, 800, 0), 1048145954824),
+    ((3, 1, 16, 640, 480, 1, 0, 5, 800, 0), 60175588),
+    ((3, 3, 48, 1920, 1080, 1, 0, 5, 800, 0), 1584285856),
+    ((3, 1, 64, 3840, 2160, 4, 0, 5, 800, 0), 25556914024),
+    ((3, 3, 128, 640, 480, 4, 100, 5, 800, 0), 1558520872),
+    ((3, 1, 218, 1920, 1080, 16, 100, 5, 800, 0), 51589148104),
+    ((3, 3, 256, 3840, 2160, 16, 100, 5, 800, 0), 183465480328),
+    ((3, 1, 320, 640, 480, 64, 0, 5, 800, 0), 18913690120),
+    ((3, 3, 512, 1920, 1080, 64, 0, 5, 800, 0), 205807288840),
+    ((0, 1, 16, 640, 480, 64, 100, 5, 800, 0), 1938241288),
+    ((0, 1, 64, 3840, 2160, 1, 0, 5, 800, 0), 7433216992),
+    ((0, 3, 128, 640, 480, 4, 0, 5, 800, 0), 1800348712),
+    ((0, 1, 218, 1920, 1080, 4, 100, 5, 800, 0), 19485252472),
+    ((0, 1, 320, 640, 480, 16, 100, 5, 800, 0), 8542617736),
+    ((1, 1, 16, 3840, 2160, 64, 0, 5, 800, 0), 55269906440),
+    ((1, 3, 48, 640, 480, 1, 0, 5, 800, 0), 368314948),
+    ((1, 1, 64, 1920, 1080, 1, 100, 5, 800, 0), 2613769296),
+    ((1, 1, 218, 640, 480, 4, 100, 5, 800, 0), 3696699784),
+    ((1, 1, 320, 3840, 2160, 16, 0, 5, 800, 0), 233835724936),
+    ((1, 3, 512, 640, 480, 64, 0, 5, 800, 0), 12118917640),
+    ((2, 1, 16, 1920, 1080, 64, 100, 5, 800, 0), 11974721544),
+    ((2, 1, 64, 640, 480, 1, 100, 5, 800, 0), 88229608),
+    ((2, 1, 218, 3840, 2160, 4, 0, 5, 800, 0), 37766505736),
+    ((2, 3, 256, 640, 480, 16, 0, 5, 800, 0), 3642194440),
+    ((2, 1, 320, 1920, 1080, 16, 100, 5, 800, 0), 47591424520),
+    ((3, 1, 16, 640, 480, 64, 100, 5, 800, 0), 1861564168),
+    ((3, 1, 64, 3840, 2160, 1, 0, 5, 800, 0), 6389228512),
+    ((3, 3, 128, 640, 480, 4, 0, 5, 800, 0), 1548690472),
+    ((3, 1, 218, 1920, 1080, 4, 100, 5, 800, 0), 20308748152),
+    ((3, 1, 320, 640, 480, 16, 100, 5, 800, 0), 7598899336),
+    ((0, 1, 128, 640, 480, 1, 0, 5, 800, 0), 450087184),
+    ((0, 1, 128, 640, 480, 4, 0, 5, 800, 0), 1800348712),
+    ((0, 1, 128, 640, 480, 16, 0, 5, 800, 0), 4684812424),
+    ((0, 1, 128, 640, 480, 64, 0, 5, 800, 0), 11189502472),
+    ((0, 1, 128, 1920, 1080, 1, 0, 5, 800, 0), 3539563600),
+    ((0, 1, 128, 1920, 1080, 4, 0, 5, 800, 0), 11680993576),
+    ((0, 1, 128, 1920, 1080, 16, 0, 5, 800, 0), 24428627080),
+    ((0, 1, 128, 1920, 1080, 64, 0, 5, 800, 0), 75419161096),
+    ((0, 1, 128, 3840, 2160, 1, 0, 5, 800, 0), 14661536464),
+    ((0, 1, 128, 3840, 2160, 4, 0, 5, 800, 0), 27857333032),
+    ((0, 1, 128, 3840, 2160, 16, 0, 5, 800, 0), 80640519304),
+    ((0, 1, 128, 3840, 2160, 64, 0, 5, 800, 0), 291773264392),
+    ((1, 1, 128, 640, 480, 1, 0, 5, 800, 0), 638830864),
+    ((1, 1, 128, 640, 480, 4, 0, 5, 800, 0), 2555323432),
+    ((1, 1, 128, 640, 480, 16, 0, 5, 800, 0), 6194761864),
+    ((1, 1, 128, 640, 480, 64, 0, 5, 800, 0), 12699451912),
+    ((1, 1, 128, 1920, 1080, 1, 0, 5, 800, 0), 5025920080),
+    ((1, 1, 128, 1920, 1080, 4, 0, 5, 800, 0), 20103680296),
+    ((1, 1, 128, 1920, 1080, 16, 0, 5, 800, 0), 44742165640),
+    ((1, 1, 128, 1920, 1080, 64, 0, 5, 800, 0), 95732699656),
+    ((1, 1, 128, 3840, 2160, 1, 0, 5, 800, 0), 20819299024),
+    ((1, 1, 128, 3840, 2160, 4, 0, 5, 800, 0), 66856495912),
+    ((1, 1, 128, 3840, 2160, 16, 0, 5, 800, 0), 119639682184),
+    ((1, 1, 128, 3840, 2160, 64, 0, 5, 800, 0), 330772427272),
+    ((0, 3, 16, 640, 480, 1, 0, 3, 72, 0), 69760228),
+    ((0, 3, 16, 640, 480, 4, 0, 3, 72, 0), 279040888),
+    ((0, 3, 16, 640, 480, 16, 0, 3, 72, 0), 732777928),
+    ((0, 3, 16, 640, 480, 64, 0, 3, 72, 0), 1780954888),
+    ((0, 3, 64, 640, 480, 1, 0, 3, 72, 0), 252258592),
+    ((0, 3, 64, 640, 480, 4, 0, 3, 72, 0), 1009034344),
+    ((0, 3, 64, 640, 480, 16, 0, 3, 72, 0), 2620559752),
+    ((0, 3, 64, 640, 480, 64, 0, 3, 72, 0), 6235506184),
+    ((0, 3, 128, 1000, 562, 4, 0, 11, 21600, 0), 4842771928),
+    ((0, 3, 128, 1000, 562, 4, 0, 5, 2400, 0), 3588208088),
+    ((1, 3, 128, 1000, 562, 4, 0, 11, 21600, 0), 7100986840),
+    ((1, 3, 128, 1000, 562, 4, 0, 5, 2400, 0), 5093684696),
+    ((2, 3, 128, 1000, 562, 4, 0, 11, 21600, 0), 1465101576),
+    ((2, 3, 128, 1000, 562, 4, 0, 5, 2400, 0), 1226307592),
+    ((3, 3, 128, 1000, 562, 4, 0, 11, 21600, 0), 4090033624),
+    ((3, 3, 128, 1000, 562, 4, 0, 5, 2400, 0), 3086382552),
+    ((0, 1, 64, 640, 480, 1, 50, 15, 7200, 0), 254716192),
+    ((0, 1, 64, 640, 480, 1, 50, 9, 2592, 0), 254716192),
+    ((0, 1, 64, 640, 480, 2, 0, 5, 800, -16), 504517176),
+    ((1, 3, 64, 640, 480, 2, 7, 5, 800, 24), 692104944),
+    ((0, 1, 128, 100, 80, 1, 0, 5, 800, 0), 16144),
+    ((2, 3, 128, 128, 80, 3, 10, 5, 800, 0), 384104),
+    ((0, 1, 64, 640, 480, 1, 0, 5, 800, -700), 614416),
+    ((0, 2, 128, 1920, 1080, 1, 0, 5, 800, 0), 0),
+    ((0, 1, 0, 64, 64, 1, 0, 5, 800, 0), 0),
+    ((5, 1, 16, 64, 64, 1, 0, 5, 800, 0), 0),
+    ((2, 1, 16, 64, 12, 1, 0, 11, 0, 0), 0),
+    ((2, 1, 16, 64, 64, 1, 0, 11, 0, 0), 373848),
+    ((0, 1, 528, 1920, 1080, 1, 0, 5, 800, 0), 0),
+    ((0, 1, 64, 640, 480, 1, 0, 17, 800, 0), 0),
+    ((0, 1, 64, 66, 48, 1, 0, 5, 800, 0), 0),
+    ((0, 1, 64, 640, 480, 0, 0, 5, 800, 0), 0),
+]
+
+
+def test_workspace_bytes_are_pinned():
+    import ctypes
+    lib = _native.lib()
+    assert len(WORKSPACE_BYTES) > 100 and len({c for c, _ in WORKSPACE_BYTES}) == len(WORKSPACE_BYTES)
+    for (mode, cn, D, W, H, max_batch, speckle, block, P2, minD), want in WORKSPACE_BYTES:
+        p = _native.SgbmParams(minDisparity=minD, numDisparities=D, blockSize=block, P1=P2 // 4, P2=P2,
+                               speckleWindowSize=speckle, speckleRange=2, mode=mode)
+        got = lib.camd_sgbm_workspace_bytes(ctypes.byref(p), W, H, cn, max_batch)
+        assert got == want, ((mode, cn, D, W, H, max_batch, speckle, block, P2, minD), got, want)
+
+
 def test_interpolation_tables_three_independent_builders():
     """The fixed-point Lanczos-4 / bilinear tables of the product (csrc/remap.hip), of the oracle (oracle/remap_ref.c)
     and of an independently written NumPy model (tests/np_interp_tables.py) agree bit for bit -- for both settings of
