@@ -7,16 +7,16 @@
 //   build_set2ds_by_flowds    xys_abs[mask], (flow_abs + xys_abs)[mask]                       -> masked compaction
 //   flow_abs_to_normal / flow_normal_to_abs
 // Integer atomics only (min / add commute, so the grids do not depend on the order they are served in); every float sum
-// is reduced in a fixed order.  Compactions are count -> exclusive scan -> emit; where the header says so the scan is the
-// caller's.  Products and sums are individually rounded (-ffp-contract=off).
+// is reduced in a fixed order.  Compactions and block sums are the pieces of compact.hpp; where the C header says so the
+// scan is the caller's.  Products and sums are individually rounded (-ffp-contract=off).
 #include "common.hpp"
+#include "compact.hpp"
 #include "triangulate.hpp"
 
 #include <cmath>
 
 namespace camd {
 
-constexpr int EP_MAX_BLOCKS = 1024;            // partials of a fixed-order sum; the final block adds four per thread
 constexpr uint32_t EP_EMPTY = 0xffffffffu;
 constexpr unsigned long long EP_MAX_CELLS = 1ull << 28;
 
@@ -38,13 +38,6 @@ __device__ __forceinline__ bool ep_cell(const T* __restrict__ uv, size_t i, int 
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_ep_fill_u32(uint32_t* __restrict__ p, size_t n, uint32_t v, unsigned long long* zero)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-    if (i == 0 && zero) *zero = 0ull;
-}
-
 // FIRST: grid[cell] = min(row index) -- np.unique(return_index=True) reports the first occurrence, the smallest index.
 // !FIRST: grid[cell] += 1 -- np.unique(return_counts=True)[inverse].
 template <typename T, bool FIRST>
@@ -61,57 +54,24 @@ __global__ __launch_bounds__(256) void k_ep_cells(const T* __restrict__ uv, size
 
 // ---- the intersection --------------------------------------------------------------------------------------------------
 // np.unique(axis=0) sorts the (u, v) cell rows lexicographically as signed integers and np.intersect1d keeps that order:
-// ascending u cell, then v cell -- the linear order of the u-major grid.  One workgroup per u column.
-__global__ __launch_bounds__(256) void k_ep_isect_count(const uint32_t* __restrict__ f1, const uint32_t* __restrict__ f2, int ch,
-                                                        uint32_t* __restrict__ colcount)
-{
-    __shared__ uint32_t part[4];
-    const size_t base = (size_t)blockIdx.x * ch;
-    uint32_t c = 0;
-    for (int v = threadIdx.x; v < ch; v += 256) c += (f1[base + v] != EP_EMPTY && f2[base + v] != EP_EMPTY) ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) colcount[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-
-// position of this thread's element among the `on` elements of the block's current 256, after `run`
-__device__ __forceinline__ unsigned long long ep_slot(bool on, unsigned long long run, uint32_t* wcnt)
-{
-    const unsigned long long bal = __ballot(on);
-    const uint32_t below = __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
-    if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    unsigned long long pos = run + below;
-    for (int k = 0; k < (int)(threadIdx.x >> 6); k++) pos += wcnt[k];
-    return pos;
-}
-
-__global__ __launch_bounds__(256) void k_ep_isect_emit(const uint32_t* __restrict__ f1, const uint32_t* __restrict__ f2, int ch,
-                                                       const long long* __restrict__ start, long long* __restrict__ idx1,
-                                                       long long* __restrict__ idx2, size_t capacity,
-                                                       unsigned long long* __restrict__ count)
-{
-    __shared__ uint32_t wcnt[4];
-    __shared__ unsigned long long run;
-    const size_t base = (size_t)blockIdx.x * ch;
-    if (threadIdx.x == 0) {
-        run = (unsigned long long)start[blockIdx.x];
-        if (blockIdx.x == 0) *count = (unsigned long long)start[gridDim.x];
+// ascending u cell, then v cell -- the linear order of the u-major grid.  A compaction (compact.hpp) whose rows are the u
+// columns.
+struct EpIsect {
+    const uint32_t *f1, *f2;
+    int ch;
+    long long *idx1, *idx2;
+    __device__ __forceinline__ bool on(int v, int cu) const
+    {
+        const size_t c = (size_t)cu * ch + v;
+        return f1[c] != EP_EMPTY && f2[c] != EP_EMPTY;
     }
-    __syncthreads();
-    for (int v0 = 0; v0 < ch; v0 += 256) {
-        const int v = v0 + threadIdx.x;
-        uint32_t a = EP_EMPTY, b = EP_EMPTY;
-        if (v < ch) { a = f1[base + v]; b = f2[base + v]; }
-        const bool on = a != EP_EMPTY && b != EP_EMPTY;
-        const unsigned long long pos = ep_slot(on, run, wcnt);
-        if (on && pos < capacity) { idx1[pos] = (long long)a; idx2[pos] = (long long)b; }
-        __syncthreads();
-        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+    __device__ __forceinline__ void emit(int v, int cu, unsigned long long pos) const
+    {
+        const size_t c = (size_t)cu * ch + v;
+        idx1[pos] = (long long)f1[c];
+        idx2[pos] = (long long)f2[c];
     }
-}
+};
 
 // ---- the overlap filter ------------------------------------------------------------------------------------------------
 // keep[i] = both pixels of match i are hit once; blockcount[b] = how many of rows 256 b .. 256 b + 255 are kept
@@ -129,10 +89,8 @@ __global__ __launch_bounds__(256) void k_ep_overlap_keep(const T* __restrict__ u
         on = ep_cell(uv1, i, stride, (T)1, w, &c1) && ep_cell(uv2, i, stride, (T)1, w, &c2) && cnt1[c1] <= 1u && cnt2[c2] <= 1u;
         keep[i] = on ? 1 : 0;
     }
-    const unsigned long long bal = __ballot(on);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) blockcount[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    const uint32_t c = block_count(on, part);
+    if (threadIdx.x == 0) blockcount[blockIdx.x] = c;
 }
 
 // uvs[mask]: the kept rows in their own order
@@ -146,7 +104,7 @@ __global__ __launch_bounds__(256) void k_ep_overlap_emit(const T* __restrict__ u
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) *count = (unsigned long long)start[gridDim.x];
     const bool on = i < n && keep[i] != 0;
-    const unsigned long long pos = ep_slot(on, (unsigned long long)start[blockIdx.x], wcnt);
+    const unsigned long long pos = block_slot(on, (unsigned long long)start[blockIdx.x], wcnt);
     if (on && pos < capacity) {
         out1[pos * 2] = uv1[i * stride]; out1[pos * 2 + 1] = uv1[i * stride + 1];
         out2[pos * 2] = uv2[i * stride]; out2[pos * 2 + 1] = uv2[i * stride + 1];
@@ -155,24 +113,9 @@ __global__ __launch_bounds__(256) void k_ep_overlap_emit(const T* __restrict__ u
 
 // ---- fixed-order sums --------------------------------------------------------------------------------------------------
 // Q running sums per thread; thread t of block g adds rows g*256+t, +G*256, ... in that order (at most
-// m = ceil(n / (256 G)) terms); the block adds its 256 threads by a binary tree (8 levels) and stores Q partials;
+// m = ceil(n / (256 G)) terms); block_tree (compact.hpp) adds the block's 256 threads (8 levels) and stores Q partials;
 // k_ep_final: thread t adds partials t, t+256, t+512, t+768 as (p0 + p1) + (p2 + p3) (2 levels; absent ones are 0), then
 // the same 8-level tree: d = 18 levels above the serial part, whatever n is.
-template <int Q>
-__device__ __forceinline__ void ep_block_tree(const double* s, double* sh, double* __restrict__ dst)
-{
-    for (int q = 0; q < Q; q++) {
-        sh[threadIdx.x] = s[q];
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) dst[q] = sh[0];
-        __syncthreads();
-    }
-}
-
 template <int Q>
 __global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
 {
@@ -186,7 +129,7 @@ __global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ par
         }
         s[q] = (p[0] + p[1]) + (p[2] + p[3]);
     }
-    ep_block_tree<Q>(s, sh, sums);
+    block_tree<Q>(s, sh, sums);
 }
 
 struct EpPoses {
@@ -209,7 +152,7 @@ __global__ __launch_bounds__(256) void k_ep_pose_partials(const double* __restri
             s[c * 2 + 1] += z2;
         }
     }
-    ep_block_tree<8>(s, sh, partials + (size_t)blockIdx.x * 8);
+    block_tree<8>(s, sh, partials + (size_t)blockIdx.x * 8);
 }
 
 // s[0] = sum of z[i] (idx == NULL) or of z[idx[i]]; s[1] = how many idx[i] lie outside [0, z_len) (they add nothing)
@@ -224,79 +167,25 @@ __global__ __launch_bounds__(256) void k_ep_vector_partials(const double* __rest
         if (j >= 0 && (unsigned long long)j < z_len) s[0] += z[j];
         else s[1] += 1.0;
     }
-    ep_block_tree<2>(s, sh, partials + (size_t)blockIdx.x * 2);
+    block_tree<2>(s, sh, partials + (size_t)blockIdx.x * 2);
 }
 
 // ---- flow ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ep_mask_count(const uint8_t* __restrict__ mask, int w, uint32_t* __restrict__ rowcount)
-{
-    __shared__ uint32_t part[4];
-    const int y = blockIdx.x;
-    uint32_t c = 0;
-    for (int x = threadIdx.x; x < w; x += 256) c += mask[(size_t)y * w + x] ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rowcount[y] = part[0] + part[1] + part[2] + part[3];
-}
-
-// exclusive scan of the row counts (one workgroup; rows <= a few thousand)
-__global__ __launch_bounds__(256) void k_ep_mask_scan(const uint32_t* __restrict__ rowcount, int n,
-                                                      unsigned long long* __restrict__ rowoff,
-                                                      unsigned long long* __restrict__ total)
-{
-    __shared__ unsigned long long carry;
-    __shared__ unsigned long long wsum[4];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + threadIdx.x;
-        unsigned long long v = i < n ? rowcount[i] : 0ull, incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            unsigned long long t = __shfl_up(incl, o);
-            if ((threadIdx.x & 63) >= o) incl += t;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) before += wsum[k];
-        if (i < n) rowoff[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
 // xys_abs = (np.mgrid[:h, :w] + 0.5 - 1e-8)[::-1]: the float64 sum (x + 0.5) - 1e-8; uvs_to = float64(flow) + xys_abs
 template <typename F>
-__global__ __launch_bounds__(256) void k_ep_flow_emit(const F* __restrict__ flow, const uint8_t* __restrict__ mask, int w,
-                                                      const unsigned long long* __restrict__ rowoff, double* __restrict__ from,
-                                                      double* __restrict__ to, size_t capacity)
-{
-    __shared__ uint32_t wcnt[4];
-    __shared__ unsigned long long run;
-    const int y = blockIdx.x;
-    if (threadIdx.x == 0) run = rowoff[y];
-    __syncthreads();
-    const double fy = ((double)y + 0.5) - 1e-8;
-    for (int base = 0; base < w; base += 256) {
-        const int x = base + threadIdx.x;
-        const bool on = x < w && mask[(size_t)y * w + x] != 0;
-        const unsigned long long pos = ep_slot(on, run, wcnt);
-        if (on && pos < capacity) {
-            const double fx = ((double)x + 0.5) - 1e-8;
-            const size_t p = ((size_t)y * w + x) * 2;
-            from[pos * 2] = fx;
-            from[pos * 2 + 1] = fy;
-            to[pos * 2] = (double)flow[p] + fx;
-            to[pos * 2 + 1] = (double)flow[p + 1] + fy;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+struct FlowRows : MaskOn {
+    const F* flow;
+    double *from, *to;
+    __device__ __forceinline__ void emit(int x, int y, unsigned long long pos) const
+    {
+        const double fx = ((double)x + 0.5) - 1e-8, fy = ((double)y + 0.5) - 1e-8;
+        const size_t p = ((size_t)y * w + x) * 2;
+        from[pos * 2] = fx;
+        from[pos * 2 + 1] = fy;
+        to[pos * 2] = (double)flow[p] + fx;
+        to[pos * 2 + 1] = (double)flow[p + 1] + fy;
     }
-}
+};
 
 // np.float32(flow_abs.transpose(2, 0, 1) / [[[w]], [[h]]]): the quotient in float64, then the cast
 template <typename F>
@@ -350,8 +239,7 @@ static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, i
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t ncell = (size_t)cells_w * cells_h;
-    hipLaunchKernelGGL(k_ep_fill_u32, dim3(div_up((long long)ncell, 256)), dim3(256), 0, st, grid, ncell, FIRST ? EP_EMPTY : 0u,
-                       outside);
+    fill(grid, ncell, FIRST ? EP_EMPTY : 0u, outside, st);
     if (n) {
         const dim3 g(div_up((long long)n, 256));
         if (uv_type == CAMD_VALUE_F64)
@@ -362,12 +250,6 @@ static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, i
     }
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
-}
-
-static int sum_blocks(size_t n)
-{
-    const long long g = (long long)((n + 255) / 256);
-    return (int)(g < 1 ? 1 : g > EP_MAX_BLOCKS ? EP_MAX_BLOCKS : g);
 }
 
 }  // namespace camd
@@ -399,7 +281,7 @@ int camd_cell_intersect_count(const uint32_t* first1, const uint32_t* first2, in
     if (!first1 || !first2 || !colcount) { set_error("camd_cell_intersect_count: NULL argument"); return CAMD_ERR_BAD_ARG; }
     rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
-    hipLaunchKernelGGL(k_ep_isect_count, dim3(cells_w), dim3(256), 0, (hipStream_t)stream, first1, first2, cells_h, colcount);
+    row_count(EpIsect{first1, first2, cells_h, nullptr, nullptr}, cells_h, cells_w, colcount, (hipStream_t)stream);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -416,8 +298,8 @@ int camd_cell_intersect_emit(const uint32_t* first1, const uint32_t* first2, int
     }
     rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
-    hipLaunchKernelGGL(k_ep_isect_emit, dim3(cells_w), dim3(256), 0, (hipStream_t)stream, first1, first2, cells_h, start, idx1, idx2,
-                       capacity, count);
+    row_emit(EpIsect{first1, first2, cells_h, idx1, idx2}, cells_h, cells_w, (const unsigned long long*)start, capacity, count,
+             (hipStream_t)stream);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -462,7 +344,7 @@ int camd_overlap_emit(const void* uv1, const void* uv2, int uv_type, size_t n, i
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        hipLaunchKernelGGL(k_ep_fill_u32, dim3(1), dim3(256), 0, st, (uint32_t*)nullptr, (size_t)0, 0u, count);
+        fill((uint32_t*)nullptr, 0, 0u, count, st);
     } else {
         const dim3 g(camd_overlap_blocks(n));
         if (uv_type == CAMD_VALUE_F64)
@@ -531,16 +413,14 @@ int camd_flow_to_matched_uvs(const void* flow_abs, int flow_type, const uint8_t*
     int rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* rowoff = reinterpret_cast<unsigned long long*>(workspace);
-    uint32_t* rowcount = reinterpret_cast<uint32_t*>(rowoff + h);
-    hipLaunchKernelGGL(k_ep_mask_count, dim3(h), dim3(256), 0, st, mask, w, rowcount);
-    hipLaunchKernelGGL(k_ep_mask_scan, dim3(1), dim3(256), 0, st, rowcount, h, rowoff, count);
+    const RowWorkspace ws(workspace, h);
+    const MaskOn on = {mask, w};
+    mask_row_count(on, h, ws.rowcount, st);
+    row_scan(ws.rowcount, h, ws.rowoff, count, st);
     if (flow_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_ep_flow_emit<double>), dim3(h), dim3(256), 0, st, (const double*)flow_abs, mask, w, rowoff, uvs_from,
-                           uvs_to, capacity);
+        row_emit(FlowRows<double>{on, (const double*)flow_abs, uvs_from, uvs_to}, w, h, ws.rowoff, capacity, nullptr, st);
     else
-        hipLaunchKernelGGL((k_ep_flow_emit<float>), dim3(h), dim3(256), 0, st, (const float*)flow_abs, mask, w, rowoff, uvs_from,
-                           uvs_to, capacity);
+        row_emit(FlowRows<float>{on, (const float*)flow_abs, uvs_from, uvs_to}, w, h, ws.rowoff, capacity, nullptr, st);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }

@@ -9,6 +9,7 @@
 // contraction; NumPy's BLAS may order / fuse them differently, so parity with the oracle is to ~1 ulp on the
 // points and exact on the z-buffer except where a projection lands within rounding error of x.5.
 #include "common.hpp"
+#include "compact.hpp"
 
 namespace camd {
 
@@ -55,88 +56,27 @@ __device__ __forceinline__ double zkey_inv(unsigned long long k)
 }
 static constexpr unsigned long long ZKEY_EMPTY = 0xffffffffffffffffull;
 
-__global__ __launch_bounds__(256) void k_pc_count(const double* __restrict__ depth, PcGrid g, uint32_t* __restrict__ rowcount)
-{
-    __shared__ uint32_t part[4];
-    const int y = blockIdx.x;
-    uint32_t c = 0;
-    for (int x = threadIdx.x; x < g.gw; x += 256) c += pc_sample(depth, g, x, y) != 0.0 ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rowcount[y] = part[0] + part[1] + part[2] + part[3];
-}
-
-// exclusive scan of the row counts (one workgroup; rows <= a few thousand)
-__global__ __launch_bounds__(256) void k_pc_scan(const uint32_t* __restrict__ rowcount, int n,
-                                                 unsigned long long* __restrict__ rowoff,
-                                                 unsigned long long* __restrict__ total)
-{
-    __shared__ unsigned long long carry;
-    __shared__ unsigned long long wsum[4];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + threadIdx.x;
-        unsigned long long v = i < n ? rowcount[i] : 0ull, incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            unsigned long long t = __shfl_up(incl, o);
-            if ((threadIdx.x & 63) >= o) incl += t;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) before += wsum[k];
-        if (i < n) rowoff[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry = before + incl;
-        __syncthreads();
+// depth_to_point_cloud as a compaction (compact.hpp): the grid cells with a non-zero depth, in row-major order
+struct PcRows {
+    const double* depth;
+    PcGrid g;
+    double Ki[9];
+    double* points;
+    double* uv;  // NULL: the points alone
+    __device__ __forceinline__ bool on(int x, int y) const { return pc_sample(depth, g, x, y) != 0.0; }
+    __device__ __forceinline__ void emit(int x, int y, unsigned long long pos) const
+    {
+        const double z = pc_sample(depth, g, x, y);
+        // utils.py:225-246: us, vs are grid indices (/ interpolation_rate when upsampled)
+        const double u = g.rate == 1.0 ? (double)x : (double)x / g.rate;
+        const double v = g.rate == 1.0 ? (double)y : (double)y / g.rate;
+        const double p0 = u * z, p1 = v * z, p2 = 1.0 * z;
+        points[pos * 3 + 0] = dot3(Ki[0], Ki[1], Ki[2], p0, p1, p2);
+        points[pos * 3 + 1] = dot3(Ki[3], Ki[4], Ki[5], p0, p1, p2);
+        points[pos * 3 + 2] = dot3(Ki[6], Ki[7], Ki[8], p0, p1, p2);
+        if (uv) { uv[pos * 2] = u; uv[pos * 2 + 1] = v; }
     }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ __launch_bounds__(256) void k_pc_emit(const double* __restrict__ depth, PcGrid g,
-                                                 const unsigned long long* __restrict__ rowoff, double Ki0, double Ki1,
-                                                 double Ki2, double Ki3, double Ki4, double Ki5, double Ki6, double Ki7,
-                                                 double Ki8, double* __restrict__ points, double* __restrict__ uv,
-                                                 size_t capacity)
-{
-    __shared__ uint32_t wcnt[4];
-    __shared__ unsigned long long run;
-    const int y = blockIdx.x;
-    if (threadIdx.x == 0) run = rowoff[y];
-    __syncthreads();
-    for (int base = 0; base < g.gw; base += 256) {
-        const int x = base + threadIdx.x;
-        const double z = x < g.gw ? pc_sample(depth, g, x, y) : 0.0;
-        const bool nz = z != 0.0;
-        const unsigned long long bal = __ballot(nz);
-        const uint32_t below = __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
-        if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(bal);
-        __syncthreads();
-        unsigned long long pos = run + below;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) pos += wcnt[k];
-        if (nz && pos < capacity) {
-            // utils.py:225-246: us, vs are grid indices (/ interpolation_rate when upsampled)
-            const double u = g.rate == 1.0 ? (double)x : (double)x / g.rate;
-            const double v = g.rate == 1.0 ? (double)y : (double)y / g.rate;
-            const double p0 = u * z, p1 = v * z, p2 = 1.0 * z;
-            points[pos * 3 + 0] = dot3(Ki0, Ki1, Ki2, p0, p1, p2);
-            points[pos * 3 + 1] = dot3(Ki3, Ki4, Ki5, p0, p1, p2);
-            points[pos * 3 + 2] = dot3(Ki6, Ki7, Ki8, p0, p1, p2);
-            if (uv) { uv[pos * 2] = u; uv[pos * 2 + 1] = v; }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(256) void k_fill_u64(unsigned long long* p, size_t n, unsigned long long v)
-{
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-}
+};
 
 struct Mat34 { double m[12]; };
 struct Mat33 { double m[9]; };
@@ -288,23 +228,6 @@ __global__ __launch_bounds__(256) void k_pc_owner(const double* __restrict__ poi
     if (keys[pix] == key) atomicMax(owner + pix, (uint32_t)i + 1u);
 }
 
-// pass 3 of point_cloud_to_arr2d: out[pix][c] = values[owner][c] (utils.py:314-316), bg where nothing landed (:308)
-template <typename V>
-__global__ __launch_bounds__(256) void k_arr2d_gather(const uint32_t* __restrict__ owner, size_t npix,
-                                                      const V* __restrict__ values, int channels, V bg,
-                                                      V* __restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npix) return;
-    const uint32_t o = owner[i];
-    if (o) {
-        const V* src = values + (size_t)(o - 1u) * channels;
-        for (int c = 0; c < channels; c++) out[i * channels + c] = src[c];
-    } else {
-        for (int c = 0; c < channels; c++) out[i * channels + c] = bg;
-    }
-}
-
 static int make_grid(PcGrid* g, int w, int h, double rate, const char* who)
 {
     if (w <= 0 || h <= 0 || !(rate > 0.0)) { set_error("%s: bad size / interpolation rate", who); return CAMD_ERR_BAD_ARG; }
@@ -342,7 +265,7 @@ size_t camd_point_cloud_workspace_bytes(int w, int h, double rate)
 {
     PcGrid g;
     if (make_grid(&g, w, h, rate, "camd_point_cloud_workspace_bytes") != CAMD_OK) return 0;
-    return (size_t)g.gh * (4 + 8) + 64;
+    return RowWorkspace::bytes(g.gh);
 }
 
 int camd_depth_to_point_cloud(const double* depth, int w, int h, const double Kinv[9], double rate, double* points,
@@ -355,12 +278,13 @@ int camd_depth_to_point_cloud(const double* depth, int w, int h, const double Ki
     rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* rowoff = reinterpret_cast<unsigned long long*>(workspace);
-    uint32_t* rowcount = reinterpret_cast<uint32_t*>(rowoff + g.gh);
-    hipLaunchKernelGGL(k_pc_count, dim3(g.gh), dim3(256), 0, st, depth, g, rowcount);
-    hipLaunchKernelGGL(k_pc_scan, dim3(1), dim3(256), 0, st, rowcount, g.gh, rowoff, count);
-    hipLaunchKernelGGL(k_pc_emit, dim3(g.gh), dim3(256), 0, st, depth, g, rowoff, Kinv[0], Kinv[1], Kinv[2], Kinv[3],
-                       Kinv[4], Kinv[5], Kinv[6], Kinv[7], Kinv[8], points, uv, capacity);
+    const RowWorkspace ws(workspace, g.gh);
+    PcRows f;
+    f.depth = depth; f.g = g; f.points = points; f.uv = uv;
+    for (int i = 0; i < 9; i++) f.Ki[i] = Kinv[i];
+    row_count(f, g.gw, g.gh, ws.rowcount, st);
+    row_scan(ws.rowcount, g.gh, ws.rowoff, count, st);
+    row_emit(f, g.gw, g.gh, ws.rowoff, capacity, nullptr, st);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -391,7 +315,7 @@ int camd_point_cloud_to_depth(const double* points, size_t n, int point_stride, 
     const size_t npix = (size_t)w * h;
     Mat33 Km;
     for (int i = 0; i < 9; i++) Km.m[i] = K[i];
-    hipLaunchKernelGGL(k_fill_u64, dim3(div_up((long long)npix, 256)), dim3(256), 0, st, keys_ws, npix, ZKEY_EMPTY);
+    fill(keys_ws, npix, ZKEY_EMPTY, nullptr, st);
     if (n) hipLaunchKernelGGL(k_pc_scatter, dim3(div_up((long long)n, 256)), dim3(256), 0, st, points, n, point_stride, Km, w, h, keys_ws);
     hipLaunchKernelGGL(k_pc_resolve, dim3(div_up((long long)npix, 256)), dim3(256), 0, st, keys_ws, npix, bg_value, depth);
     CAMD_LAUNCH_CHECK();
@@ -417,7 +341,7 @@ int camd_project_depth(const double* depth2, int w2, int h2, const double K2inv[
     Mat34 M;
     for (int i = 0; i < 9; i++) { Ki.m[i] = K2inv[i]; Km.m[i] = K1[i]; }
     for (int i = 0; i < 12; i++) M.m[i] = T_2in1[i];
-    hipLaunchKernelGGL(k_fill_u64, dim3(div_up((long long)npix, 256)), dim3(256), 0, st, keys_ws, npix, ZKEY_EMPTY);
+    fill(keys_ws, npix, ZKEY_EMPTY, nullptr, st);
     hipLaunchKernelGGL(k_project_depth, dim3(div_up(g.gw, 256), g.gh), dim3(256), 0, st, depth2, g, Ki, M, Km, w1, h1, keys_ws);
     hipLaunchKernelGGL(k_pc_resolve, dim3(div_up((long long)npix, 256)), dim3(256), 0, st, keys_ws, npix, 0.0, depth1);
     CAMD_LAUNCH_CHECK();
@@ -496,15 +420,7 @@ int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, 
         hipLaunchKernelGGL(k_pc_scatter, src_grid, dim3(256), 0, st, points, n, point_stride, Km, w, h, keys_ws);
         hipLaunchKernelGGL(k_pc_owner, src_grid, dim3(256), 0, st, points, n, point_stride, Km, w, h, keys_ws, owner_ws);
     }
-    if (value_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_arr2d_gather<double>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const double*)values,
-                           channels, bg_value, (double*)out);
-    else if (value_type == CAMD_VALUE_F32)
-        hipLaunchKernelGGL((k_arr2d_gather<float>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const float*)values,
-                           channels, (float)bg_value, (float*)out);
-    else
-        hipLaunchKernelGGL((k_arr2d_gather<uint8_t>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const uint8_t*)values,
-                           channels, (uint8_t)bg_value, (uint8_t*)out);
+    owner_gather(value_type, owner_ws, npix, values, channels, bg_value, 0, out, st);  // utils.py:308, 314-316
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }

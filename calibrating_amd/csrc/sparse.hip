@@ -10,6 +10,7 @@
 // an integer maximum, the bins are filled in any order and searched by the key (distance, index), the plane sums are
 // reduced in a fixed order without float atomics.
 #include "common.hpp"
+#include "compact.hpp"
 #include "triangulate.hpp"
 
 #include <cmath>
@@ -17,7 +18,6 @@
 namespace camd {
 
 constexpr int SP_MAX_RADIUS = CAMD_NEAREST_MAX_RADIUS;
-constexpr int PL_MAX_BLOCKS = 1024;
 
 // ---- a. scatter ------------------------------------------------------------------------------------------------------
 // xs, ys = np.int32(uvs.round()) (half to even); rows outside the image -- NaN and inf among them -- are dropped (:312-313)
@@ -29,12 +29,6 @@ __device__ __forceinline__ bool sp_pixel(const double* __restrict__ uv, size_t i
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_sp_clear_u32(uint32_t* __restrict__ p, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = 0u;
-}
-
 // owner[pix] = 1 + the largest row index landing there: arr2d[ys, xs] = values assigns in row order, the last one stays
 __global__ __launch_bounds__(256) void k_sp_owner(const double* __restrict__ uv, size_t n, int stride, int w, int h,
                                                   uint32_t* __restrict__ owner)
@@ -43,23 +37,6 @@ __global__ __launch_bounds__(256) void k_sp_owner(const double* __restrict__ uv,
     if (i >= n) return;
     size_t pix;
     if (sp_pixel(uv, i, stride, w, h, &pix)) atomicMax(owner + pix, (uint32_t)i + 1u);
-}
-
-// keep != 0: a caller's arr2d is updated in place, pixels nobody reaches are left alone
-template <typename V>
-__global__ __launch_bounds__(256) void k_sp_gather(const uint32_t* __restrict__ owner, size_t npix,
-                                                   const V* __restrict__ values, int channels, V bg, int keep,
-                                                   V* __restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npix) return;
-    const uint32_t o = owner[i];
-    if (o) {
-        const V* src = values + (size_t)(o - 1u) * channels;
-        for (int c = 0; c < channels; c++) out[i * channels + c] = src[c];
-    } else if (!keep) {
-        for (int c = 0; c < channels; c++) out[i * channels + c] = bg;
-    }
 }
 
 // ---- b. arr2d_to_uvzs ------------------------------------------------------------------------------------------------
@@ -76,76 +53,18 @@ __global__ __launch_bounds__(256) void k_sp_all_rows(const O* __restrict__ arr, 
     rows[r * 3 + 2] = arr[(size_t)y * w + x];
 }
 
-__global__ __launch_bounds__(256) void k_sp_mask_count(const uint8_t* __restrict__ mask, int w, uint32_t* __restrict__ rowcount)
-{
-    __shared__ uint32_t part[4];
-    const int y = blockIdx.x;
-    uint32_t c = 0;
-    for (int x = threadIdx.x; x < w; x += 256) c += mask[(size_t)y * w + x] ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) rowcount[y] = part[0] + part[1] + part[2] + part[3];
-}
-
-// exclusive scan of the row counts (one workgroup; rows <= a few thousand)
-__global__ __launch_bounds__(256) void k_sp_mask_scan(const uint32_t* __restrict__ rowcount, int n,
-                                                      unsigned long long* __restrict__ rowoff,
-                                                      unsigned long long* __restrict__ total)
-{
-    __shared__ unsigned long long carry;
-    __shared__ unsigned long long wsum[4];
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + threadIdx.x;
-        unsigned long long v = i < n ? rowcount[i] : 0ull, incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            unsigned long long t = __shfl_up(incl, o);
-            if ((threadIdx.x & 63) >= o) incl += t;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) before += wsum[k];
-        if (i < n) rowoff[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-// np.array([xs[mask], ys[mask], arr2d[mask]]).T: the masked pixels in row-major order
+// np.array([xs[mask], ys[mask], arr2d[mask]]).T: the masked pixels in row-major order, as a compaction (compact.hpp)
 template <typename O>
-__global__ __launch_bounds__(256) void k_sp_mask_emit(const O* __restrict__ arr, const uint8_t* __restrict__ mask, int w,
-                                                      const unsigned long long* __restrict__ rowoff, O* __restrict__ rows,
-                                                      size_t capacity)
-{
-    __shared__ uint32_t wcnt[4];
-    __shared__ unsigned long long run;
-    const int y = blockIdx.x;
-    if (threadIdx.x == 0) run = rowoff[y];
-    __syncthreads();
-    for (int base = 0; base < w; base += 256) {
-        const int x = base + threadIdx.x;
-        const bool on = x < w && mask[(size_t)y * w + x] != 0;
-        const unsigned long long bal = __ballot(on);
-        const uint32_t below = __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
-        if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = __popcll(bal);
-        __syncthreads();
-        unsigned long long pos = run + below;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); k++) pos += wcnt[k];
-        if (on && pos < capacity) {
-            rows[pos * 3 + 0] = (O)x;
-            rows[pos * 3 + 1] = (O)y;
-            rows[pos * 3 + 2] = arr[(size_t)y * w + x];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+struct MaskRows : MaskOn {
+    const O* arr;
+    O* rows;
+    __device__ __forceinline__ void emit(int x, int y, unsigned long long pos) const
+    {
+        rows[pos * 3 + 0] = (O)x;
+        rows[pos * 3 + 1] = (O)y;
+        rows[pos * 3 + 2] = arr[(size_t)y * w + x];
     }
-}
+};
 
 // ---- c. nearest fill -------------------------------------------------------------------------------------------------
 // A sample (u, v) lies in the integer cell (floor(u), floor(v)).  A pixel x can only be nearer than `distance` <= R to
@@ -233,7 +152,7 @@ __global__ __launch_bounds__(256) void k_sp_nearest(const double* __restrict__ s
 
 // ---- d. plane fit ----------------------------------------------------------------------------------------------------
 // sums: 0 uu  1 uv  2 u  3 vv  4 v  5 n  6 uz  7 vz  8 z.  Thread t of block g adds rows g*256+t, +G*256, ... in that
-// order; the block adds its 256 threads by a fixed tree; k_sp_plane_final adds the G partials in index order.
+// order; the block adds its 256 threads by a fixed tree (block_tree, compact.hpp); k_sp_plane_final adds the G partials in index order.
 template <typename Z>
 __global__ __launch_bounds__(256) void k_sp_plane_partials(const double* __restrict__ uv, int stride, const Z* __restrict__ z,
                                                            size_t n, double* __restrict__ partials)
@@ -246,16 +165,7 @@ __global__ __launch_bounds__(256) void k_sp_plane_partials(const double* __restr
         s[3] += v * v; s[4] += v;     s[5] += 1.0;
         s[6] += u * zz; s[7] += v * zz; s[8] += zz;
     }
-    for (int q = 0; q < 9; q++) {
-        sh[threadIdx.x] = s[q];
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partials[(size_t)blockIdx.x * 9 + q] = sh[0];
-        __syncthreads();
-    }
+    block_tree<9>(s, sh, partials + (size_t)blockIdx.x * 9);
 }
 
 __global__ __launch_bounds__(64) void k_sp_plane_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
@@ -339,18 +249,9 @@ int camd_uvzs_to_arr2d(const double* uv, size_t n, int uv_stride, int w, int h, 
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w * h;
-    const dim3 dst_grid(div_up((long long)npix, 256));
-    hipLaunchKernelGGL(k_sp_clear_u32, dst_grid, dim3(256), 0, st, owner_ws, npix);
+    fill(owner_ws, npix, 0u, nullptr, st);
     if (n) hipLaunchKernelGGL(k_sp_owner, dim3(div_up((long long)n, 256)), dim3(256), 0, st, uv, n, uv_stride, w, h, owner_ws);
-    if (value_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_sp_gather<double>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const double*)values, channels,
-                           bg_value, keep, (double*)out);
-    else if (value_type == CAMD_VALUE_F32)
-        hipLaunchKernelGGL((k_sp_gather<float>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const float*)values, channels,
-                           (float)bg_value, keep, (float*)out);
-    else
-        hipLaunchKernelGGL((k_sp_gather<uint8_t>), dst_grid, dim3(256), 0, st, owner_ws, npix, (const uint8_t*)values, channels,
-                           keep ? (uint8_t)0 : (uint8_t)bg_value, keep, (uint8_t*)out);
+    owner_gather(value_type, owner_ws, npix, values, channels, bg_value, keep, out, st);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -371,7 +272,7 @@ int camd_arr2d_to_uvzs(const void* arr2d, int w, int h, int as_int64, void* rows
     return CAMD_OK;
 }
 
-size_t camd_arr2d_mask_workspace_bytes(int h) { return h > 0 ? (size_t)h * (4 + 8) + 64 : 0; }
+size_t camd_arr2d_mask_workspace_bytes(int h) { return RowWorkspace::bytes(h); }
 
 int camd_arr2d_to_uvzs_masked(const void* arr2d, const uint8_t* mask, int w, int h, int as_int64, void* rows,
                               size_t capacity, unsigned long long* count, void* workspace, void* stream)
@@ -383,16 +284,14 @@ int camd_arr2d_to_uvzs_masked(const void* arr2d, const uint8_t* mask, int w, int
     int rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* rowoff = reinterpret_cast<unsigned long long*>(workspace);
-    uint32_t* rowcount = reinterpret_cast<uint32_t*>(rowoff + h);
-    hipLaunchKernelGGL(k_sp_mask_count, dim3(h), dim3(256), 0, st, mask, w, rowcount);
-    hipLaunchKernelGGL(k_sp_mask_scan, dim3(1), dim3(256), 0, st, rowcount, h, rowoff, count);
+    const RowWorkspace ws(workspace, h);
+    const MaskOn on = {mask, w};
+    mask_row_count(on, h, ws.rowcount, st);
+    row_scan(ws.rowcount, h, ws.rowoff, count, st);
     if (as_int64)
-        hipLaunchKernelGGL((k_sp_mask_emit<long long>), dim3(h), dim3(256), 0, st, (const long long*)arr2d, mask, w, rowoff,
-                           (long long*)rows, capacity);
+        row_emit(MaskRows<long long>{on, (const long long*)arr2d, (long long*)rows}, w, h, ws.rowoff, capacity, nullptr, st);
     else
-        hipLaunchKernelGGL((k_sp_mask_emit<double>), dim3(h), dim3(256), 0, st, (const double*)arr2d, mask, w, rowoff,
-                           (double*)rows, capacity);
+        row_emit(MaskRows<double>{on, (const double*)arr2d, (double*)rows}, w, h, ws.rowoff, capacity, nullptr, st);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -422,7 +321,7 @@ int camd_sparse_bin_count(const double* uv, size_t n, int uv_stride, int w, int 
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t ncell = (size_t)b.bw * b.bh;
-    hipLaunchKernelGGL(k_sp_clear_u32, dim3(div_up((long long)ncell, 256)), dim3(256), 0, st, counts, ncell);
+    fill(counts, ncell, 0u, nullptr, st);
     if (n) hipLaunchKernelGGL(k_sp_bin_count, dim3(div_up((long long)n, 256)), dim3(256), 0, st, uv, n, uv_stride, b, counts);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
@@ -476,11 +375,7 @@ int camd_nearest_fill(const double* sorted_uv, const uint32_t* sorted_idx, const
     return CAMD_OK;
 }
 
-int camd_plane_sums_blocks(size_t n)
-{
-    const long long g = (long long)((n + 255) / 256);
-    return (int)(g < 1 ? 1 : g > PL_MAX_BLOCKS ? PL_MAX_BLOCKS : g);
-}
+int camd_plane_sums_blocks(size_t n) { return sum_blocks(n); }
 
 int camd_plane_sums(const double* uv, int uv_stride, const void* z, int z_type, size_t n, double* partials_ws, double* sums,
                     void* stream)
@@ -492,7 +387,7 @@ int camd_plane_sums(const double* uv, int uv_stride, const void* z, int z_type, 
     int rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int g = camd_plane_sums_blocks(n);
+    const int g = sum_blocks(n);
     if (z_type == CAMD_VALUE_F64)
         hipLaunchKernelGGL((k_sp_plane_partials<double>), dim3(g), dim3(256), 0, st, uv, uv_stride, (const double*)z, n, partials_ws);
     else

@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _native, hostio
+from .sparse import _check_array, _dtype_name
 
 
 def _to_dev(a, dtype):
@@ -129,20 +130,6 @@ def project_depth(depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
 
 # ---- the z-buffer with a payload -----------------------------------------------------------------------------------
 _VALUE_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32, "uint8": _native.VALUE_U8}
-
-
-def _dtype_name(a):
-    return str(a.dtype).replace("torch.", "")
-
-
-def _check_array(a, what):
-    """ndarray or CUDA tensor, checked without touching the device."""
-    if isinstance(a, np.ndarray):
-        return
-    if not (hasattr(a, "is_cuda") and hasattr(a, "data_ptr")):
-        raise TypeError("%s must be a NumPy array or a torch CUDA tensor, got %s" % (what, type(a).__name__))
-    if not a.is_cuda:
-        raise ValueError("tensor inputs must live on the GPU (%s)" % what)
 
 
 def _check_xy(xy, what="xy"):

@@ -29,6 +29,7 @@ def _dtype_name(a):
 
 
 def _check_array(a, what):
+    """ndarray or CUDA tensor, checked without touching the device."""
     if _is_np(a):
         return
     if not (hasattr(a, "is_cuda") and hasattr(a, "data_ptr")):
