@@ -12,9 +12,12 @@ from .sgbm import MODE_HH, MODE_HH4, MODE_SGBM, MODE_SGBM_3WAY, StereoSGBM, Ster
 from .stereo_matching import FeatureMatchingAsStereoMatching, MetaStereoMatching, SemiGlobalBlockMatching
 from .stereo_camera import Stereo
 from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, filter_overlap_uvs, flow_abs_to_normal,
-                                flow_normal_to_abs, flow_to_matched_uvs, matching_uvs_in_one_img)
+                                flow_normal_to_abs, flow_to_matched_uvs, matching_uvs_in_one_img,
+                                matching_uvs_in_one_img_batch)
+from .reconstruction_epipolar_geometry import ReconstructionExtrinsics
 
 __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "StereoSGBM",
            "StereoSGBM_create", "MODE_SGBM", "MODE_HH", "MODE_SGBM_3WAY", "MODE_HH4", "__version__",
            "FeatureMatchingAsStereoMatching", "EssentialMatrixStereo", "filter_overlap_uvs", "matching_uvs_in_one_img",
-           "flow_abs_to_normal", "flow_normal_to_abs", "flow_to_matched_uvs", "build_set2ds_by_flowds"]
+           "flow_abs_to_normal", "flow_normal_to_abs", "flow_to_matched_uvs", "build_set2ds_by_flowds",
+           "matching_uvs_in_one_img_batch", "ReconstructionExtrinsics"]

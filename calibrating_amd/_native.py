@@ -42,6 +42,16 @@ class SgbmParams(ctypes.Structure):
     _fields_ = [(n, c_int) for n in FIELDS]
 
 
+class CellSet(ctypes.Structure):  # camd_cell_set
+    _fields_ = [("uv", c_void_p), ("n", ctypes.c_ulonglong), ("grid_offset", ctypes.c_ulonglong), ("uv_type", c_int),
+                ("cu0", c_int), ("cv0", c_int), ("cells_w", c_int), ("cells_h", c_int), ("reserved", c_int)]
+
+
+class CellTriple(ctypes.Structure):  # camd_cell_triple
+    _fields_ = [("grid_offset1", ctypes.c_ulonglong), ("grid_offset2", ctypes.c_ulonglong), ("column_offset", ctypes.c_ulonglong),
+                ("cells_w", c_int), ("cells_h", c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/calibrating_amd.h declares
 SIGNATURES = {
     "camd_last_error": (ctypes.c_char_p, []),
@@ -123,6 +133,18 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     "camd_flow_abs_to_normal": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "camd_flow_normal_to_abs": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
+    "camd_uv_bounds_blocks": (c_int, []),
+    "camd_uv_bounds_batch": (c_int, [ctypes.POINTER(CellSet), c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_cell_first_index_batch": (c_int, [ctypes.POINTER(CellSet), c_int, c_void_p, c_double, c_void_p, c_size_t, c_void_p,
+                                            c_void_p]),
+    "camd_cell_intersect_count_batch": (c_int, [c_void_p, c_size_t, ctypes.POINTER(CellTriple), c_int, c_void_p, c_void_p,
+                                                c_size_t, c_void_p]),
+    "camd_cell_intersect_emit_batch": (c_int, [c_void_p, c_size_t, ctypes.POINTER(CellTriple), c_int, c_void_p, c_void_p,
+                                               c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "camd_uvzi_pack": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_double, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "camd_column_sum_blocks": (c_int, [c_size_t]),
+    "camd_column_sum": (c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "camd_column_scale": (c_int, [c_void_p, c_size_t, c_int, c_int, c_size_t, c_size_t, c_double, c_void_p]),
     "camd_set_global_option": (c_int, [c_int, c_int]),
     "camd_lanczos4_table_host": (c_int, [c_void_p]),
     "camd_bilinear_table_host": (c_int, [c_void_p]),

@@ -208,6 +208,133 @@ __global__ __launch_bounds__(256) void k_ep_flow_normal_to_abs(const F* __restri
     out[p * 2 + 1] = (double)flow[npix + p] * th;
 }
 
+// ---- all triples of a reconstruction in one pass (calibrating_amd/reconstruction_epipolar_geometry.py) ------------------
+// The same cells, grids and compaction as above, with blockIdx.y choosing the point set / the triple from a descriptor
+// table in device memory.  Grids of several windows lie in one buffer at their grid_offset; the columns of all triples
+// lie in one flat count / start array at their column_offset, so ONE scan serves all and a triple's pairs come out
+// contiguous, at start[column_offset], in the order the single call gives them.
+constexpr int EP_BOUNDS_BLOCKS = 32;
+
+template <typename T>
+__device__ __forceinline__ void ep_bounds_rows(const T* __restrict__ uv, size_t n, double* lo, double* hi, int* nan)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)EP_BOUNDS_BLOCKS * 256)
+        for (int k = 0; k < 2; k++) {
+            const double x = (double)uv[i * 2 + k];
+            if (x != x) *nan = 1;
+            lo[k] = fmin(lo[k], x);
+            hi[k] = fmax(hi[k], x);
+        }
+}
+
+// bounds[(set * EP_BOUNDS_BLOCKS + block) * 4 ..] = min u, min v, max u, max v of the block's rows (+inf / -inf where it
+// has none, NaN where a coordinate is NaN): min and max commute, so the host's minimum over the blocks is exact
+__global__ __launch_bounds__(256) void k_ep_bounds_batch(const camd_cell_set* __restrict__ sets, double* __restrict__ bounds)
+{
+    __shared__ double sh[4][4];
+    const camd_cell_set s = sets[blockIdx.y];
+    double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    int nan = 0;
+    if (s.uv_type == CAMD_VALUE_F64) ep_bounds_rows((const double*)s.uv, (size_t)s.n, lo, hi, &nan);
+    else ep_bounds_rows((const float*)s.uv, (size_t)s.n, lo, hi, &nan);
+    double v[4] = {lo[0], lo[1], -hi[0], -hi[1]};  // four minima
+    for (int k = 0; k < 4; k++) {
+        for (int o = 32; o > 0; o >>= 1) v[k] = fmin(v[k], __shfl_down(v[k], o));
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v[k];
+    }
+    nan = __syncthreads_or(nan);
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        const double m = fmin(fmin(sh[0][k], sh[1][k]), fmin(sh[2][k], sh[3][k]));
+        bounds[((size_t)blockIdx.y * EP_BOUNDS_BLOCKS + blockIdx.x) * 4 + k] = nan ? NAN : (k < 2 ? m : -m);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ep_first_batch(const camd_cell_set* __restrict__ sets, double d,
+                                                        uint32_t* __restrict__ grids, unsigned long long* __restrict__ outside)
+{
+    const camd_cell_set s = sets[blockIdx.y];
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= s.n) return;
+    const EpWin w = {s.cu0, s.cv0, s.cells_w, s.cells_h};
+    size_t cell;
+    const bool in = s.uv_type == CAMD_VALUE_F64 ? ep_cell((const double*)s.uv, i, 2, d, w, &cell)
+                                                : ep_cell((const float*)s.uv, i, 2, (float)d, w, &cell);
+    if (!in) { atomicAdd(outside, 1ull); return; }
+    atomicMin(grids + s.grid_offset + cell, (uint32_t)i);
+}
+
+// one workgroup per (u column, triple): k_row_count / k_row_emit of compact.hpp with the triple's grids
+__global__ __launch_bounds__(256) void k_ep_isect_count_batch(const camd_cell_triple* __restrict__ triples,
+                                                              const uint32_t* __restrict__ grids, uint32_t* __restrict__ colcount)
+{
+    __shared__ uint32_t part[4];
+    const camd_cell_triple t = triples[blockIdx.y];
+    const int cu = blockIdx.x;
+    if (cu >= t.cells_w) return;
+    const EpIsect f = {grids + t.grid_offset1, grids + t.grid_offset2, t.cells_h, nullptr, nullptr};
+    uint32_t c = 0;
+    for (int v = threadIdx.x; v < t.cells_h; v += 256) c += f.on(v, cu) ? 1u : 0u;
+    c = block_total(wave_sum(c), part);
+    if (threadIdx.x == 0) colcount[t.column_offset + cu] = c;
+}
+
+__global__ __launch_bounds__(256) void k_ep_isect_emit_batch(const camd_cell_triple* __restrict__ triples,
+                                                             const uint32_t* __restrict__ grids,
+                                                             const unsigned long long* __restrict__ start, long long* idx1,
+                                                             long long* idx2, size_t capacity, unsigned long long* __restrict__ counts)
+{
+    __shared__ uint32_t wcnt[4];
+    __shared__ unsigned long long run;
+    const camd_cell_triple t = triples[blockIdx.y];
+    const int cu = blockIdx.x;
+    if (cu >= t.cells_w) return;
+    const EpIsect f = {grids + t.grid_offset1, grids + t.grid_offset2, t.cells_h, idx1, idx2};
+    if (threadIdx.x == 0) {
+        run = start[t.column_offset + cu];
+        if (cu == 0) counts[blockIdx.y] = start[t.column_offset + t.cells_w] - start[t.column_offset];
+    }
+    __syncthreads();
+    for (int base = 0; base < t.cells_h; base += 256) {
+        const int v = base + threadIdx.x;
+        const bool on = v < t.cells_h && f.on(v, cu);
+        const unsigned long long pos = block_slot(on, run, wcnt);
+        if (on && pos < capacity) f.emit(v, cu, pos);
+        __syncthreads();
+        if (threadIdx.x == 0) run += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+// ---- the per-view depth rows [u, v, z, other view] ---------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_ep_uvzi_pack(const T* __restrict__ uv, const double* __restrict__ z, size_t n, double view,
+                                                      double* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i * 4] = (double)uv[i * 2];
+    out[i * 4 + 1] = (double)uv[i * 2 + 1];
+    out[i * 4 + 2] = z[i];
+    out[i * 4 + 3] = view;
+}
+
+// s[0] = sum of a[i * stride], i < n: the shape of k_ep_vector_partials
+__global__ __launch_bounds__(256) void k_ep_column_partials(const double* __restrict__ a, size_t n, int stride,
+                                                            double* __restrict__ partials)
+{
+    __shared__ double sh[256];
+    double s[1] = {0};
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s[0] += a[i * stride];
+    block_tree<1>(s, sh, partials + blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_ep_column_scale(double* __restrict__ a, size_t n, int stride, double rate)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i * stride] *= rate;
+}
+
 static int make_window(EpWin* w, int cu0, int cv0, int cells_w, int cells_h, const char* who)
 {
     if (cells_w <= 0 || cells_h <= 0 || (unsigned long long)cells_w * (unsigned long long)cells_h > EP_MAX_CELLS) {
@@ -249,6 +376,67 @@ static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, i
                                outside);
     }
     CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+
+// the tables are checked on the host, entry by entry, before anything indexes device memory with them
+static int upload(const void* host, size_t bytes, void* dev, hipStream_t st, const char* who)
+{
+    const hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) { set_error("%s: hipMemcpyAsync: %s", who, hipGetErrorString(e)); return CAMD_ERR_HIP; }
+    return CAMD_OK;
+}
+
+static int check_sets(const char* who, const camd_cell_set* sets, int nsets, const void* sets_dev, bool windows, size_t grid_cells,
+                      size_t* max_n)
+{
+    if (!sets || !sets_dev || nsets <= 0 || nsets > 65535) {
+        set_error("%s: 1 .. 65535 sets and both tables are required", who);
+        return CAMD_ERR_BAD_ARG;
+    }
+    *max_n = 0;
+    for (int k = 0; k < nsets; k++) {
+        const camd_cell_set& s = sets[k];
+        if (!uv_type_ok(s.uv_type) || s.n >= 0xffffffffull || (s.n && !s.uv)) {
+            set_error("%s: set %d: bad type, rows or pointer", who, k);
+            return CAMD_ERR_BAD_ARG;
+        }
+        if (windows) {
+            EpWin w;
+            const int rc = make_window(&w, s.cu0, s.cv0, s.cells_w, s.cells_h, who);
+            if (rc != CAMD_OK) return rc;
+            if (s.grid_offset > grid_cells || (size_t)s.cells_w * s.cells_h > grid_cells - s.grid_offset) {
+                set_error("%s: set %d: its grid leaves the %zu cells given", who, k, grid_cells);
+                return CAMD_ERR_BAD_ARG;
+            }
+        }
+        if (s.n > *max_n) *max_n = (size_t)s.n;
+    }
+    return CAMD_OK;
+}
+
+static int check_triples(const char* who, const camd_cell_triple* triples, int ntriples, const void* triples_dev, size_t grid_cells,
+                         size_t ncols, int* max_w)
+{
+    if (!triples || !triples_dev || ntriples <= 0 || ntriples > 65535) {
+        set_error("%s: 1 .. 65535 triples and both tables are required", who);
+        return CAMD_ERR_BAD_ARG;
+    }
+    *max_w = 0;
+    for (int k = 0; k < ntriples; k++) {
+        const camd_cell_triple& t = triples[k];
+        EpWin w;
+        const int rc = make_window(&w, 0, 0, t.cells_w, t.cells_h, who);
+        if (rc != CAMD_OK) return rc;
+        const size_t cells = (size_t)t.cells_w * t.cells_h;
+        if (t.grid_offset1 > grid_cells || cells > grid_cells - t.grid_offset1 || t.grid_offset2 > grid_cells ||
+            cells > grid_cells - t.grid_offset2 || t.column_offset > ncols || (size_t)t.cells_w > ncols - t.column_offset) {
+            set_error("%s: triple %d: its grids or columns leave the %zu cells / %zu columns given", who, k, grid_cells, ncols);
+            return CAMD_ERR_BAD_ARG;
+        }
+        if (t.cells_w > *max_w) *max_w = t.cells_w;
+    }
     return CAMD_OK;
 }
 
@@ -460,6 +648,143 @@ int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h
     else
         hipLaunchKernelGGL((k_ep_flow_normal_to_abs<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)flow_normal, w, h,
                            target_w, target_h, flow_abs);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_uv_bounds_blocks(void) { return EP_BOUNDS_BLOCKS; }
+
+int camd_uv_bounds_batch(const camd_cell_set* sets_host, int nsets, camd_cell_set* sets_dev, double* bounds, void* stream)
+{
+    size_t max_n;
+    int rc = check_sets("camd_uv_bounds_batch", sets_host, nsets, sets_dev, false, 0, &max_n);
+    if (rc != CAMD_OK) return rc;
+    if (!bounds) { set_error("camd_uv_bounds_batch: NULL argument"); return CAMD_ERR_BAD_ARG; }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = upload(sets_host, sizeof(camd_cell_set) * nsets, sets_dev, st, "camd_uv_bounds_batch");
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_ep_bounds_batch, dim3(EP_BOUNDS_BLOCKS, nsets), dim3(256), 0, st, sets_dev, bounds);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_cell_first_index_batch(const camd_cell_set* sets_host, int nsets, camd_cell_set* sets_dev, double max_distance,
+                                uint32_t* grids, size_t grid_cells, unsigned long long* outside, void* stream)
+{
+    size_t max_n;
+    int rc = check_sets("camd_cell_first_index_batch", sets_host, nsets, sets_dev, true, grid_cells, &max_n);
+    if (rc != CAMD_OK) return rc;
+    if (!grids || !outside || !(max_distance > 0.0)) { set_error("camd_cell_first_index_batch: bad arguments"); return CAMD_ERR_BAD_ARG; }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = upload(sets_host, sizeof(camd_cell_set) * nsets, sets_dev, st, "camd_cell_first_index_batch");
+    if (rc != CAMD_OK) return rc;
+    fill(grids, grid_cells, EP_EMPTY, outside, st);
+    if (max_n)
+        hipLaunchKernelGGL(k_ep_first_batch, dim3(div_up((long long)max_n, 256), nsets), dim3(256), 0, st, sets_dev, max_distance,
+                           grids, outside);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_cell_intersect_count_batch(const uint32_t* grids, size_t grid_cells, const camd_cell_triple* triples_host, int ntriples,
+                                    camd_cell_triple* triples_dev, uint32_t* colcount, size_t ncols, void* stream)
+{
+    int max_w;
+    int rc = check_triples("camd_cell_intersect_count_batch", triples_host, ntriples, triples_dev, grid_cells, ncols, &max_w);
+    if (rc != CAMD_OK) return rc;
+    if (!grids || !colcount) { set_error("camd_cell_intersect_count_batch: NULL argument"); return CAMD_ERR_BAD_ARG; }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = upload(triples_host, sizeof(camd_cell_triple) * ntriples, triples_dev, st, "camd_cell_intersect_count_batch");
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_ep_isect_count_batch, dim3(max_w, ntriples), dim3(256), 0, st, triples_dev, grids, colcount);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_cell_intersect_emit_batch(const uint32_t* grids, size_t grid_cells, const camd_cell_triple* triples_host, int ntriples,
+                                   camd_cell_triple* triples_dev, const long long* start, size_t ncols, long long* idx1,
+                                   long long* idx2, size_t capacity, unsigned long long* counts, void* stream)
+{
+    int max_w;
+    int rc = check_triples("camd_cell_intersect_emit_batch", triples_host, ntriples, triples_dev, grid_cells, ncols, &max_w);
+    if (rc != CAMD_OK) return rc;
+    if (!grids || !start || !counts || (capacity && (!idx1 || !idx2))) {
+        set_error("camd_cell_intersect_emit_batch: NULL argument");
+        return CAMD_ERR_BAD_ARG;
+    }
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = upload(triples_host, sizeof(camd_cell_triple) * ntriples, triples_dev, st, "camd_cell_intersect_emit_batch");
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_ep_isect_emit_batch, dim3(max_w, ntriples), dim3(256), 0, st, triples_dev, grids,
+                       (const unsigned long long*)start, idx1, idx2, capacity, counts);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_uvzi_pack(const void* uv, int uv_type, const double* z, size_t n, double other_view, double* rows, size_t rows_total,
+                   size_t row_offset, void* stream)
+{
+    if (!rows || !uv_type_ok(uv_type) || row_offset > rows_total || n > rows_total - row_offset || (n && (!uv || !z))) {
+        set_error("camd_uvzi_pack: bad arguments (rows %zu + %zu of %zu)", row_offset, n, rows_total);
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (n == 0) return CAMD_OK;
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    const dim3 g(div_up((long long)n, 256));
+    double* out = rows + row_offset * 4;
+    if (uv_type == CAMD_VALUE_F64)
+        hipLaunchKernelGGL((k_ep_uvzi_pack<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)uv, z, n, other_view, out);
+    else
+        hipLaunchKernelGGL((k_ep_uvzi_pack<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)uv, z, n, other_view, out);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+static bool column_range_ok(size_t rows_total, int columns, int column, size_t row_offset, size_t n)
+{
+    return columns > 0 && column >= 0 && column < columns && row_offset <= rows_total && n <= rows_total - row_offset;
+}
+
+int camd_column_sum_blocks(size_t n) { return sum_blocks(n); }
+
+int camd_column_sum(const double* rows, size_t rows_total, int columns, int column, size_t row_offset, size_t n,
+                    double* partials_ws, double* sum, void* stream)
+{
+    if (!rows || !partials_ws || !sum || n == 0 || !column_range_ok(rows_total, columns, column, row_offset, n)) {
+        set_error("camd_column_sum: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int g = sum_blocks(n);
+    hipLaunchKernelGGL(k_ep_column_partials, dim3(g), dim3(256), 0, st, rows + row_offset * columns + column, n, columns, partials_ws);
+    hipLaunchKernelGGL((k_ep_final<1>), dim3(1), dim3(256), 0, st, partials_ws, g, sum);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_column_scale(double* rows, size_t rows_total, int columns, int column, size_t row_offset, size_t n, double rate,
+                      void* stream)
+{
+    if (!rows || !column_range_ok(rows_total, columns, column, row_offset, n)) {
+        set_error("camd_column_scale: bad arguments");
+        return CAMD_ERR_BAD_ARG;
+    }
+    if (n == 0) return CAMD_OK;
+    int rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
+    hipLaunchKernelGGL(k_ep_column_scale, dim3(div_up((long long)n, 256)), dim3(256), 0, (hipStream_t)stream,
+                       rows + row_offset * columns + column, n, columns, rate);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }

@@ -21,6 +21,9 @@ from .sparse import _check_array, _dev, _dtype_name, _is_np, matched_uvs_to_zs  
 from .stereo_camera import Stereo
 
 MAX_CELLS = 1 << 28  # the most one cell window may hold: two uint32 grids of it are 2 GiB
+# the most cells all grids of one pass of matching_uvs_in_one_img_batch hold together (uint32 each: 512 MiB); beyond it
+# the pairs are worked off in several passes
+BATCH_MAX_CELLS = 1 << 27
 _UV_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32}
 
 
@@ -257,6 +260,153 @@ def matching_uvs_in_one_img(uvs1, uvs2, MAX_DISTANCE=1, MIN_MATCHED_PIXELS=10, p
     if was_np:
         i1, i2 = hostio.to_host_list(i1, i2)
     return dict(uv_match_idx1=i1, uv_match_idx2=i2)
+
+
+def _batch_bounds(sets):
+    """(len(sets), 4) float64 [min u, min v, max u, max v]: ndarrays on the host, all tensors in one launch and one
+    read-back (camd_uv_bounds_batch leaves one row per workgroup; min / max commute, so finishing on the host is exact)."""
+    import torch
+    out = np.empty((len(sets), 4), np.float64)
+    dev = [k for k, s in enumerate(sets) if not _is_np(s)]
+    for k, s in enumerate(sets):
+        if _is_np(s):
+            out[k] = _min_max(s)
+    if dev:
+        lib = _native.lib()
+        B = lib.camd_uv_bounds_blocks()
+        table = (_native.CellSet * len(dev))()
+        for e, k in zip(table, dev):
+            e.uv, e.n, e.uv_type = sets[k].data_ptr(), int(sets[k].shape[0]), _UV_TYPES[_dtype_name(sets[k])]
+        device = sets[dev[0]].device
+        with torch.cuda.device(device):
+            table_dev = torch.empty(len(dev) * 48, dtype=torch.uint8, device=device)
+            parts = torch.empty((len(dev), B, 4), dtype=torch.float64, device=device)
+            _native.check(lib.camd_uv_bounds_batch(table, len(dev), table_dev.data_ptr(), parts.data_ptr(), _native.current_stream()),
+                          "matching_uvs_in_one_img_batch")
+        parts = parts.cpu().numpy()  # the one read-back of all bounds
+        out[dev, :2], out[dev, 2:] = parts[:, :, :2].min(1), parts[:, :, 2:].max(1)
+    return out
+
+
+def matching_uvs_in_one_img_batch(pairs_of_sets, MAX_DISTANCE=1, MIN_MATCHED_PIXELS=10, max_cells=None):
+    """``[matching_uvs_in_one_img(a, b, MAX_DISTANCE, MIN_MATCHED_PIXELS) for a, b in pairs_of_sets]``, bit for bit, without
+    a host synchronisation per pair: one read-back of all bounds, one of all counts.  A point set that several pairs name
+    (the SAME object) gets its first-occurrence grid once.  Sets that pairs link share one cell window, the union of their
+    bounds (the result does not depend on the window as long as it covers the data).  All grids of a pass hold at most
+    ``max_cells`` cells (default ``BATCH_MAX_CELLS``); beyond it the pairs are worked off in several passes."""
+    import torch
+    pairs = list(pairs_of_sets)
+    if not pairs:
+        return []
+    cap_cells = BATCH_MAX_CELLS if max_cells is None else int(max_cells)
+    d = float(MAX_DISTANCE)
+    if not (d > 0 and np.isfinite(d)):
+        raise ValueError("MAX_DISTANCE must be a positive number, got %r" % (MAX_DISTANCE,))
+    sets, slot = [], {}  # distinct point sets in order of first appearance
+    for a, b in pairs:
+        for uv in (a, b):
+            if id(uv) not in slot:
+                _float_rows(uv, "a point set", pairs[0][0])
+                if int(uv.shape[0]) == 0:
+                    raise ValueError("matching_uvs_in_one_img needs at least one point in each set")
+                slot[id(uv)] = len(sets)
+                sets.append(uv)
+    was_np = _is_np(sets[0])
+    names = [(np.zeros(1, _float_rows(s, "a point set")) / MAX_DISTANCE).dtype.name for s in sets]
+    devs = [_dev(sets[0], dtype=names[0])]
+    devs += [_dev(s, devs[0].device, dtype=nm) for s, nm in zip(sets[1:], names[1:])]
+    device = devs[0].device
+    raw = _batch_bounds([s if _is_np(s) else t for s, t in zip(sets, devs)])
+    with np.errstate(over="ignore", invalid="ignore"):
+        bounds = [raw[k].astype(nm) / np.dtype(nm).type(d) for k, nm in enumerate(names)]
+    # sets that a pair links share a window
+    root = list(range(len(sets)))
+
+    def find(k):
+        while root[k] != k:
+            root[k] = root[root[k]]
+            k = root[k]
+        return k
+
+    for a, b in pairs:
+        root[find(slot[id(b)])] = find(slot[id(a)])
+    hint = " -- raise MAX_DISTANCE (%r)" % (MAX_DISTANCE,)
+    windows = {r: _window([bounds[k] for k in range(len(sets)) if find(k) == r], "matching_uvs_in_one_img_batch", hint)
+               for r in sorted({find(k) for k in range(len(sets))})}
+    cells = [windows[find(k)][2] * windows[find(k)][3] for k in range(len(sets))]
+    # passes: pairs in the order of their windows, as many as the cell cap lets the grids of their sets in
+    order = sorted(range(len(pairs)), key=lambda p: (find(slot[id(pairs[p][0])]), p))
+    passes, members, used = [[]], set(), 0
+    for p in order:
+        need = {slot[id(uv)] for uv in pairs[p]}
+        if sum(cells[k] for k in need) > cap_cells:
+            raise ValueError("matching_uvs_in_one_img_batch: one pair needs %d cells, more than max_cells = %d%s"
+                             % (sum(cells[k] for k in need), cap_cells, hint))
+        extra = sum(cells[k] for k in need - members)
+        if passes[-1] and used + extra > cap_cells:
+            passes.append([])
+            members, used, extra = set(), 0, sum(cells[k] for k in need)
+        passes[-1].append(p)
+        members |= need
+        used += extra
+    lib, st = _native.lib(), _native.current_stream
+    done, keep = [], []  # per pass (pair numbers, idx, counts, outside); host tables stay alive until the read-back
+    with torch.cuda.device(device):
+        for chunk in passes:
+            mine = sorted({slot[id(uv)] for p in chunk for uv in pairs[p]})
+            goff, total = {}, 0
+            stable = (_native.CellSet * len(mine))()
+            for e, k in zip(stable, mine):
+                cu0, cv0, cw, ch = windows[find(k)]
+                e.uv, e.n, e.grid_offset, e.uv_type = devs[k].data_ptr(), int(devs[k].shape[0]), total, _UV_TYPES[names[k]]
+                e.cu0, e.cv0, e.cells_w, e.cells_h = cu0, cv0, cw, ch
+                goff[k] = total
+                total += cw * ch
+            ttable = (_native.CellTriple * len(chunk))()
+            ncols = capacity = 0
+            for e, p in zip(ttable, chunk):
+                k1, k2 = (slot[id(uv)] for uv in pairs[p])
+                _, _, cw, ch = windows[find(k1)]
+                e.grid_offset1, e.grid_offset2, e.column_offset, e.cells_w, e.cells_h = goff[k1], goff[k2], ncols, cw, ch
+                ncols += cw
+                capacity += min(int(devs[k1].shape[0]), int(devs[k2].shape[0]), cw * ch)  # a cell is shared at most once
+            grids = torch.empty(total, dtype=torch.int32, device=device)
+            tables_dev = torch.empty(len(mine) * 48 + len(chunk) * 32, dtype=torch.uint8, device=device)
+            sd, td = tables_dev.data_ptr(), tables_dev.data_ptr() + len(mine) * 48
+            outside = torch.empty(1, dtype=torch.int64, device=device)
+            who = "matching_uvs_in_one_img_batch"
+            _native.check(lib.camd_cell_first_index_batch(stable, len(mine), sd, d, grids.data_ptr(), total, outside.data_ptr(), st()), who)
+            colcount = torch.empty(ncols, dtype=torch.int32, device=device)
+            _native.check(lib.camd_cell_intersect_count_batch(grids.data_ptr(), total, ttable, len(chunk), td, colcount.data_ptr(),
+                                                              ncols, st()), who)
+            start = torch.zeros(ncols + 1, dtype=torch.int64, device=device)
+            torch.cumsum(colcount, 0, dtype=torch.int64, out=start[1:])  # ONE exclusive scan over the columns of all triples
+            idx = torch.empty((2, capacity), dtype=torch.int64, device=device)
+            counts = torch.empty(len(chunk), dtype=torch.int64, device=device)
+            _native.check(lib.camd_cell_intersect_emit_batch(grids.data_ptr(), total, ttable, len(chunk), td, start.data_ptr(), ncols,
+                                                             idx[0].data_ptr(), idx[1].data_ptr(), capacity, counts.data_ptr(), st()), who)
+            done.append((chunk, idx, counts, outside))
+            keep.append((stable, ttable))
+        numbers = torch.cat([t for _, _, c, o in done for t in (c, o)]).cpu().numpy()  # synchronises: the one read-back of all counts
+    del keep
+    results, at = [None] * len(pairs), 0
+    for chunk, idx, _, _ in done:
+        counts, out = numbers[at:at + len(chunk)], int(numbers[at + len(chunk)])
+        at += len(chunk) + 1
+        if out:
+            raise RuntimeError("matching_uvs_in_one_img_batch: %d rows fell outside the windows sized from the data" % out)
+        if was_np:
+            idx = hostio.to_host(idx[:, :int(counts.sum())])
+        off = 0
+        for p, c in zip(chunk, (int(c) for c in counts)):
+            if c < MIN_MATCHED_PIXELS:
+                results[p] = {}
+            elif was_np:
+                results[p] = dict(uv_match_idx1=idx[0, off:off + c].copy(), uv_match_idx2=idx[1, off:off + c].copy())
+            else:
+                results[p] = dict(uv_match_idx1=idx[0, off:off + c], uv_match_idx2=idx[1, off:off + c])
+            off += c
+    return results
 
 
 # ---- flow ------------------------------------------------------------------------------------------------------------

@@ -410,6 +410,54 @@ int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, f
 int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h, double target_w, double target_h,
                             double* flow_abs, void* stream);
 
+/* ---- all triples of a multi-view reconstruction in one pass (csrc/epipolar.hip; reconstruction_epipolar_geometry.py) ----
+ * The batched form of the three camd_cell_* steps above: many point sets / many pairs of grids per launch, chosen by
+ * blockIdx.y from a table.  Tables are HOST arrays; every entry is checked here against grid_cells / ncols before it is
+ * copied to the caller's device table (nsets / ntriples entries, 1 .. 65535) and used, so no table can index outside
+ * the buffers given.  uv: [n][2] contiguous.  Integer atomics only: the bits are those of the single calls.         */
+typedef struct camd_cell_set {
+    const void* uv;                 /* device rows [n][2] of uv_type */
+    unsigned long long n;           /* < 2^32 - 1 */
+    unsigned long long grid_offset; /* where this set's cells_w * cells_h grid starts in grids, in cells */
+    int uv_type, cu0, cv0, cells_w, cells_h, reserved;
+} camd_cell_set;
+typedef struct camd_cell_triple {
+    unsigned long long grid_offset1, grid_offset2; /* the two grids (one window: cells_w x cells_h) */
+    unsigned long long column_offset;              /* where its cells_w columns start in colcount / start */
+    int cells_w, cells_h;
+} camd_cell_triple;
+/* bounds[(set * B + b) * 4 + 0..3] = min u, min v, max u, max v over the rows block b of B = camd_uv_bounds_blocks()
+ * took (+inf / -inf where it took none, NaN where it met a NaN); the caller takes the minimum / maximum over b on the
+ * host.  The window fields of the sets are not read.                                                              */
+int camd_uv_bounds_blocks(void);
+int camd_uv_bounds_batch(const camd_cell_set* sets_host, int nsets, camd_cell_set* sets_dev, double* bounds, void* stream);
+/* camd_cell_first_index of every set into its own grid (grids: grid_cells uint32, cleared here; *outside as above)  */
+int camd_cell_first_index_batch(const camd_cell_set* sets_host, int nsets, camd_cell_set* sets_dev, double max_distance,
+                                uint32_t* grids, size_t grid_cells, unsigned long long* outside, void* stream);
+/* camd_cell_intersect_count / _emit of every triple: colcount[column_offset + c] for c < cells_w; the caller scans ALL
+ * ncols counts once (start: ncols + 1 int64, start[0] = 0); triple k's pairs are idx1 / idx2[start[column_offset] ..) and
+ * counts[k] (device u64) = how many.  Triples' columns must not overlap and should tile [0, ncols).  One workgroup per
+ * (u column, triple).                                                                                              */
+int camd_cell_intersect_count_batch(const uint32_t* grids, size_t grid_cells, const camd_cell_triple* triples_host, int ntriples,
+                                    camd_cell_triple* triples_dev, uint32_t* colcount, size_t ncols, void* stream);
+int camd_cell_intersect_emit_batch(const uint32_t* grids, size_t grid_cells, const camd_cell_triple* triples_host, int ntriples,
+                                   camd_cell_triple* triples_dev, const long long* start, size_t ncols, long long* idx1,
+                                   long long* idx2, size_t capacity, unsigned long long* counts, void* stream);
+/* The per-view depth rows of ReconstructionExtrinsics (:225-241), [rows_total][4] float64 = [u, v, z, other view]:
+ * rows[row_offset + i] = [float64(uv[i][0]), float64(uv[i][1]), z[i], other_view] for i < n.  uv: [n][2] of uv_type.  */
+int camd_uvzi_pack(const void* uv, int uv_type, const double* z, size_t n, double other_view, double* rows, size_t rows_total,
+                   size_t row_offset, void* stream);
+/* *sum (device) = sum of rows[row_offset + i][column], i < n, of a [rows_total][columns] float64 array: the numerator
+ * of uvzis[:, 2].mean().  REDUCTION SHAPE: that of camd_vector_sum -- G = camd_column_sum_blocks(n) = clamp(ceil(n / 256),
+ * 1, 1024) workgroups, m = ceil(n / (256 G)) serial terms per thread, d = 18 tree levels, block partials in index
+ * order, no float atomics.  partials_ws: G doubles.  n >= 1.                                                       */
+int camd_column_sum_blocks(size_t n);
+int camd_column_sum(const double* rows, size_t rows_total, int columns, int column, size_t row_offset, size_t n,
+                    double* partials_ws, double* sum, void* stream);
+/* rows[row_offset + i][column] *= rate, i < n: one multiply per element (uvzis[:, 2] *= rate)                        */
+int camd_column_scale(double* rows, size_t rows_total, int columns, int column, size_t row_offset, size_t n, double rate,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
