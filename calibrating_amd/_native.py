@@ -34,6 +34,7 @@ INTER_LINEAR = 1
 INTER_LANCZOS4 = 4
 VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_arr2d / camd_uvzs_to_arr2d
 NEAREST_MAX_RADIUS = 32  # CAMD_NEAREST_MAX_RADIUS
+POINTS_PIXELS = 0x100  # CAMD_POINTS_PIXELS, or-ed into camd_undistort_points' out_type
 
 
 class SgbmParams(ctypes.Structure):
@@ -158,6 +159,10 @@ SIGNATURES = {
                                      c_int, c_int, c_int, c_void_p]),
     "camd_distort_index_map": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "camd_distort_depth": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "camd_undistort_points": (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                      c_void_p]),
+    "camd_project_points": (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

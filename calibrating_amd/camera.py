@@ -5,6 +5,8 @@ Only the record format of the reference's ``Cam`` is mirrored (``Cam.load`` / ``
 ``fx, fy, cx, cy``, optional ``D`` (default five zeros), ``xy`` = (width, height) (required), and the
 free-form keys ``name``, ``T_in_main_cam``, ``retval``.  Intrinsic calibration itself
 (cv2.calibrateCamera, boards, caches) is outside the stereo-depth hot path.
+Two point methods of the reference's ``Cam`` run on the GPU: ``undistort_points`` and ``project_points``
+(camera.py:275-287; csrc/points.hip), the step between a matcher's raw pixels and the epipolar path.
 """
 import copy
 
@@ -103,6 +105,24 @@ class Cam(dict):
         half_x, half_y = self.xy[0] / 2 / self.fx, self.xy[1] / 2 / self.fy  # tangents of the half angles
         deg = lambda t: float(np.degrees(2 * np.arctan(t)))  # noqa: E731
         return dict(fov=deg(np.hypot(half_x, half_y)), fovx=deg(half_x), fovy=deg(half_y))
+
+    def project_points(self, xyzs, T=None):
+        """Pixels of this camera's RAW image for 3-D points (camera.py:275-280: cv2.projectPoints with K and D), on the
+        GPU.  ``xyzs``: (n, 3) or (n, 1, 3), float32 or float64, ndarray or CUDA tensor -> (n, 2) of the same kind and
+        type.  ``T``: the 4x4 pose that takes the points into this camera's frame; None = they are in it already.  The
+        pose goes through cv2's two Rodrigues passes on the host (matrix -> vector -> matrix)."""
+        from . import geometry, imgproc
+        rvec, tvec = (np.zeros((3, 1)), np.zeros((3, 1))) if T is None else geometry.T_to_r_t(T)
+        return imgproc.project_points(xyzs, rvec, tvec, self.K, self.D)
+
+    def undistort_points(self, uvs, iters=5):
+        """Pixels of the RAW image -> pixels of the undistorted (pinhole K) image (camera.py:282-287), on the GPU: what a
+        matcher's or a flow's points need before ``EssentialMatrixStereo`` / ``ReconstructionExtrinsics`` see them.
+        ``uvs``: (n, 2) or (n, 1, 2), float32 or float64, ndarray or CUDA tensor -> (n, 2) float64 of the same kind
+        (float32 points come back as float64, as NumPy's promotion makes them in the reference).  ``iters``: rounds of
+        cv2.undistortPoints' iteration (cv2 runs 5); more for strong lenses."""
+        from . import imgproc
+        return imgproc.undistort_points(uvs, self.K, self.D, iters=iters, pixels=True)
 
     def project_cam2_depth(cam1, cam2, depth2, T=None, interpolation=1.5):
         """Depth image of ``cam2`` re-projected into this camera (camera.py:298-309), on the GPU.

@@ -248,6 +248,92 @@ def check_distortion(D):
     return D
 
 
+_POINT_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32}
+
+
+def _point_rows(a, width, what):
+    """The (n, width) rows of ``a`` = (n, width) or (n, 1, width), float32 / float64, ndarray or CUDA tensor -- checked
+    before the device is touched -- as (CUDA tensor whose rows are read in place, row stride in elements, was_numpy).
+    A tensor whose rows are the leading columns of wider rows (``uvzs[:, :2]``, ``xyzuv[:, :3]``) is not copied."""
+    import torch
+    was_np = isinstance(a, np.ndarray)
+    if not was_np and not isinstance(a, torch.Tensor):
+        raise TypeError("%s must be a NumPy array or a torch CUDA tensor, got %s" % (what, type(a).__name__))
+    if str(a.dtype).replace("torch.", "") not in _POINT_TYPES:
+        raise ValueError("%s must be float32 or float64 (cv2 takes nothing else), got %s" % (what, a.dtype))
+    if not was_np and not a.is_cuda:
+        raise ValueError("tensor inputs must live on the GPU (%s)" % what)
+    if a.ndim == 3 and a.shape[1] == 1:
+        a = a[:, 0]
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError("%s must be (n, %d) or (n, 1, %d), got %s" % (what, width, width, tuple(a.shape)))
+    if a.shape[0] >= 2 ** 31:
+        raise ValueError("%s: %d rows, the kernels take fewer than 2^31" % (what, a.shape[0]))
+    if was_np:
+        _native.require_device()
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda(), width, True
+    n = a.shape[0]
+    if a.stride(1) != 1 or (n > 1 and not width <= a.stride(0) < 2 ** 31):
+        a = a.contiguous()
+    return a, (int(a.stride(0)) if n > 1 else width), False
+
+
+def undistort_points(uvs, K, D=None, iters=5, pixels=False):
+    """cv2.undistortPoints(uvs, K, D)[:, 0] (camera.py:286; no R, no P) on the GPU: pixels of the raw image, (n, 2) or
+    (n, 1, 2), float32 or float64 -> the normalised pinhole coordinates (n, 2) in the same type.  ``iters`` (1 .. 100)
+    rounds of cv2's fixed-point iteration, 5 as in cv2, which tests no epsilon here.  NumPy in -> NumPy out; a CUDA
+    tensor -> a tensor on its device and the current stream, its rows read in place (no copy for ``uvzs[:, :2]``).
+    ``pixels=True``: the points go back to pixels of the undistorted camera in the same kernel, normalised * [fx, fy] +
+    [cx, cy] in float64 -> (n, 2) float64 whatever the input's type: the whole of ``Cam.undistort_points``."""
+    import torch
+    D = check_distortion(D)
+    if D.size not in (0, 4, 5, 8, 12, 14):
+        raise ValueError("%d distortion coefficients; cv2 takes 4, 5, 8, 12 or 14" % D.size)
+    if int(iters) != iters or not 1 <= iters <= 100:
+        raise ValueError("iters must be an integer in 1 .. 100, got %r" % (iters,))
+    K = np.ascontiguousarray(np.asarray(K, np.float64)[:3, :3]).reshape(9)
+    t, stride, was_np = _point_rows(uvs, 2, "uvs")
+    out = torch.empty((t.shape[0], 2), dtype=torch.float64 if pixels else t.dtype, device=t.device)
+    if t.shape[0]:
+        uv_type = _POINT_TYPES[str(t.dtype).replace("torch.", "")]
+        out_type = _native.VALUE_F64 | _native.POINTS_PIXELS if pixels else uv_type
+        with torch.cuda.device(t.device):
+            rc = _native.lib().camd_undistort_points(t.data_ptr(), uv_type, t.shape[0], stride, K.ctypes.data, D.ctypes.data if D.size else None, int(D.size),
+                                                     int(iters), out.data_ptr(), out_type, _native.current_stream())
+        _native.check(rc, "undistort_points")
+    return hostio.to_host(out) if was_np else out
+
+
+def project_points(xyzs, rvec_or_R, tvec, K, D=None):
+    """cv2.projectPoints(xyzs, rvec, tvec, K, D)[0][:, 0] (camera.py:280) on the GPU: points (n, 3) or (n, 1, 3), float32
+    or float64 -> their pixels (n, 2) in the same type.  ``rvec_or_R``: a Rodrigues vector (turned into its matrix on the
+    host, ``geometry.rodrigues``) or a 3x3 matrix; ``tvec``: 3 numbers.  NumPy in -> NumPy out; a CUDA tensor -> a tensor
+    on its device and the current stream, its rows read in place (no copy for ``xyzuv[:, :3]``)."""
+    import torch
+    from . import geometry
+    D = check_distortion(D)
+    if D.size not in (0, 4, 5, 8, 12, 14):
+        raise ValueError("%d distortion coefficients; cv2 takes 4, 5, 8, 12 or 14" % D.size)
+    R = np.asarray(rvec_or_R, np.float64)
+    if R.size not in (3, 9):
+        raise ValueError("rvec_or_R must be a Rodrigues vector or a 3x3 matrix, got shape %s" % (R.shape,))
+    R = np.ascontiguousarray(geometry.rodrigues(R) if R.size == 3 else R, np.float64).reshape(9)
+    tv = np.ascontiguousarray(tvec, np.float64).reshape(-1)
+    if tv.size != 3:
+        raise ValueError("tvec must hold 3 numbers, got %d" % tv.size)
+    K = np.ascontiguousarray(np.asarray(K, np.float64)[:3, :3]).reshape(9)
+    t, stride, was_np = _point_rows(xyzs, 3, "xyzs")
+    out = torch.empty((t.shape[0], 2), dtype=t.dtype, device=t.device)
+    if t.shape[0]:
+        with torch.cuda.device(t.device):
+            rc = _native.lib().camd_project_points(t.data_ptr(), _POINT_TYPES[str(t.dtype).replace("torch.", "")], t.shape[0],
+                                                   stride, R.ctypes.data, tv.ctypes.data, K.ctypes.data,
+                                                   D.ctypes.data if D.size else None, int(D.size), out.data_ptr(),
+                                                   _native.current_stream())
+        _native.check(rc, "project_points")
+    return hostio.to_host(out) if was_np else out
+
+
 def distort_index_map(K, D, size, device=None):
     """The per-rig part of ``Stereo.distort_depth`` (stereo_camera.py:440-462) built on the GPU: an int32 CUDA tensor
     (h, w) whose entry [y, x] is the row-major index of the FIRST pixel of the undistorted image that

@@ -458,6 +458,34 @@ int camd_column_sum(const double* rows, size_t rows_total, int columns, int colu
 int camd_column_scale(double* rows, size_t rows_total, int columns, int column, size_t row_offset, size_t n, double rate,
                       void* stream);
 
+/* ---- matched points between the raw image and the pinhole model (csrc/points.hip) ----------------------------
+ * What stands between a matcher, which sees the raw frames, and the epipolar path above, which takes pinhole pixels.
+ * One lane per point; rows are read in place: `*_stride` elements of `*_type` CAMD_VALUE_F64 / CAMD_VALUE_F32 from one
+ * row to the next, so (u, v) / (x, y, z) may be the leading columns of uvzs / uvzis / xyzuv rows.  n < 2^31; n == 0
+ * launches nothing.  out: [n][2] contiguous, aligned to one row (2 elements), not overlapping the input.  K: 9 host
+ * doubles; dist: ndist = 0, 4, 5, 8, 12 or 14 host doubles (k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tauX tauY); non-zero
+ * tauX / tauY are refused with CAMD_ERR_UNSUPPORTED.  float64 inside, no contraction, every division rounded once.
+ *
+ * replaces cv2.undistortPoints(uvs, K, D) of Cam.undistort_points (camera.py:286; epipolar_geometry.py:285-288, 327 begins
+ * with it), no R, no P: x = (u - cx) * (1 / fx), y alike; with ndist != 0, x0 = x and `iters` (1 .. 100; cv2 runs 5, it
+ * has no epsilon test here) rounds of
+ *   r2 = x*x + y*y;  icdist = (1 + ((k6*r2 + k5)*r2 + k4)*r2) / (1 + ((k3*r2 + k2)*r2 + k1)*r2)
+ *   icdist < 0: the point keeps its start value and is iterated no further
+ *   dX = 2*p1*x*y + p2*(r2 + 2*x*x) + s1*r2 + s2*r2*r2;  dY = p1*(r2 + 2*y*y) + 2*p2*x*y + s3*r2 + s4*r2*r2
+ *   x = (x0 - dX) * icdist;  y = (y0 - dY) * icdist
+ * The normalised point is rounded to uv_type -- cv2's hand-over -- and stored as out_type.  out_type |
+ * CAMD_POINTS_PIXELS: it goes back to pixels of the undistorted camera first, value * fx + cx and value * fy + cy in
+ * float64: the whole of camera.py:286-287 with out_type CAMD_VALUE_F64.                                            */
+enum { CAMD_POINTS_PIXELS = 0x100 };
+int camd_undistort_points(const void* uv, int uv_type, size_t n, int uv_stride, const double K[9], const double* dist,
+                          int ndist, int iters, void* out, int out_type, void* stream);
+/* replaces cv2.projectPoints(xyzs, rvec, tvec, K, D)[0] of Cam.project_points (camera.py:275-280), no Jacobians; R = the
+ * matrix of rvec (9 host doubles, row-major), t: 3 host doubles.  X = R0*x + R1*y + R2*z + t0 summed left to right, Y, Z
+ * alike; iz = Z ? 1 / Z : 1; the distortion polynomial of camd_distort_index_map on (X*iz, Y*iz); u = xd*fx + cx,
+ * v = yd*fy + cy, stored in xyz_type.                                                                               */
+int camd_project_points(const void* xyz, int xyz_type, size_t n, int xyz_stride, const double R[9], const double t[3],
+                        const double K[9], const double* dist, int ndist, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
