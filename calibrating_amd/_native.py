@@ -4,6 +4,12 @@ The library holds the hand-written gfx950 kernels; there is no CPU fallback.  ``
 ``RuntimeError`` when the shared object is missing (run ``python -c "import __graft_entry__ as g;
 g.build()"`` or ``make -C calibrating_amd/csrc``) and every compute entry point returns
 ``CAMD_ERR_NO_DEVICE`` -> ``RuntimeError`` when no MI355X is visible.
+
+Two ways into the library.  An entry point that queues work takes the stream as its last argument and is reached through
+``call(name, device, *args, what=label)``: it enters ``device``, appends THAT device's current stream and maps the status
+to an exception, so the device a launch runs on and the stream it is queued on cannot disagree.  The entry points without
+a stream (``*_blocks``, ``*_workspace_bytes``, ``*_grid``, ``*_host``, the SGBM handle's create / destroy / query /
+options / profile) are plain ``lib().fn(...)`` calls followed by ``check``.  ``_arrays`` holds the array side of a call.
 """
 import ctypes
 import os
@@ -218,3 +224,12 @@ def require_device():
 def current_stream():
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def call(name, device, *args, what=None):
+    """``lib().<name>(*args, stream)`` on ``device`` and on the current stream OF THAT DEVICE, then ``check`` under the
+    label ``what`` (default: the entry point's name).  For every entry point whose last parameter is the stream."""
+    import torch
+    with torch.cuda.device(device):
+        rc = getattr(lib(), name)(*args, current_stream())
+    check(rc, name if what is None else what)

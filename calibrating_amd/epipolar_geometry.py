@@ -16,34 +16,35 @@ raise ``ValueError``.
 """
 import numpy as np
 
-from . import _native, geometry, hostio, sparse
-from .sparse import _check_array, _dev, _dtype_name, _is_np, matched_uvs_to_zs  # noqa: F401  (matched_uvs_to_zs: re-export)
+from . import _native, geometry, hostio
+from ._arrays import FLOAT_TYPES, Kinv9, check_array, dtype_name, is_np, mat, to_caller, to_device
+from ._native import call
+from .sparse import matched_uvs_to_zs  # noqa: F401  (also a re-export)
 from .stereo_camera import Stereo
 
 MAX_CELLS = 1 << 28  # the most one cell window may hold: two uint32 grids of it are 2 GiB
 # the most cells all grids of one pass of matching_uvs_in_one_img_batch hold together (uint32 each: 512 MiB); beyond it
 # the pairs are worked off in several passes
 BATCH_MAX_CELLS = 1 << 27
-_UV_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32}
 
 
 def _float_rows(a, what, other=None):
     """(n, 2) rows as they take part in NumPy's arithmetic: float32 stays, everything else becomes float64."""
-    _check_array(a, what)
+    check_array(a, what)
     if len(a.shape) != 2 or a.shape[1] != 2:
         raise ValueError("%s must be (n, 2), got %s" % (what, tuple(a.shape)))
     if int(a.shape[0]) >= 2 ** 32 - 1:
         raise ValueError("%s: %d rows do not fit the 32-bit row index" % (what, a.shape[0]))
-    if other is not None and _is_np(a) != _is_np(other):
+    if other is not None and is_np(a) != is_np(other):
         raise TypeError("%s: pass both point sets as ndarrays or both as CUDA tensors" % what)
-    return "float32" if _dtype_name(a) == "float32" else "float64"
+    return "float32" if dtype_name(a) == "float32" else "float64"
 
 
 def _min_max(a):
     """[min u, min v, max u, max v] as float64 on the host.  Tensors are reduced on the device and four numbers read back.
     ndarrays are reduced on the host BEFORE they are uploaded: non-finite input and an oversized window are then refused
     without touching the device (one pass over host memory that a device-resident caller does not pay)."""
-    if _is_np(a):
+    if is_np(a):
         return np.concatenate([a.min(0), a.max(0)]).astype(np.float64)
     import torch
     return torch.cat([a.amin(0), a.amax(0)]).to(torch.float64).cpu().numpy()
@@ -67,10 +68,10 @@ def _window(bounds, what, hint):
 def uvs_to_xyz_noramls(uvs, K):
     """Rays (x, y, 1) of pixels: ``(u, v, 1) @ inv(K).T`` (epipolar_geometry.py:84-85; the spelling is the reference's)."""
     Kinv_T = np.linalg.inv(np.asarray(K)).T
-    if _is_np(uvs):
+    if is_np(uvs):
         return np.pad(uvs, ((0, 0), (0, 1)), constant_values=1) @ Kinv_T
     import torch
-    _check_array(uvs, "uvs")
+    check_array(uvs, "uvs")
     ones = torch.ones((uvs.shape[0], 1), dtype=uvs.dtype, device=uvs.device)
     return torch.cat([uvs, ones], 1).to(torch.float64) @ torch.from_numpy(np.ascontiguousarray(Kinv_T, np.float64)).to(uvs.device)
 
@@ -116,7 +117,7 @@ def decompose_essential_matrix(E):
 def _host_subsample(uvs, n):
     """Every ``n // 100``-th row (all of them up to 100) on the host: the only rows the essential matrix reads."""
     rows = uvs[:: n // 100] if n > 100 else uvs
-    return rows if _is_np(rows) else rows.cpu().numpy()
+    return rows if is_np(rows) else rows.cpu().numpy()
 
 
 def _pose_candidates(uvs1, uvs2, K1, K2, baseline):
@@ -133,33 +134,29 @@ def _pose_candidates(uvs1, uvs2, K1, K2, baseline):
 def _candidate_means(a, b, K1, K2, Ts):
     """(4, 2) mean zs1 / zs2 of the matches under each candidate: one pass over device-resident (n, 2) float64 rows."""
     import torch
-    lib, n = _native.lib(), int(a.shape[0])
-    Kinv = [np.ascontiguousarray(np.linalg.inv(K)).reshape(9) for K in (K1, K2)]
-    T4 = np.ascontiguousarray(np.stack(Ts), np.float64).reshape(64)
-    with torch.cuda.device(a.device):
-        partials = torch.empty(lib.camd_epipolar_sums_blocks(n) * 8, dtype=torch.float64, device=a.device)
-        sums = torch.empty(8, dtype=torch.float64, device=a.device)
-        rc = lib.camd_epipolar_sums(a.data_ptr(), b.data_ptr(), n, Kinv[0].ctypes.data, Kinv[1].ctypes.data, T4.ctypes.data,
-                                    partials.data_ptr(), sums.data_ptr(), _native.current_stream())
-    _native.check(rc, "EssentialMatrixStereo")
+    n = int(a.shape[0])
+    Kinv = [Kinv9(K) for K in (K1, K2)]
+    T4 = mat(np.stack(Ts), 64)
+    partials = torch.empty(_native.lib().camd_epipolar_sums_blocks(n) * 8, dtype=torch.float64, device=a.device)
+    sums = torch.empty(8, dtype=torch.float64, device=a.device)
+    call("camd_epipolar_sums", a.device, a.data_ptr(), b.data_ptr(), n, Kinv[0].ctypes.data, Kinv[1].ctypes.data, T4.ctypes.data,
+         partials.data_ptr(), sums.data_ptr(), what="EssentialMatrixStereo")
     return sums.cpu().numpy().reshape(4, 2) / n
 
 
 def _mean(z, idx=None, what="mean"):
     """``z.mean()`` / ``z[idx].mean()`` of a float64 vector through the fixed-order reduction (one number read back)."""
     import torch
-    zd = _dev(z, dtype="float64")
+    zd = to_device(z, dtype="float64", cast=True)
     lib = _native.lib()
     n = int(zd.shape[0]) if idx is None else int(idx.shape[0])
     if n == 0:
         raise ValueError("%s of no elements" % what)
-    with torch.cuda.device(zd.device):
-        i = None if idx is None else _dev(idx, zd.device, dtype="int64")
-        partials = torch.empty(lib.camd_vector_sum_blocks(n) * 2, dtype=torch.float64, device=zd.device)
-        sums = torch.empty(2, dtype=torch.float64, device=zd.device)
-        rc = lib.camd_vector_sum(zd.data_ptr(), int(zd.shape[0]), None if i is None else i.data_ptr(), n, partials.data_ptr(),
-                                 sums.data_ptr(), _native.current_stream())
-    _native.check(rc, what)
+    i = None if idx is None else to_device(idx, dtype="int64", cast=True, device=zd.device)
+    partials = torch.empty(lib.camd_vector_sum_blocks(n) * 2, dtype=torch.float64, device=zd.device)
+    sums = torch.empty(2, dtype=torch.float64, device=zd.device)
+    call("camd_vector_sum", zd.device, zd.data_ptr(), int(zd.shape[0]), None if i is None else i.data_ptr(), n,
+         partials.data_ptr(), sums.data_ptr(), what=what)
     total, bad = sums.cpu().numpy()
     if bad:
         raise IndexError("%s: %d indices lie outside the %d depths" % (what, int(bad), int(zd.shape[0])))
@@ -172,39 +169,37 @@ def filter_overlap_uvs(uvs1, uvs2):
     ``(uvs1[mask], uvs2[mask])``, order and dtype kept."""
     import torch
     name = _float_rows(uvs1, "uvs1")
-    if _float_rows(uvs2, "uvs2", uvs1) != name or _dtype_name(uvs1) not in _UV_TYPES or _dtype_name(uvs2) != _dtype_name(uvs1):
-        raise ValueError("uvs1, uvs2 must both be float64 or both float32, got %s and %s" % (_dtype_name(uvs1), _dtype_name(uvs2)))
+    if _float_rows(uvs2, "uvs2", uvs1) != name or dtype_name(uvs1) not in FLOAT_TYPES or dtype_name(uvs2) != dtype_name(uvs1):
+        raise ValueError("uvs1, uvs2 must both be float64 or both float32, got %s and %s" % (dtype_name(uvs1), dtype_name(uvs2)))
     n = int(uvs1.shape[0])
     if int(uvs2.shape[0]) != n:
         raise ValueError("uvs1, uvs2 must have the same number of rows, got %d and %d" % (n, uvs2.shape[0]))
-    was_np = _is_np(uvs1)
+    was_np = is_np(uvs1)
     if n == 0:
         return (uvs1.copy(), uvs2.copy()) if was_np else (uvs1.clone(), uvs2.clone())
     cu0, cv0, cw, ch = _window([_min_max(uvs1), _min_max(uvs2)], "filter_overlap_uvs", "")
-    a = _dev(uvs1)
-    b = _dev(uvs2, a.device)
-    lib, st, t = _native.lib(), _native.current_stream, _UV_TYPES[name]
-    with torch.cuda.device(a.device):
-        pop = torch.empty((2, cw * ch), dtype=torch.int32, device=a.device)
-        counters = torch.zeros(3, dtype=torch.int64, device=a.device)  # kept rows, rows outside the window of set 1 / 2
-        for k, uv in enumerate((a, b)):
-            _native.check(lib.camd_cell_population(uv.data_ptr(), t, n, 2, cu0, cv0, cw, ch, pop[k].data_ptr(),
-                                                   counters[1 + k:].data_ptr(), st()), "filter_overlap_uvs")
-        blocks = lib.camd_overlap_blocks(n)
-        keep = torch.empty(n, dtype=torch.uint8, device=a.device)
-        blockcount = torch.empty(blocks, dtype=torch.int32, device=a.device)
-        _native.check(lib.camd_overlap_keep(a.data_ptr(), b.data_ptr(), t, n, 2, cu0, cv0, cw, ch, pop[0].data_ptr(),
-                                            pop[1].data_ptr(), keep.data_ptr(), blockcount.data_ptr(), st()), "filter_overlap_uvs")
-        start = torch.zeros(blocks + 1, dtype=torch.int64, device=a.device)
-        torch.cumsum(blockcount, 0, dtype=torch.int64, out=start[1:])  # the exclusive scan between count and emit
-        out = torch.empty((2, n, 2), dtype=a.dtype, device=a.device)
-        _native.check(lib.camd_overlap_emit(a.data_ptr(), b.data_ptr(), t, n, 2, keep.data_ptr(), start.data_ptr(),
-                                            out[0].data_ptr(), out[1].data_ptr(), n, counters.data_ptr(), st()), "filter_overlap_uvs")
+    a = to_device(uvs1)
+    b = to_device(uvs2, device=a.device)
+    dev, t, who = a.device, FLOAT_TYPES[name], "filter_overlap_uvs"
+    pop = torch.empty((2, cw * ch), dtype=torch.int32, device=dev)
+    counters = torch.zeros(3, dtype=torch.int64, device=dev)  # kept rows, rows outside the window of set 1 / 2
+    for k, uv in enumerate((a, b)):
+        call("camd_cell_population", dev, uv.data_ptr(), t, n, 2, cu0, cv0, cw, ch, pop[k].data_ptr(),
+             counters[1 + k:].data_ptr(), what=who)
+    blocks = _native.lib().camd_overlap_blocks(n)
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    blockcount = torch.empty(blocks, dtype=torch.int32, device=dev)
+    call("camd_overlap_keep", dev, a.data_ptr(), b.data_ptr(), t, n, 2, cu0, cv0, cw, ch, pop[0].data_ptr(), pop[1].data_ptr(),
+         keep.data_ptr(), blockcount.data_ptr(), what=who)
+    start = torch.zeros(blocks + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(blockcount, 0, dtype=torch.int64, out=start[1:])  # the exclusive scan between count and emit
+    out = torch.empty((2, n, 2), dtype=a.dtype, device=dev)
+    call("camd_overlap_emit", dev, a.data_ptr(), b.data_ptr(), t, n, 2, keep.data_ptr(), start.data_ptr(), out[0].data_ptr(),
+         out[1].data_ptr(), n, counters.data_ptr(), what=who)
     count, out1, out2 = (int(v) for v in counters.cpu().numpy())  # synchronises: the output length is data dependent
     if out1 or out2:
         raise RuntimeError("filter_overlap_uvs: %d rows fell outside the window sized from the data" % (out1 + out2))
-    res = out[0, :count], out[1, :count]
-    return tuple(hostio.to_host_list(*res)) if was_np else res
+    return to_caller((out[0, :count], out[1, :count]), was_np)
 
 
 # ---- matching_uvs_in_one_img -------------------------------------------------------------------------------------------
@@ -230,35 +225,29 @@ def matching_uvs_in_one_img(uvs1, uvs2, MAX_DISTANCE=1, MIN_MATCHED_PIXELS=10, p
     with np.errstate(over="ignore", invalid="ignore"):
         bounds = [_min_max(uv).astype(nm) / np.dtype(nm).type(d) for uv, nm in zip((uvs1, uvs2), names)]
     cu0, cv0, cw, ch = _window(bounds, "matching_uvs_in_one_img", hint)
-    was_np = _is_np(uvs1)
-    a = _dev(uvs1, dtype=names[0])
-    b = _dev(uvs2, a.device, dtype=names[1])
-    lib, st = _native.lib(), _native.current_stream
-    with torch.cuda.device(a.device):
-        first = torch.empty((2, cw * ch), dtype=torch.int32, device=a.device)
-        counters = torch.zeros(3, dtype=torch.int64, device=a.device)  # shared cells, rows outside the window of set 1 / 2
-        for k, (uv, nm) in enumerate(zip((a, b), names)):
-            _native.check(lib.camd_cell_first_index(uv.data_ptr(), _UV_TYPES[nm], int(uv.shape[0]), 2, d, cu0, cv0, cw, ch,
-                                                    first[k].data_ptr(), counters[1 + k:].data_ptr(), st()),
-                          "matching_uvs_in_one_img")
-        colcount = torch.empty(cw, dtype=torch.int32, device=a.device)
-        _native.check(lib.camd_cell_intersect_count(first[0].data_ptr(), first[1].data_ptr(), cw, ch, colcount.data_ptr(), st()),
-                      "matching_uvs_in_one_img")
-        start = torch.zeros(cw + 1, dtype=torch.int64, device=a.device)
-        torch.cumsum(colcount, 0, dtype=torch.int64, out=start[1:])  # the exclusive scan between count and emit
-        cap = min(n1, n2)
-        idx = torch.empty((2, cap), dtype=torch.int64, device=a.device)
-        _native.check(lib.camd_cell_intersect_emit(first[0].data_ptr(), first[1].data_ptr(), cw, ch, start.data_ptr(),
-                                                   idx[0].data_ptr(), idx[1].data_ptr(), cap, counters.data_ptr(), st()),
-                      "matching_uvs_in_one_img")
+    was_np = is_np(uvs1)
+    a = to_device(uvs1, dtype=names[0], cast=True)
+    b = to_device(uvs2, dtype=names[1], cast=True, device=a.device)
+    dev, who = a.device, "matching_uvs_in_one_img"
+    first = torch.empty((2, cw * ch), dtype=torch.int32, device=dev)
+    counters = torch.zeros(3, dtype=torch.int64, device=dev)  # shared cells, rows outside the window of set 1 / 2
+    for k, (uv, nm) in enumerate(zip((a, b), names)):
+        call("camd_cell_first_index", dev, uv.data_ptr(), FLOAT_TYPES[nm], int(uv.shape[0]), 2, d, cu0, cv0, cw, ch,
+             first[k].data_ptr(), counters[1 + k:].data_ptr(), what=who)
+    colcount = torch.empty(cw, dtype=torch.int32, device=dev)
+    call("camd_cell_intersect_count", dev, first[0].data_ptr(), first[1].data_ptr(), cw, ch, colcount.data_ptr(), what=who)
+    start = torch.zeros(cw + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(colcount, 0, dtype=torch.int64, out=start[1:])  # the exclusive scan between count and emit
+    cap = min(n1, n2)
+    idx = torch.empty((2, cap), dtype=torch.int64, device=dev)
+    call("camd_cell_intersect_emit", dev, first[0].data_ptr(), first[1].data_ptr(), cw, ch, start.data_ptr(), idx[0].data_ptr(),
+         idx[1].data_ptr(), cap, counters.data_ptr(), what=who)
     count, out1, out2 = (int(v) for v in counters.cpu().numpy())  # synchronises: the output length is data dependent
     if out1 or out2:
         raise RuntimeError("matching_uvs_in_one_img: %d rows fell outside the window sized from the data" % (out1 + out2))
     if count < MIN_MATCHED_PIXELS:
         return {}
-    i1, i2 = idx[0, :count], idx[1, :count]
-    if was_np:
-        i1, i2 = hostio.to_host_list(i1, i2)
+    i1, i2 = to_caller((idx[0, :count], idx[1, :count]), was_np)
     return dict(uv_match_idx1=i1, uv_match_idx2=i2)
 
 
@@ -267,22 +256,20 @@ def _batch_bounds(sets):
     read-back (camd_uv_bounds_batch leaves one row per workgroup; min / max commute, so finishing on the host is exact)."""
     import torch
     out = np.empty((len(sets), 4), np.float64)
-    dev = [k for k, s in enumerate(sets) if not _is_np(s)]
+    dev = [k for k, s in enumerate(sets) if not is_np(s)]
     for k, s in enumerate(sets):
-        if _is_np(s):
+        if is_np(s):
             out[k] = _min_max(s)
     if dev:
-        lib = _native.lib()
-        B = lib.camd_uv_bounds_blocks()
+        B = _native.lib().camd_uv_bounds_blocks()
         table = (_native.CellSet * len(dev))()
         for e, k in zip(table, dev):
-            e.uv, e.n, e.uv_type = sets[k].data_ptr(), int(sets[k].shape[0]), _UV_TYPES[_dtype_name(sets[k])]
+            e.uv, e.n, e.uv_type = sets[k].data_ptr(), int(sets[k].shape[0]), FLOAT_TYPES[dtype_name(sets[k])]
         device = sets[dev[0]].device
-        with torch.cuda.device(device):
-            table_dev = torch.empty(len(dev) * 48, dtype=torch.uint8, device=device)
-            parts = torch.empty((len(dev), B, 4), dtype=torch.float64, device=device)
-            _native.check(lib.camd_uv_bounds_batch(table, len(dev), table_dev.data_ptr(), parts.data_ptr(), _native.current_stream()),
-                          "matching_uvs_in_one_img_batch")
+        table_dev = torch.empty(len(dev) * 48, dtype=torch.uint8, device=device)
+        parts = torch.empty((len(dev), B, 4), dtype=torch.float64, device=device)
+        call("camd_uv_bounds_batch", device, table, len(dev), table_dev.data_ptr(), parts.data_ptr(),
+             what="matching_uvs_in_one_img_batch")
         parts = parts.cpu().numpy()  # the one read-back of all bounds
         out[dev, :2], out[dev, 2:] = parts[:, :, :2].min(1), parts[:, :, 2:].max(1)
     return out
@@ -311,12 +298,12 @@ def matching_uvs_in_one_img_batch(pairs_of_sets, MAX_DISTANCE=1, MIN_MATCHED_PIX
                     raise ValueError("matching_uvs_in_one_img needs at least one point in each set")
                 slot[id(uv)] = len(sets)
                 sets.append(uv)
-    was_np = _is_np(sets[0])
+    was_np = is_np(sets[0])
     names = [(np.zeros(1, _float_rows(s, "a point set")) / MAX_DISTANCE).dtype.name for s in sets]
-    devs = [_dev(sets[0], dtype=names[0])]
-    devs += [_dev(s, devs[0].device, dtype=nm) for s, nm in zip(sets[1:], names[1:])]
+    devs = [to_device(sets[0], dtype=names[0], cast=True)]
+    devs += [to_device(s, dtype=nm, cast=True, device=devs[0].device) for s, nm in zip(sets[1:], names[1:])]
     device = devs[0].device
-    raw = _batch_bounds([s if _is_np(s) else t for s, t in zip(sets, devs)])
+    raw = _batch_bounds([s if is_np(s) else t for s, t in zip(sets, devs)])
     with np.errstate(over="ignore", invalid="ignore"):
         bounds = [raw[k].astype(nm) / np.dtype(nm).type(d) for k, nm in enumerate(names)]
     # sets that a pair links share a window
@@ -349,45 +336,43 @@ def matching_uvs_in_one_img_batch(pairs_of_sets, MAX_DISTANCE=1, MIN_MATCHED_PIX
         passes[-1].append(p)
         members |= need
         used += extra
-    lib, st = _native.lib(), _native.current_stream
     done, keep = [], []  # per pass (pair numbers, idx, counts, outside); host tables stay alive until the read-back
-    with torch.cuda.device(device):
-        for chunk in passes:
-            mine = sorted({slot[id(uv)] for p in chunk for uv in pairs[p]})
-            goff, total = {}, 0
-            stable = (_native.CellSet * len(mine))()
-            for e, k in zip(stable, mine):
-                cu0, cv0, cw, ch = windows[find(k)]
-                e.uv, e.n, e.grid_offset, e.uv_type = devs[k].data_ptr(), int(devs[k].shape[0]), total, _UV_TYPES[names[k]]
-                e.cu0, e.cv0, e.cells_w, e.cells_h = cu0, cv0, cw, ch
-                goff[k] = total
-                total += cw * ch
-            ttable = (_native.CellTriple * len(chunk))()
-            ncols = capacity = 0
-            for e, p in zip(ttable, chunk):
-                k1, k2 = (slot[id(uv)] for uv in pairs[p])
-                _, _, cw, ch = windows[find(k1)]
-                e.grid_offset1, e.grid_offset2, e.column_offset, e.cells_w, e.cells_h = goff[k1], goff[k2], ncols, cw, ch
-                ncols += cw
-                capacity += min(int(devs[k1].shape[0]), int(devs[k2].shape[0]), cw * ch)  # a cell is shared at most once
-            grids = torch.empty(total, dtype=torch.int32, device=device)
-            tables_dev = torch.empty(len(mine) * 48 + len(chunk) * 32, dtype=torch.uint8, device=device)
-            sd, td = tables_dev.data_ptr(), tables_dev.data_ptr() + len(mine) * 48
-            outside = torch.empty(1, dtype=torch.int64, device=device)
-            who = "matching_uvs_in_one_img_batch"
-            _native.check(lib.camd_cell_first_index_batch(stable, len(mine), sd, d, grids.data_ptr(), total, outside.data_ptr(), st()), who)
-            colcount = torch.empty(ncols, dtype=torch.int32, device=device)
-            _native.check(lib.camd_cell_intersect_count_batch(grids.data_ptr(), total, ttable, len(chunk), td, colcount.data_ptr(),
-                                                              ncols, st()), who)
-            start = torch.zeros(ncols + 1, dtype=torch.int64, device=device)
-            torch.cumsum(colcount, 0, dtype=torch.int64, out=start[1:])  # ONE exclusive scan over the columns of all triples
-            idx = torch.empty((2, capacity), dtype=torch.int64, device=device)
-            counts = torch.empty(len(chunk), dtype=torch.int64, device=device)
-            _native.check(lib.camd_cell_intersect_emit_batch(grids.data_ptr(), total, ttable, len(chunk), td, start.data_ptr(), ncols,
-                                                             idx[0].data_ptr(), idx[1].data_ptr(), capacity, counts.data_ptr(), st()), who)
-            done.append((chunk, idx, counts, outside))
-            keep.append((stable, ttable))
-        numbers = torch.cat([t for _, _, c, o in done for t in (c, o)]).cpu().numpy()  # synchronises: the one read-back of all counts
+    who = "matching_uvs_in_one_img_batch"
+    for chunk in passes:
+        mine = sorted({slot[id(uv)] for p in chunk for uv in pairs[p]})
+        goff, total = {}, 0
+        stable = (_native.CellSet * len(mine))()
+        for e, k in zip(stable, mine):
+            cu0, cv0, cw, ch = windows[find(k)]
+            e.uv, e.n, e.grid_offset, e.uv_type = devs[k].data_ptr(), int(devs[k].shape[0]), total, FLOAT_TYPES[names[k]]
+            e.cu0, e.cv0, e.cells_w, e.cells_h = cu0, cv0, cw, ch
+            goff[k] = total
+            total += cw * ch
+        ttable = (_native.CellTriple * len(chunk))()
+        ncols = capacity = 0
+        for e, p in zip(ttable, chunk):
+            k1, k2 = (slot[id(uv)] for uv in pairs[p])
+            _, _, cw, ch = windows[find(k1)]
+            e.grid_offset1, e.grid_offset2, e.column_offset, e.cells_w, e.cells_h = goff[k1], goff[k2], ncols, cw, ch
+            ncols += cw
+            capacity += min(int(devs[k1].shape[0]), int(devs[k2].shape[0]), cw * ch)  # a cell is shared at most once
+        grids = torch.empty(total, dtype=torch.int32, device=device)
+        tables_dev = torch.empty(len(mine) * 48 + len(chunk) * 32, dtype=torch.uint8, device=device)
+        sd, td = tables_dev.data_ptr(), tables_dev.data_ptr() + len(mine) * 48
+        outside = torch.empty(1, dtype=torch.int64, device=device)
+        call("camd_cell_first_index_batch", device, stable, len(mine), sd, d, grids.data_ptr(), total, outside.data_ptr(), what=who)
+        colcount = torch.empty(ncols, dtype=torch.int32, device=device)
+        call("camd_cell_intersect_count_batch", device, grids.data_ptr(), total, ttable, len(chunk), td, colcount.data_ptr(), ncols,
+             what=who)
+        start = torch.zeros(ncols + 1, dtype=torch.int64, device=device)
+        torch.cumsum(colcount, 0, dtype=torch.int64, out=start[1:])  # ONE exclusive scan over the columns of all triples
+        idx = torch.empty((2, capacity), dtype=torch.int64, device=device)
+        counts = torch.empty(len(chunk), dtype=torch.int64, device=device)
+        call("camd_cell_intersect_emit_batch", device, grids.data_ptr(), total, ttable, len(chunk), td, start.data_ptr(), ncols,
+             idx[0].data_ptr(), idx[1].data_ptr(), capacity, counts.data_ptr(), what=who)
+        done.append((chunk, idx, counts, outside))
+        keep.append((stable, ttable))
+    numbers = torch.cat([t for _, _, c, o in done for t in (c, o)]).cpu().numpy()  # synchronises: the one read-back of all counts
     del keep
     results, at = [None] * len(pairs), 0
     for chunk, idx, _, _ in done:
@@ -411,12 +396,12 @@ def matching_uvs_in_one_img_batch(pairs_of_sets, MAX_DISTANCE=1, MIN_MATCHED_PIX
 
 # ---- flow ------------------------------------------------------------------------------------------------------------
 def _flow(flow, what, channel_axis):
-    _check_array(flow, what)
+    check_array(flow, what)
     if len(flow.shape) != 3 or flow.shape[channel_axis] != 2:
         want = "(h, w, 2)" if channel_axis == 2 else "(2, h, w)"
         raise ValueError("%s must be %s, got %s" % (what, want, tuple(flow.shape)))
-    name = _dtype_name(flow)
-    if name not in _UV_TYPES:
+    name = dtype_name(flow)
+    if name not in FLOAT_TYPES:
         raise ValueError("%s must be float32 or float64, got %s" % (what, name))
     hw = [int(s) for i, s in enumerate(flow.shape) if i != channel_axis]
     if min(hw) <= 0:
@@ -428,13 +413,10 @@ def flow_abs_to_normal(flow_abs):
     """(h, w, 2) flow in pixels -> float32 (2, h, w) in image widths / heights (flow_utils.py:83-86)."""
     import torch
     name, h, w = _flow(flow_abs, "flow_abs", 2)
-    was_np = _is_np(flow_abs)
-    f = _dev(flow_abs)
-    with torch.cuda.device(f.device):
-        out = torch.empty((2, h, w), dtype=torch.float32, device=f.device)
-        rc = _native.lib().camd_flow_abs_to_normal(f.data_ptr(), _UV_TYPES[name], w, h, out.data_ptr(), _native.current_stream())
-    _native.check(rc, "flow_abs_to_normal")
-    return hostio.to_host(out) if was_np else out
+    f = to_device(flow_abs)
+    out = torch.empty((2, h, w), dtype=torch.float32, device=f.device)
+    call("camd_flow_abs_to_normal", f.device, f.data_ptr(), FLOAT_TYPES[name], w, h, out.data_ptr(), what="flow_abs_to_normal")
+    return to_caller(out, is_np(flow_abs))
 
 
 def flow_normal_to_abs(flow, hw=None):
@@ -443,14 +425,11 @@ def flow_normal_to_abs(flow, hw=None):
     import torch
     name, h, w = _flow(flow, "flow", 0)
     th, tw = (h, w) if hw is None else hw
-    was_np = _is_np(flow)
-    f = _dev(flow)
-    with torch.cuda.device(f.device):
-        out = torch.empty((h, w, 2), dtype=torch.float64, device=f.device)
-        rc = _native.lib().camd_flow_normal_to_abs(f.data_ptr(), _UV_TYPES[name], w, h, float(tw), float(th), out.data_ptr(),
-                                                   _native.current_stream())
-    _native.check(rc, "flow_normal_to_abs")
-    return hostio.to_host(out) if was_np else out
+    f = to_device(flow)
+    out = torch.empty((h, w, 2), dtype=torch.float64, device=f.device)
+    call("camd_flow_normal_to_abs", f.device, f.data_ptr(), FLOAT_TYPES[name], w, h, float(tw), float(th), out.data_ptr(),
+         what="flow_normal_to_abs")
+    return to_caller(out, is_np(flow))
 
 
 def flow_to_matched_uvs(flow_abs, mask):
@@ -458,27 +437,22 @@ def flow_to_matched_uvs(flow_abs, mask):
     order and where the flow takes them -- one direction of ``build_set2ds_by_flowds`` (:276-282)."""
     import torch
     name, h, w = _flow(flow_abs, "flow_abs", 2)
-    _check_array(mask, "mask")
+    check_array(mask, "mask")
     if tuple(mask.shape) != (h, w):
         raise ValueError("mask %s does not match flow_abs %s" % (tuple(mask.shape), (h, w)))
-    was_np = _is_np(flow_abs)
-    f = _dev(flow_abs)
-    m = _dev(np.asarray(mask != 0) if _is_np(mask) else (mask != 0), f.device).view(torch.uint8)
-    lib = _native.lib()
-    with torch.cuda.device(f.device):
-        rows = torch.empty((2, h * w, 2), dtype=torch.float64, device=f.device)
-        count = torch.zeros(1, dtype=torch.int64, device=f.device)
-        ws = torch.empty(lib.camd_arr2d_mask_workspace_bytes(h), dtype=torch.uint8, device=f.device)
-        rc = lib.camd_flow_to_matched_uvs(f.data_ptr(), _UV_TYPES[name], m.data_ptr(), w, h, rows[0].data_ptr(), rows[1].data_ptr(),
-                                          h * w, count.data_ptr(), ws.data_ptr(), _native.current_stream())
-    _native.check(rc, "flow_to_matched_uvs")
+    f = to_device(flow_abs)
+    m = to_device(np.asarray(mask != 0) if is_np(mask) else (mask != 0), device=f.device).view(torch.uint8)
+    rows = torch.empty((2, h * w, 2), dtype=torch.float64, device=f.device)
+    count = torch.zeros(1, dtype=torch.int64, device=f.device)
+    ws = torch.empty(_native.lib().camd_arr2d_mask_workspace_bytes(h), dtype=torch.uint8, device=f.device)
+    call("camd_flow_to_matched_uvs", f.device, f.data_ptr(), FLOAT_TYPES[name], m.data_ptr(), w, h, rows[0].data_ptr(),
+         rows[1].data_ptr(), h * w, count.data_ptr(), ws.data_ptr(), what="flow_to_matched_uvs")
     n = int(count.item())  # synchronises: the output length is data dependent
-    res = rows[0, :n], rows[1, :n]
-    return tuple(hostio.to_host_list(*res)) if was_np else res
+    return to_caller((rows[0, :n], rows[1, :n]), is_np(flow_abs))
 
 
 def _cat(parts):
-    if _is_np(parts[0]):
+    if is_np(parts[0]):
         return np.concatenate(parts)
     import torch
     return torch.cat(parts)
@@ -520,7 +494,6 @@ class EssentialMatrixStereo(Stereo):
     caller's kind), ``E`` (3x3 ndarray) and ``z1, z2`` (the winner's mean depths, floats)."""
 
     def __init__(self, uvs1=None, uvs2=None, K1=None, K2=None, baseline=1, xy1=None, xy2=None, name1="cam1", name2="cam2"):
-        import torch
         if uvs1 is None:  # (type(self)() as Stereo.copy makes it)
             super().__init__()
             return
@@ -540,16 +513,14 @@ class EssentialMatrixStereo(Stereo):
         if K1.shape != (3, 3) or K2.shape != (3, 3):
             raise ValueError("K1, K2 must be 3x3")
         E, Ts = _pose_candidates(uvs1, uvs2, K1, K2, baseline)
-        a = _dev(uvs1, dtype="float64")
-        b = _dev(uvs2, a.device, dtype="float64")
+        a = to_device(uvs1, dtype="float64", cast=True)
+        b = to_device(uvs2, dtype="float64", cast=True, device=a.device)
         means = _candidate_means(a, b, K1, K2, Ts)
         # the first candidate with both means positive; if none is, the last one, as the reference's loop leaves it
         self.candidate = next((c for c in range(4) if means[c, 0] > 0 and means[c, 1] > 0), 3)
         T = Ts[self.candidate]
-        with torch.cuda.device(a.device):
-            zs = matched_uvs_to_zs(a, b, K1, K2, T)
-        if _is_np(uvs1):
-            zs["zs1"], zs["zs2"] = hostio.to_host_list(zs["zs1"], zs["zs2"])
+        zs = matched_uvs_to_zs(a, b, K1, K2, T)
+        zs["zs1"], zs["zs2"] = to_caller((zs["zs1"], zs["zs2"]), is_np(uvs1))
         super().__init__()
         self.load(dict(R=T[:3, :3], t=T[:3, 3], cam1=dict(xy=list(xy1), K=K1, name=str(name1)),
                        cam2=dict(xy=list(xy2), K=K2, name=str(name2))))

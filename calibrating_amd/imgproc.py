@@ -7,24 +7,9 @@ import ctypes
 
 import numpy as np
 
-from . import _native, hostio
-from ._native import INTER_LANCZOS4, INTER_LINEAR, INTER_NEAREST
-
-
-def _to_dev(a, dtype=None):
-    """(tensor on GPU, was_numpy)"""
-    import torch
-    if isinstance(a, np.ndarray):
-        _native.require_device()
-        t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-        was_np = True
-    else:
-        t, was_np = a, False
-    if not t.is_cuda:
-        raise ValueError("tensor inputs must live on the GPU")
-    if dtype is not None and t.dtype != dtype:
-        raise ValueError("expected dtype %s, got %s" % (dtype, t.dtype))
-    return t.contiguous(), was_np
+from . import _arrays, _native
+from ._arrays import DIST_COUNTS, FLOAT_TYPES, K9, check_array, dist, dtype_name, is_np, mat, to_caller, to_device
+from ._native import INTER_LANCZOS4, INTER_LINEAR, INTER_NEAREST, call
 
 
 def _img_dims(t):
@@ -42,27 +27,18 @@ def remap(src, mapx, mapy, interpolation=INTER_LANCZOS4, x_shift=0):
     """cv2.remap(src, mapx, mapy, interpolation) for uint8 images, CV_32FC1 maps, BORDER_CONSTANT 0
     (stereo_camera.py:217-228).  ``x_shift`` fuses stereo_camera.py:230-240."""
     import torch
-    s, was_np = _to_dev(src, torch.uint8)
-    mx, _ = _to_dev(mapx, torch.float32)
-    my, _ = _to_dev(mapy, torch.float32)
+    s, was_np = to_device(src, dtype="uint8"), is_np(src)
+    mx = to_device(mapx, dtype="float32")
+    my = to_device(mapy, dtype="float32")
     if mx.shape != my.shape or mx.dim() != 2:
         raise ValueError("mapx / mapy must be 2-D float32 arrays of equal shape")
     n, sh, sw, cn, batched = _img_dims(s)
     dh, dw = mx.shape
     shape = (n, dh, dw) + ((cn,) if s.dim() > 2 else ())
     dst = torch.empty(shape, dtype=torch.uint8, device=s.device)
-    with torch.cuda.device(s.device):
-        rc = _native.lib().camd_remap_u8(s.data_ptr(), sw, sh, cn, sw * cn, sh * sw * cn, mx.data_ptr(),
-                                         my.data_ptr(), dst.data_ptr(), dw, dh, dw * cn, dh * dw * cn,
-                                         int(interpolation), int(x_shift), n, _native.current_stream())
-    _native.check(rc, "remap")
-    dst = dst if batched else dst[0]
-    return hostio.to_host(dst) if was_np else dst
-
-
-def _dist_args(D):
-    D = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
-    return D, (D.ctypes.data if D.size else None), int(D.size)
+    call("camd_remap_u8", s.device, s.data_ptr(), sw, sh, cn, sw * cn, sh * sw * cn, mx.data_ptr(), my.data_ptr(),
+         dst.data_ptr(), dw, dh, dw * cn, dh * dw * cn, int(interpolation), int(x_shift), n, what="remap")
+    return to_caller(dst if batched else dst[0], was_np)
 
 
 def init_undistort_rectify_map(A, dist, R, Anew, size, valid_for=None, device=None):
@@ -72,21 +48,17 @@ def init_undistort_rectify_map(A, dist, R, Anew, size, valid_for=None, device=No
     import torch
     _native.require_device()
     w, h = int(size[0]), int(size[1])
-    A = np.ascontiguousarray(A, np.float64).reshape(9)
-    Anew = np.ascontiguousarray(np.asarray(Anew, np.float64)[:, :3]).reshape(9)
-    Rm = None if R is None else np.ascontiguousarray(R, np.float64).reshape(9)
-    D, dptr, nd = _dist_args(dist)
+    A, Anew = mat(A, 9), K9(Anew)
+    Rm = None if R is None else mat(R, 9)
+    D, dptr, nd = _arrays.dist(dist)  # (the parameter shadows the helper's name)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     mapx = torch.empty((h, w), dtype=torch.float32, device=dev)
     mapy = torch.empty((h, w), dtype=torch.float32, device=dev)
     mask = torch.empty((h, w), dtype=torch.uint8, device=dev) if valid_for is not None else None
     sw, sh = (int(valid_for[0]), int(valid_for[1])) if valid_for is not None else (0, 0)
-    with torch.cuda.device(dev):
-        rc = _native.lib().camd_init_undistort_rectify_map(
-            A.ctypes.data, dptr, nd, None if Rm is None else Rm.ctypes.data, Anew.ctypes.data, w, h,
-            mapx.data_ptr(), mapy.data_ptr(), None if mask is None else mask.data_ptr(), sw, sh,
-            _native.current_stream())
-    _native.check(rc, "init_undistort_rectify_map")
+    call("camd_init_undistort_rectify_map", dev, A.ctypes.data, dptr, nd, None if Rm is None else Rm.ctypes.data,
+         Anew.ctypes.data, w, h, mapx.data_ptr(), mapy.data_ptr(), None if mask is None else mask.data_ptr(), sw, sh,
+         what="init_undistort_rectify_map")
     return (mapx, mapy) if mask is None else (mapx, mapy, mask)
 
 
@@ -95,27 +67,23 @@ def undistort_maps_device(K, D, size, device=None):
     import torch
     _native.require_device()
     w, h = int(size[0]), int(size[1])
-    K = np.ascontiguousarray(K, np.float64).reshape(9)
-    D, dptr, nd = _dist_args(D)
+    K = mat(K, 9)
+    D, dptr, nd = dist(D)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     mxy = torch.empty((h, w, 2), dtype=torch.int16, device=dev)
     ma = torch.empty((h, w), dtype=torch.int16, device=dev)  # uint16 bit patterns (torch has no uint16 arithmetic)
-    with torch.cuda.device(dev):
-        rc = _native.lib().camd_undistort_maps(K.ctypes.data, dptr, nd, w, h, mxy.data_ptr(), ma.data_ptr(),
-                                               _native.current_stream())
-    _native.check(rc, "undistort_maps")
+    call("camd_undistort_maps", dev, K.ctypes.data, dptr, nd, w, h, mxy.data_ptr(), ma.data_ptr(), what="undistort_maps")
     return mxy, ma
 
 
 def undistort_maps(K, D, size):
     """The CV_16SC2 + CV_16UC1 maps cv2.undistort(img, K, D) builds internally (host, init time)."""
     w, h = int(size[0]), int(size[1])
-    K = np.ascontiguousarray(K, np.float64).reshape(9)
-    D = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
+    K = mat(K, 9)
+    D, dptr, nd = dist(D)
     mxy = np.empty((h, w, 2), np.int16)
     ma = np.empty((h, w), np.uint16)
-    rc = _native.lib().camd_undistort_maps_host(K.ctypes.data, D.ctypes.data if D.size else None, D.size, w, h,
-                                                mxy.ctypes.data, ma.ctypes.data)
+    rc = _native.lib().camd_undistort_maps_host(K.ctypes.data, dptr, nd, w, h, mxy.ctypes.data, ma.ctypes.data)
     _native.check(rc, "undistort_maps")
     return mxy, ma
 
@@ -124,48 +92,40 @@ def remap_fixed_bilinear(src, mapxy, mapa):
     """cv2.remap(src, map16SC2, map16UC1, INTER_LINEAR): the second half of cv2.undistort
     (stereo_camera.py:430-431)."""
     import torch
-    s, was_np = _to_dev(src, torch.uint8)
-    mxy, _ = _to_dev(mapxy, torch.int16)
-    ma, _ = _to_dev(mapa.view(np.int16) if isinstance(mapa, np.ndarray) else mapa, torch.int16)
+    s, was_np = to_device(src, dtype="uint8"), is_np(src)
+    mxy = to_device(mapxy, dtype="int16")
+    ma = to_device(mapa.view(np.int16) if is_np(mapa) else mapa, dtype="int16")
     n, sh, sw, cn, batched = _img_dims(s)
     dh, dw = ma.shape
     shape = (n, dh, dw) + ((cn,) if s.dim() > 2 else ())
     dst = torch.empty(shape, dtype=torch.uint8, device=s.device)
-    with torch.cuda.device(s.device):
-        rc = _native.lib().camd_remap_fixed_bilinear_u8(
-            s.data_ptr(), sw, sh, cn, sw * cn, sh * sw * cn, mxy.data_ptr(), ma.data_ptr(), dst.data_ptr(), dw,
-            dh, dw * cn, dh * dw * cn, n, _native.current_stream())
-    _native.check(rc, "remap_fixed_bilinear")
-    dst = dst if batched else dst[0]
-    return hostio.to_host(dst) if was_np else dst
+    call("camd_remap_fixed_bilinear_u8", s.device, s.data_ptr(), sw, sh, cn, sw * cn, sh * sw * cn, mxy.data_ptr(),
+         ma.data_ptr(), dst.data_ptr(), dw, dh, dw * cn, dh * dw * cn, n, what="remap_fixed_bilinear")
+    return to_caller(dst if batched else dst[0], was_np)
 
 
 def medianBlur3_s16(disp):
     """cv2.medianBlur(disp, 3) on int16 (the unconditional tail of StereoSGBM.compute)."""
     import torch
-    s, was_np = _to_dev(disp, torch.int16)
+    s, was_np = to_device(disp, dtype="int16"), is_np(disp)
     h, w = s.shape[-2:]
     n = s.numel() // (h * w)
     dst = torch.empty_like(s)
-    with torch.cuda.device(s.device):
-        rc = _native.lib().camd_median3_s16(s.data_ptr(), dst.data_ptr(), w, h, n, _native.current_stream())
-    _native.check(rc, "medianBlur3_s16")
-    return hostio.to_host(dst) if was_np else dst
+    call("camd_median3_s16", s.device, s.data_ptr(), dst.data_ptr(), w, h, n, what="medianBlur3_s16")
+    return to_caller(dst, was_np)
 
 
 def filterSpeckles(disp, newVal, maxSpeckleSize, maxDiff):
     """cv2.filterSpeckles(disp, newVal, maxSpeckleSize, maxDiff) on int16; returns a new array."""
     import torch
-    s, was_np = _to_dev(disp, torch.int16)
+    s, was_np = to_device(disp, dtype="int16"), is_np(disp)
     s = s.clone()
     h, w = s.shape[-2:]
     n = s.numel() // (h * w)
     ws = torch.empty(_native.lib().camd_speckle_workspace_bytes(w, h, n), dtype=torch.uint8, device=s.device)
-    with torch.cuda.device(s.device):
-        rc = _native.lib().camd_filter_speckles_s16(s.data_ptr(), w, h, int(newVal), int(maxSpeckleSize),
-                                                    int(maxDiff), ws.data_ptr(), n, _native.current_stream())
-    _native.check(rc, "filterSpeckles")
-    return hostio.to_host(s) if was_np else s
+    call("camd_filter_speckles_s16", s.device, s.data_ptr(), w, h, int(newVal), int(maxSpeckleSize), int(maxDiff),
+         ws.data_ptr(), n, what="filterSpeckles")
+    return to_caller(s, was_np)
 
 
 def disp_to_depth(disp16, valid_mask, sgbm_min_disparity, add_min_disparity, translate, baseline_fx,
@@ -173,25 +133,18 @@ def disp_to_depth(disp16, valid_mask, sgbm_min_disparity, add_min_disparity, tra
     """stereo_matching.py:63-69 + stereo_camera.py:510-513 in one pass.
     Returns (disparity float32, rectify_depth float64)."""
     import torch
-    d, was_np = _to_dev(disp16, torch.int16)
-    m, _ = _to_dev(valid_mask.view(np.uint8) if isinstance(valid_mask, np.ndarray) and valid_mask.dtype == bool
-                   else valid_mask)
+    d, was_np = to_device(disp16, dtype="int16"), is_np(disp16)
+    m = to_device(valid_mask.view(np.uint8) if is_np(valid_mask) and valid_mask.dtype == bool else valid_mask)
     if m.dtype == torch.bool:
         m = m.view(torch.uint8)
     h, w = d.shape[-2:]
     n = d.numel() // (h * w)
     disparity = torch.empty(d.shape, dtype=torch.float32, device=d.device)
     depth = torch.empty(d.shape, dtype=torch.float64, device=d.device)
-    with torch.cuda.device(d.device):
-        rc = _native.lib().camd_disp_to_depth(d.data_ptr(), m.data_ptr(), w, h, int(sgbm_min_disparity),
-                                              int(add_min_disparity), int(bool(translate)),
-                                              ctypes.c_double(baseline_fx), ctypes.c_double(max_depth),
-                                              disparity.data_ptr(), depth.data_ptr(), n,
-                                              _native.current_stream())
-    _native.check(rc, "disp_to_depth")
-    if was_np:
-        return tuple(hostio.to_host(disparity, depth))
-    return disparity, depth
+    call("camd_disp_to_depth", d.device, d.data_ptr(), m.data_ptr(), w, h, int(sgbm_min_disparity), int(add_min_disparity),
+         int(bool(translate)), ctypes.c_double(baseline_fx), ctypes.c_double(max_depth), disparity.data_ptr(),
+         depth.data_ptr(), n, what="disp_to_depth")
+    return to_caller((disparity, depth), was_np)
 
 
 def disp16_resized_to_depth(sdisp16, hw, valid_mask, sgbm_min_disparity, add_min_disparity, translate, baseline_fx,
@@ -200,8 +153,8 @@ def disp16_resized_to_depth(sdisp16, hw, valid_mask, sgbm_min_disparity, add_min
     :408-413 in one pass: ``sdisp16`` is the int16 disparity of the downsized pair(s), ``hw`` the rectified size.
     Returns (disparity float32, rectify_depth float64) at ``hw``.  CUDA tensors only."""
     import torch
-    d, _ = _to_dev(sdisp16, torch.int16)
-    m, _ = _to_dev(valid_mask)
+    d = to_device(sdisp16, dtype="int16")
+    m = to_device(valid_mask)
     if m.dtype == torch.bool:
         m = m.view(torch.uint8)
     sh, sw = d.shape[-2:]
@@ -209,38 +162,32 @@ def disp16_resized_to_depth(sdisp16, hw, valid_mask, sgbm_min_disparity, add_min
     h, w = int(hw[0]), int(hw[1])
     disparity = torch.empty(d.shape[:-2] + (h, w), dtype=torch.float32, device=d.device)
     depth = torch.empty(d.shape[:-2] + (h, w), dtype=torch.float64, device=d.device)
-    with torch.cuda.device(d.device):
-        rc = _native.lib().camd_disp16_resized_to_depth(d.data_ptr(), sw, sh, m.data_ptr(), w, h,
-                                                        int(sgbm_min_disparity), int(add_min_disparity),
-                                                        int(bool(translate)), ctypes.c_double(baseline_fx),
-                                                        ctypes.c_double(max_depth), disparity.data_ptr(),
-                                                        depth.data_ptr(), n, _native.current_stream())
-    _native.check(rc, "disp16_resized_to_depth")
+    call("camd_disp16_resized_to_depth", d.device, d.data_ptr(), sw, sh, m.data_ptr(), w, h, int(sgbm_min_disparity),
+         int(add_min_disparity), int(bool(translate)), ctypes.c_double(baseline_fx), ctypes.c_double(max_depth),
+         disparity.data_ptr(), depth.data_ptr(), n, what="disp16_resized_to_depth")
     return disparity, depth
 
 
 def unrectify_depth(depth, M_row2, mapx, mapy):
     """utils.rotate_depth_by_remap (utils.py:192-199): z-rescale + INTER_NEAREST remap, float64."""
     import torch
-    z, was_np = _to_dev(depth, torch.float64)
-    mx, _ = _to_dev(mapx, torch.float32)
-    my, _ = _to_dev(mapy, torch.float32)
+    z, was_np = to_device(depth, dtype="float64"), is_np(depth)
+    mx = to_device(mapx, dtype="float32")
+    my = to_device(mapy, dtype="float32")
     h, w = z.shape[-2:]
     n = z.numel() // (h * w)
     oh, ow = mx.shape
     M = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(M_row2).reshape(3)])
     out = torch.empty(z.shape[:-2] + (oh, ow), dtype=torch.float64, device=z.device)
-    with torch.cuda.device(z.device):
-        rc = _native.lib().camd_unrectify_depth(z.data_ptr(), w, h, M, mx.data_ptr(), my.data_ptr(),
-                                                out.data_ptr(), ow, oh, n, _native.current_stream())
-    _native.check(rc, "unrectify_depth")
-    return hostio.to_host(out) if was_np else out
+    call("camd_unrectify_depth", z.device, z.data_ptr(), w, h, M, mx.data_ptr(), my.data_ptr(), out.data_ptr(), ow, oh, n,
+         what="unrectify_depth")
+    return to_caller(out, was_np)
 
 
 def check_distortion(D):
     """The distortion vector as the kernels take it (float64, flat, up to 14 entries); tilted-sensor coefficients
     (tauX, tauY = D[12:14]) are refused here, before any device call, as everywhere else in the library."""
-    D = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
+    D = dist(D)[0]
     if D.size > 14:
         raise ValueError("%d distortion coefficients; cv2's model has at most 14" % D.size)
     if D.size > 12 and (D[12:] != 0).any():
@@ -248,21 +195,22 @@ def check_distortion(D):
     return D
 
 
-_POINT_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32}
+def _cv2_distortion(D):
+    """``dist`` of a vector that passed ``check_distortion`` and has one of the lengths cv2 takes."""
+    D = check_distortion(D)
+    if D.size not in DIST_COUNTS:
+        raise ValueError("%d distortion coefficients; cv2 takes 4, 5, 8, 12 or 14" % D.size)
+    return dist(D)
 
 
 def _point_rows(a, width, what):
     """The (n, width) rows of ``a`` = (n, width) or (n, 1, width), float32 / float64, ndarray or CUDA tensor -- checked
     before the device is touched -- as (CUDA tensor whose rows are read in place, row stride in elements, was_numpy).
     A tensor whose rows are the leading columns of wider rows (``uvzs[:, :2]``, ``xyzuv[:, :3]``) is not copied."""
-    import torch
-    was_np = isinstance(a, np.ndarray)
-    if not was_np and not isinstance(a, torch.Tensor):
-        raise TypeError("%s must be a NumPy array or a torch CUDA tensor, got %s" % (what, type(a).__name__))
-    if str(a.dtype).replace("torch.", "") not in _POINT_TYPES:
+    check_array(a, what)
+    was_np = is_np(a)
+    if dtype_name(a) not in FLOAT_TYPES:
         raise ValueError("%s must be float32 or float64 (cv2 takes nothing else), got %s" % (what, a.dtype))
-    if not was_np and not a.is_cuda:
-        raise ValueError("tensor inputs must live on the GPU (%s)" % what)
     if a.ndim == 3 and a.shape[1] == 1:
         a = a[:, 0]
     if a.ndim != 2 or a.shape[1] != width:
@@ -270,8 +218,7 @@ def _point_rows(a, width, what):
     if a.shape[0] >= 2 ** 31:
         raise ValueError("%s: %d rows, the kernels take fewer than 2^31" % (what, a.shape[0]))
     if was_np:
-        _native.require_device()
-        return torch.from_numpy(np.ascontiguousarray(a)).cuda(), width, True
+        return to_device(a), width, True
     n = a.shape[0]
     if a.stride(1) != 1 or (n > 1 and not width <= a.stride(0) < 2 ** 31):
         a = a.contiguous()
@@ -286,22 +233,18 @@ def undistort_points(uvs, K, D=None, iters=5, pixels=False):
     ``pixels=True``: the points go back to pixels of the undistorted camera in the same kernel, normalised * [fx, fy] +
     [cx, cy] in float64 -> (n, 2) float64 whatever the input's type: the whole of ``Cam.undistort_points``."""
     import torch
-    D = check_distortion(D)
-    if D.size not in (0, 4, 5, 8, 12, 14):
-        raise ValueError("%d distortion coefficients; cv2 takes 4, 5, 8, 12 or 14" % D.size)
+    D, dptr, nd = _cv2_distortion(D)
     if int(iters) != iters or not 1 <= iters <= 100:
         raise ValueError("iters must be an integer in 1 .. 100, got %r" % (iters,))
-    K = np.ascontiguousarray(np.asarray(K, np.float64)[:3, :3]).reshape(9)
+    K = K9(K)
     t, stride, was_np = _point_rows(uvs, 2, "uvs")
     out = torch.empty((t.shape[0], 2), dtype=torch.float64 if pixels else t.dtype, device=t.device)
     if t.shape[0]:
-        uv_type = _POINT_TYPES[str(t.dtype).replace("torch.", "")]
+        uv_type = FLOAT_TYPES[dtype_name(t)]
         out_type = _native.VALUE_F64 | _native.POINTS_PIXELS if pixels else uv_type
-        with torch.cuda.device(t.device):
-            rc = _native.lib().camd_undistort_points(t.data_ptr(), uv_type, t.shape[0], stride, K.ctypes.data, D.ctypes.data if D.size else None, int(D.size),
-                                                     int(iters), out.data_ptr(), out_type, _native.current_stream())
-        _native.check(rc, "undistort_points")
-    return hostio.to_host(out) if was_np else out
+        call("camd_undistort_points", t.device, t.data_ptr(), uv_type, t.shape[0], stride, K.ctypes.data, dptr, nd, int(iters),
+             out.data_ptr(), out_type, what="undistort_points")
+    return to_caller(out, was_np)
 
 
 def project_points(xyzs, rvec_or_R, tvec, K, D=None):
@@ -311,27 +254,21 @@ def project_points(xyzs, rvec_or_R, tvec, K, D=None):
     on its device and the current stream, its rows read in place (no copy for ``xyzuv[:, :3]``)."""
     import torch
     from . import geometry
-    D = check_distortion(D)
-    if D.size not in (0, 4, 5, 8, 12, 14):
-        raise ValueError("%d distortion coefficients; cv2 takes 4, 5, 8, 12 or 14" % D.size)
+    D, dptr, nd = _cv2_distortion(D)
     R = np.asarray(rvec_or_R, np.float64)
     if R.size not in (3, 9):
         raise ValueError("rvec_or_R must be a Rodrigues vector or a 3x3 matrix, got shape %s" % (R.shape,))
-    R = np.ascontiguousarray(geometry.rodrigues(R) if R.size == 3 else R, np.float64).reshape(9)
+    R = mat(geometry.rodrigues(R) if R.size == 3 else R, 9)
     tv = np.ascontiguousarray(tvec, np.float64).reshape(-1)
     if tv.size != 3:
         raise ValueError("tvec must hold 3 numbers, got %d" % tv.size)
-    K = np.ascontiguousarray(np.asarray(K, np.float64)[:3, :3]).reshape(9)
+    K = K9(K)
     t, stride, was_np = _point_rows(xyzs, 3, "xyzs")
     out = torch.empty((t.shape[0], 2), dtype=t.dtype, device=t.device)
     if t.shape[0]:
-        with torch.cuda.device(t.device):
-            rc = _native.lib().camd_project_points(t.data_ptr(), _POINT_TYPES[str(t.dtype).replace("torch.", "")], t.shape[0],
-                                                   stride, R.ctypes.data, tv.ctypes.data, K.ctypes.data,
-                                                   D.ctypes.data if D.size else None, int(D.size), out.data_ptr(),
-                                                   _native.current_stream())
-        _native.check(rc, "project_points")
-    return hostio.to_host(out) if was_np else out
+        call("camd_project_points", t.device, t.data_ptr(), FLOAT_TYPES[dtype_name(t)], t.shape[0], stride, R.ctypes.data,
+             tv.ctypes.data, K.ctypes.data, dptr, nd, out.data_ptr(), what="project_points")
+    return to_caller(out, was_np)
 
 
 def distort_index_map(K, D, size, device=None):
@@ -344,19 +281,17 @@ def distort_index_map(K, D, size, device=None):
     are read here, once).  The reference raises it too for targets >= w / >= h and silently wraps negative ones to the
     far edge (NumPy's negative indexing); here both sides are refused."""
     import torch
-    D = check_distortion(D)
+    D, dptr, nd = dist(check_distortion(D))
     w, h = int(size[0]), int(size[1])
     if w <= 0 or h <= 0:
         raise ValueError("image size must be positive, got %s" % ((w, h),))
-    K = np.ascontiguousarray(np.asarray(K, np.float64)[:3, :3]).reshape(9)
+    K = K9(K)
     _native.require_device()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     idx = torch.empty((h, w), dtype=torch.int32, device=dev)
     stats = torch.empty(6, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _native.lib().camd_distort_index_map(K.ctypes.data, D.ctypes.data if D.size else None, int(D.size), w, h,
-                                                  idx.data_ptr(), stats.data_ptr(), _native.current_stream())
-    _native.check(rc, "distort_index_map")
+    call("camd_distort_index_map", dev, K.ctypes.data, dptr, nd, w, h, idx.data_ptr(), stats.data_ptr(),
+         what="distort_index_map")
     n_out, min_u, max_u, min_v, max_v, n_nonfinite = (int(v) for v in stats.cpu())
     if n_out:
         where = "U in [%d, %d], V in [%d, %d]" % (min_u, max_u, min_v, max_v) if min_u <= max_u else "no finite target"
@@ -370,8 +305,8 @@ def distort_depth(depth, src_index):
     """stereo_camera.py:438,463 (``res = zeros; res[y, x] = depths[index]``) as one gather through ``src_index``
     (``distort_index_map``): depth (h, w) or (n, h, w), float64 or float32 -> the same shape and dtype; holes are 0."""
     import torch
-    idx, _ = _to_dev(src_index, torch.int32)
-    z, was_np = _to_dev(depth)
+    idx = to_device(src_index, dtype="int32")
+    z, was_np = to_device(depth), is_np(depth)
     if z.dtype not in (torch.float64, torch.float32):
         raise ValueError("depth must be float64 or float32, got %s" % z.dtype)
     if idx.dim() != 2 or z.dim() not in (2, 3) or tuple(z.shape[-2:]) != tuple(idx.shape):
@@ -382,8 +317,6 @@ def distort_depth(depth, src_index):
     h, w = idx.shape
     out = torch.empty_like(z)
     if z.numel():
-        with torch.cuda.device(z.device):
-            rc = _native.lib().camd_distort_depth(z.data_ptr(), z.element_size(), w, h, idx.data_ptr(), out.data_ptr(),
-                                                  z.numel() // (h * w), _native.current_stream())
-        _native.check(rc, "distort_depth")
-    return hostio.to_host(out) if was_np else out
+        call("camd_distort_depth", z.device, z.data_ptr(), z.element_size(), w, h, idx.data_ptr(), out.data_ptr(),
+             z.numel() // (h * w), what="distort_depth")
+    return to_caller(out, was_np)

@@ -13,25 +13,14 @@ import ctypes
 
 import numpy as np
 
-from . import _native, hostio
-from .sparse import _check_array, _dtype_name
+from . import _native
+from ._arrays import VALUE_TYPES, K9, Kinv9, check_array, dtype_name, is_np, mat, positive_wh, to_caller, to_device
+from ._native import call
 
 
-def _to_dev(a, dtype):
-    import torch
-    if isinstance(a, np.ndarray):
-        _native.require_device()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda(), True
-    if not a.is_cuda:
-        raise ValueError("tensor inputs must live on the GPU")
-    return a.to(dtype).contiguous(), False
-
-
-def _mat(m, n):
-    a = np.ascontiguousarray(m, np.float64).reshape(-1)
-    if a.size != n:
-        raise ValueError("expected %d matrix entries, got %d" % (n, a.size))
-    return a
+def _f64(a):
+    """(float64 CUDA tensor -- this module casts, as the reference's NumPy does -- , was_numpy)"""
+    return to_device(a, dtype="float64", cast=True), is_np(a)
 
 
 def get_appropriate_interpolation_rate(cam1, cam2, interpolation=1.5):
@@ -49,9 +38,9 @@ def depth_to_point_cloud(depth, K, interpolation_rate=1, return_xyzuv=False):
     """(N, 3) points of the non-zero depths in row-major order, or (N, 5) ``xyzuv`` (utils.py:213-246).
     uint16 depth is millimetres, as in the reference."""
     import torch
-    if isinstance(depth, np.ndarray) and depth.dtype == np.uint16:
+    if is_np(depth) and depth.dtype == np.uint16:
         depth = np.float32(depth / 1000.0)
-    d, was_np = _to_dev(depth, torch.float64)
+    d, was_np = _f64(depth)
     if d.dim() != 2:
         raise AssertionError("depth.ndim == 2")
     h, w = d.shape
@@ -60,96 +49,65 @@ def depth_to_point_cloud(depth, K, interpolation_rate=1, return_xyzuv=False):
     gw, gh = ctypes.c_int(), ctypes.c_int()
     _native.check(lib.camd_point_cloud_grid(w, h, rate, ctypes.byref(gw), ctypes.byref(gh)), "depth_to_point_cloud")
     cap = gw.value * gh.value
-    Kinv = np.ascontiguousarray(np.linalg.inv(np.asarray(K, np.float64)[:3, :3])).reshape(9)
-    with torch.cuda.device(d.device):
-        pts = torch.empty((cap, 3), dtype=torch.float64, device=d.device)
-        uv = torch.empty((cap, 2), dtype=torch.float64, device=d.device) if return_xyzuv else None
-        count = torch.zeros(1, dtype=torch.int64, device=d.device)
-        ws = torch.empty(lib.camd_point_cloud_workspace_bytes(w, h, rate), dtype=torch.uint8, device=d.device)
-        rc = lib.camd_depth_to_point_cloud(d.data_ptr(), w, h, Kinv.ctypes.data, rate, pts.data_ptr(),
-                                           None if uv is None else uv.data_ptr(), cap, count.data_ptr(), ws.data_ptr(),
-                                           _native.current_stream())
-    _native.check(rc, "depth_to_point_cloud")
+    Kinv = Kinv9(K)
+    pts = torch.empty((cap, 3), dtype=torch.float64, device=d.device)
+    uv = torch.empty((cap, 2), dtype=torch.float64, device=d.device) if return_xyzuv else None
+    count = torch.zeros(1, dtype=torch.int64, device=d.device)
+    ws = torch.empty(lib.camd_point_cloud_workspace_bytes(w, h, rate), dtype=torch.uint8, device=d.device)
+    call("camd_depth_to_point_cloud", d.device, d.data_ptr(), w, h, Kinv.ctypes.data, rate, pts.data_ptr(),
+         None if uv is None else uv.data_ptr(), cap, count.data_ptr(), ws.data_ptr(), what="depth_to_point_cloud")
     n = int(count.item())  # synchronises: the output length is data dependent
-    out = torch.cat([pts[:n], uv[:n]], dim=1) if return_xyzuv else pts[:n]
-    return hostio.to_host(out) if was_np else out
+    return to_caller(torch.cat([pts[:n], uv[:n]], dim=1) if return_xyzuv else pts[:n], was_np)
 
 
 def apply_T_to_point_cloud(T, point_cloud):
     """(T @ [p, 1])[:3] for every row; extra columns are carried over (utils.py:152-161)."""
     import torch
-    p, was_np = _to_dev(point_cloud, torch.float64)
+    p, was_np = _f64(point_cloud)
     xyz = p[:, :3].contiguous()
     out = torch.empty_like(xyz)
-    Tm = _mat(T, 16)
-    with torch.cuda.device(p.device):
-        rc = _native.lib().camd_apply_T_to_point_cloud(xyz.data_ptr(), xyz.shape[0], Tm.ctypes.data, out.data_ptr(),
-                                                       _native.current_stream())
-    _native.check(rc, "apply_T_to_point_cloud")
+    Tm = mat(T, 16)
+    call("camd_apply_T_to_point_cloud", p.device, xyz.data_ptr(), xyz.shape[0], Tm.ctypes.data, out.data_ptr(),
+         what="apply_T_to_point_cloud")
     if p.shape[1] > 3:
         out = torch.cat([out, p[:, 3:]], dim=1)
-    return hostio.to_host(out) if was_np else out
+    return to_caller(out, was_np)
 
 
 def point_cloud_to_depth(points, K, xy, bg_value=0):
     """Depth image (xy[1], xy[0]) float64 of a point cloud: nearest z per pixel (utils.py:249-318)."""
     import torch
-    p, was_np = _to_dev(points, torch.float64)
+    p, was_np = _f64(points)
     if p.dim() != 2 or p.shape[1] < 3:
         raise ValueError("points must be (N, >=3)")
     w, h = int(xy[0]), int(xy[1])
-    Km = _mat(np.asarray(K, np.float64)[:3, :3], 9)
-    with torch.cuda.device(p.device):
-        depth = torch.empty((h, w), dtype=torch.float64, device=p.device)
-        keys = torch.empty((h, w), dtype=torch.int64, device=p.device)
-        rc = _native.lib().camd_point_cloud_to_depth(p.data_ptr(), p.shape[0], p.shape[1], Km.ctypes.data, w, h,
-                                                     float(bg_value), depth.data_ptr(), keys.data_ptr(),
-                                                     _native.current_stream())
-    _native.check(rc, "point_cloud_to_depth")
-    return hostio.to_host(depth) if was_np else depth
+    Km = K9(K)
+    depth = torch.empty((h, w), dtype=torch.float64, device=p.device)
+    keys = torch.empty((h, w), dtype=torch.int64, device=p.device)
+    call("camd_point_cloud_to_depth", p.device, p.data_ptr(), p.shape[0], p.shape[1], Km.ctypes.data, w, h, float(bg_value),
+         depth.data_ptr(), keys.data_ptr(), what="point_cloud_to_depth")
+    return to_caller(depth, was_np)
 
 
 def project_depth(depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
     """depth image of camera 2 seen from camera 1: depth_to_point_cloud -> apply_T -> point_cloud_to_depth
     (camera.py:298-309) as one scatter pass over the sampling grid."""
     import torch
-    d, was_np = _to_dev(depth2, torch.float64)
+    d, was_np = _f64(depth2)
     h2, w2 = d.shape
     w1, h1 = int(xy1[0]), int(xy1[1])
-    K2inv = np.ascontiguousarray(np.linalg.inv(np.asarray(K2, np.float64)[:3, :3])).reshape(9)
-    Tm, K1m = _mat(T_2in1, 16), _mat(np.asarray(K1, np.float64)[:3, :3], 9)
-    with torch.cuda.device(d.device):
-        depth1 = torch.empty((h1, w1), dtype=torch.float64, device=d.device)
-        keys = torch.empty((h1, w1), dtype=torch.int64, device=d.device)
-        rc = _native.lib().camd_project_depth(d.data_ptr(), w2, h2, K2inv.ctypes.data, Tm.ctypes.data, K1m.ctypes.data,
-                                              float(interpolation_rate), w1, h1, depth1.data_ptr(), keys.data_ptr(),
-                                              _native.current_stream())
-    _native.check(rc, "project_depth")
-    return hostio.to_host(depth1) if was_np else depth1
+    K2inv, Tm, K1m = Kinv9(K2), mat(T_2in1, 16), K9(K1)
+    depth1 = torch.empty((h1, w1), dtype=torch.float64, device=d.device)
+    keys = torch.empty((h1, w1), dtype=torch.int64, device=d.device)
+    call("camd_project_depth", d.device, d.data_ptr(), w2, h2, K2inv.ctypes.data, Tm.ctypes.data, K1m.ctypes.data,
+         float(interpolation_rate), w1, h1, depth1.data_ptr(), keys.data_ptr(), what="project_depth")
+    return to_caller(depth1, was_np)
 
 
 # ---- the z-buffer with a payload -----------------------------------------------------------------------------------
-_VALUE_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32, "uint8": _native.VALUE_U8}
-
-
-def _check_xy(xy, what="xy"):
-    w, h = int(xy[0]), int(xy[1])
-    if w <= 0 or h <= 0:
-        raise ValueError("%s must be a positive (width, height), got %s" % (what, (xy[0], xy[1])))
-    return w, h
-
-
 def _same_device(a, b, what):
-    if not isinstance(a, np.ndarray) and not isinstance(b, np.ndarray) and a.device != b.device:
+    if not is_np(a) and not is_np(b) and a.device != b.device:
         raise ValueError("%s live on different devices: %s and %s" % (what, a.device, b.device))
-
-
-def _keep_dtype_to_dev(a, device=None):
-    import torch
-    if isinstance(a, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        return t.cuda() if device is None else t.to(device)
-    return a.contiguous()
 
 
 def point_cloud_to_arr2d(points, K, xy, values=None, bg_value=0):
@@ -159,90 +117,81 @@ def point_cloud_to_arr2d(points, K, xy, values=None, bg_value=0):
     ``values = img[mask]``.  Points with bit-equal z on one pixel: the later row wins."""
     if values is None:
         return point_cloud_to_depth(points, K, xy, bg_value=bg_value)
-    _check_array(points, "points")
-    _check_array(values, "values")
+    check_array(points, "points")
+    check_array(values, "values")
     if len(points.shape) != 2 or points.shape[1] < 3:
         raise ValueError("points must be (N, >=3), got %s" % (tuple(points.shape),))
     n = int(points.shape[0])
     vshape = tuple(values.shape)
     if len(vshape) not in (1, 2) or vshape[0] != n or (len(vshape) == 2 and vshape[1] < 1):
         raise ValueError("values must be (N,) or (N, C) with N = %d points, got %s" % (n, vshape))
-    name = _dtype_name(values)
-    if name not in _VALUE_TYPES:
+    name = dtype_name(values)
+    if name not in VALUE_TYPES:
         raise ValueError("values must be float64, float32 or uint8, got %s" % name)
     bg = float(bg_value)
     if name == "uint8" and not (0 <= bg <= 255 and bg == int(bg)):
         raise ValueError("bg_value %r is not a uint8" % (bg_value,))
     _same_device(points, values, "points and values")
-    w, h = _check_xy(xy)
-    Km = _mat(np.asarray(K, np.float64)[:3, :3], 9)
+    w, h = positive_wh(xy)
+    Km = K9(K)
     channels = vshape[1] if len(vshape) == 2 else 1
     import torch
-    p, _ = _to_dev(points, torch.float64)
-    v = _keep_dtype_to_dev(values, p.device)
-    was_np = isinstance(values, np.ndarray)
-    with torch.cuda.device(p.device):
-        out = torch.empty((h, w, channels) if channels >= 2 else (h, w), dtype=v.dtype, device=p.device)
-        keys = torch.empty((h, w), dtype=torch.int64, device=p.device)
-        owner = torch.empty((h, w), dtype=torch.int32, device=p.device)
-        rc = _native.lib().camd_point_cloud_to_arr2d(p.data_ptr(), n, p.shape[1], Km.ctypes.data, w, h, v.data_ptr(),
-                                                     channels, _VALUE_TYPES[name], bg, out.data_ptr(), keys.data_ptr(),
-                                                     owner.data_ptr(), _native.current_stream())
-    _native.check(rc, "point_cloud_to_arr2d")
-    return hostio.to_host(out) if was_np else out
+    p, _ = _f64(points)
+    v = to_device(values, device=p.device)
+    out = torch.empty((h, w, channels) if channels >= 2 else (h, w), dtype=v.dtype, device=p.device)
+    keys = torch.empty((h, w), dtype=torch.int64, device=p.device)
+    owner = torch.empty((h, w), dtype=torch.int32, device=p.device)
+    call("camd_point_cloud_to_arr2d", p.device, p.data_ptr(), n, p.shape[1], Km.ctypes.data, w, h, v.data_ptr(), channels,
+         VALUE_TYPES[name], bg, out.data_ptr(), keys.data_ptr(), owner.data_ptr(), what="point_cloud_to_arr2d")
+    return to_caller(out, is_np(values))
 
 
 def _check_depth2(depth2):
-    _check_array(depth2, "depth2")
+    check_array(depth2, "depth2")
     if len(depth2.shape) not in (2, 3) or 0 in tuple(depth2.shape):
         raise ValueError("depth2 must be (h2, w2) or (n, h2, w2), got %s" % (tuple(depth2.shape),))
-    name = _dtype_name(depth2)
+    name = dtype_name(depth2)
     if name not in ("float64", "float32", "uint16"):
         raise ValueError("depth2 must be float64, float32 or uint16 (millimetres), got %s" % name)
     return name
 
 
-def _depth_to_dev(depth2, name):
+def _depth_metres(depth2, name):
     """float64 CUDA tensor of the depth in metres; uint16 is millimetres through float32 (utils.py:218-219)."""
-    import torch
-    if isinstance(depth2, np.ndarray):
-        if name == "uint16":
-            depth2 = np.float32(depth2 / 1000.0)
-        _native.require_device()
-        return torch.from_numpy(np.ascontiguousarray(depth2, dtype=np.float64)).cuda()
     if name == "uint16":
-        depth2 = (depth2.to(torch.float64) / 1000.0).to(torch.float32)
-    return depth2.to(torch.float64).contiguous()
+        if is_np(depth2):
+            depth2 = np.float32(depth2 / 1000.0)
+        else:
+            import torch
+            depth2 = (depth2.to(torch.float64) / 1000.0).to(torch.float32)
+    return to_device(depth2, dtype="float64", cast=True)
 
 
 def _reproject_args(K1, K2, T_2in1, xy1, interpolation_rate):
-    w1, h1 = _check_xy(xy1, "xy1")
+    w1, h1 = positive_wh(xy1, "xy1")
     rate = float(interpolation_rate)
     if not (rate > 0 and np.isfinite(rate)):
         raise ValueError("interpolation_rate must be positive and finite, got %r" % (interpolation_rate,))
     K2m = np.asarray(K2, np.float64)
     if K2m.ndim != 2 or K2m.shape[0] < 3 or K2m.shape[1] < 3:
         raise ValueError("K2 must be a 3x3 matrix, got shape %s" % (K2m.shape,))
-    K2inv = np.ascontiguousarray(np.linalg.inv(K2m[:3, :3])).reshape(9)
+    K2inv = Kinv9(K2m)
     K1m = np.asarray(K1, np.float64)
     if K1m.ndim != 2 or K1m.shape[0] < 3 or K1m.shape[1] < 3:
         raise ValueError("K1 must be a 3x3 matrix, got shape %s" % (K1m.shape,))
-    return w1, h1, rate, K2inv, _mat(T_2in1, 16), _mat(K1m[:3, :3], 9)
+    return w1, h1, rate, K2inv, mat(T_2in1, 16), K9(K1m)
 
 
 def _reproject_maps(d, w1, h1, rate, K2inv, Tm, K1m):
     """(n, 2, h1, w1) float32 CUDA tensor of a float64 (n, h2, w2) CUDA depth."""
     import torch
     n, h2, w2 = d.shape
-    with torch.cuda.device(d.device):
-        maps = torch.empty((n, 2, h1, w1), dtype=torch.float32, device=d.device)
-        keys = torch.empty((n, h1, w1), dtype=torch.int64, device=d.device)
-        owner = torch.empty((n, h1, w1), dtype=torch.int32, device=d.device)
-        rc = _native.lib().camd_reproject_remap(d.data_ptr(), w2, h2, h2 * w2, K2inv.ctypes.data, Tm.ctypes.data,
-                                                K1m.ctypes.data, rate, w1, h1, maps.data_ptr(),
-                                                maps.data_ptr() + 4 * h1 * w1, 2 * h1 * w1, keys.data_ptr(),
-                                                owner.data_ptr(), n, _native.current_stream())
-    _native.check(rc, "get_reproject_remap")
+    maps = torch.empty((n, 2, h1, w1), dtype=torch.float32, device=d.device)
+    keys = torch.empty((n, h1, w1), dtype=torch.int64, device=d.device)
+    owner = torch.empty((n, h1, w1), dtype=torch.int32, device=d.device)
+    call("camd_reproject_remap", d.device, d.data_ptr(), w2, h2, h2 * w2, K2inv.ctypes.data, Tm.ctypes.data, K1m.ctypes.data,
+         rate, w1, h1, maps.data_ptr(), maps.data_ptr() + 4 * h1 * w1, 2 * h1 * w1, keys.data_ptr(), owner.data_ptr(), n,
+         what="get_reproject_remap")
     return maps
 
 
@@ -252,12 +201,10 @@ def get_reproject_remap(K1, K2, T_2in1, depth2, xy1, interpolation_rate=1):
     uint16 depth is millimetres."""
     name = _check_depth2(depth2)
     args = _reproject_args(K1, K2, T_2in1, xy1, interpolation_rate)
-    was_np = isinstance(depth2, np.ndarray)
-    d = _depth_to_dev(depth2, name)
+    d = _depth_metres(depth2, name)
     batched = d.dim() == 3
     maps = _reproject_maps(d if batched else d[None], *args)
-    maps = maps if batched else maps[0]
-    return hostio.to_host(maps) if was_np else maps
+    return to_caller(maps if batched else maps[0], is_np(depth2))
 
 
 def reproject_img(img2, depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
@@ -266,9 +213,9 @@ def reproject_img(img2, depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
     is ``depth2`` (n, h2, w2) with ``img2`` (n, h2, w2) or (n, h2, w2, 3).  Pixels nothing reaches are 0."""
     from . import imgproc
     name = _check_depth2(depth2)
-    _check_array(img2, "img2")
-    if _dtype_name(img2) != "uint8":
-        raise ValueError("img2 must be uint8, got %s" % _dtype_name(img2))
+    check_array(img2, "img2")
+    if dtype_name(img2) != "uint8":
+        raise ValueError("img2 must be uint8, got %s" % dtype_name(img2))
     batched = len(depth2.shape) == 3
     ishape, dshape = tuple(img2.shape), tuple(depth2.shape)
     if not (ishape == dshape or ishape == dshape + (3,)):
@@ -276,12 +223,10 @@ def reproject_img(img2, depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
                          % (ishape, dshape))
     _same_device(img2, depth2, "img2 and depth2")
     args = _reproject_args(K1, K2, T_2in1, xy1, interpolation_rate)
-    was_np = isinstance(img2, np.ndarray)
     import torch
-    d = _depth_to_dev(depth2, name)
-    img = _keep_dtype_to_dev(img2, d.device)
+    d = _depth_metres(depth2, name)
+    img = to_device(img2, device=d.device)
     maps = _reproject_maps(d if batched else d[None], *args)
     imgs = img if batched else img[None]
     out = torch.stack([imgproc.remap(imgs[i], maps[i, 0], maps[i, 1], imgproc.INTER_LINEAR) for i in range(len(imgs))])
-    out = out if batched else out[0]
-    return hostio.to_host(out) if was_np else out
+    return to_caller(out if batched else out[0], is_np(img2))

@@ -17,8 +17,9 @@ from itertools import combinations
 import numpy as np
 from numpy.linalg import inv
 
-from . import _native, epipolar_geometry as eg, hostio
-from .sparse import _dev, _dtype_name, _is_np
+from . import _native, epipolar_geometry as eg
+from ._arrays import FLOAT_TYPES, dtype_name, is_np, to_caller, to_device
+from ._native import call
 
 TRIPLE_STAGES = ("batch", "loop")
 TRIPLE_STAGE = "batch"  # how the triples are matched unless cfg["triple_stage"] says otherwise (DESIGN.md 4.3c has the timing)
@@ -99,34 +100,24 @@ def plan_propagation(view_keys, triples, reroot=None):
 def _column_sum(buf, row0, n, column=2):
     """Sum of ``buf[row0 : row0 + n, column]`` through the fixed-order reduction; a device scalar is read back."""
     import torch
-    lib = _native.lib()
-    with torch.cuda.device(buf.device):
-        partials = torch.empty(lib.camd_column_sum_blocks(n), dtype=torch.float64, device=buf.device)
-        out = torch.empty(1, dtype=torch.float64, device=buf.device)
-        rc = lib.camd_column_sum(buf.data_ptr(), int(buf.shape[0]), int(buf.shape[1]), column, row0, n, partials.data_ptr(),
-                                 out.data_ptr(), _native.current_stream())
-    _native.check(rc, "ReconstructionExtrinsics")
+    partials = torch.empty(_native.lib().camd_column_sum_blocks(n), dtype=torch.float64, device=buf.device)
+    out = torch.empty(1, dtype=torch.float64, device=buf.device)
+    call("camd_column_sum", buf.device, buf.data_ptr(), int(buf.shape[0]), int(buf.shape[1]), column, row0, n,
+         partials.data_ptr(), out.data_ptr(), what="ReconstructionExtrinsics")
     return float(out.cpu().numpy()[0])
 
 
 def _column_scale(buf, row0, n, rate, column=2):
-    import torch
-    with torch.cuda.device(buf.device):
-        rc = _native.lib().camd_column_scale(buf.data_ptr(), int(buf.shape[0]), int(buf.shape[1]), column, row0, n, float(rate),
-                                             _native.current_stream())
-    _native.check(rc, "ReconstructionExtrinsics.change_scale")
+    call("camd_column_scale", buf.device, buf.data_ptr(), int(buf.shape[0]), int(buf.shape[1]), column, row0, n, float(rate),
+         what="ReconstructionExtrinsics.change_scale")
 
 
 def _pack(buf, row0, uvs, zs, other):
-    import torch
-    name = "float32" if _dtype_name(uvs) == "float32" else "float64"
-    uv = _dev(uvs, buf.device if not _is_np(uvs) else None, dtype=name)
-    z = _dev(zs, buf.device if not _is_np(zs) else None, dtype="float64")
-    n = int(uv.shape[0])
-    with torch.cuda.device(buf.device):
-        rc = _native.lib().camd_uvzi_pack(uv.data_ptr(), eg._UV_TYPES[name], z.data_ptr(), n, float(other), buf.data_ptr(),
-                                          int(buf.shape[0]), row0, _native.current_stream())
-    _native.check(rc, "ReconstructionExtrinsics")
+    name = "float32" if dtype_name(uvs) == "float32" else "float64"
+    uv = to_device(uvs, dtype=name, cast=True, device=None if is_np(uvs) else buf.device)
+    z = to_device(zs, dtype="float64", cast=True, device=None if is_np(zs) else buf.device)
+    call("camd_uvzi_pack", buf.device, uv.data_ptr(), FLOAT_TYPES[name], z.data_ptr(), int(uv.shape[0]), float(other),
+         buf.data_ptr(), int(buf.shape[0]), row0, what="ReconstructionExtrinsics")
 
 
 class ReconstructionExtrinsics:
@@ -247,14 +238,13 @@ class ReconstructionExtrinsics:
             blocks[k1].insert(0, (d["uvs1"], d["zs1"], k2))
             blocks[k2].insert(0, (d["uvs2"], d["zs2"], k1))
         first = next(iter(stereods.values())).epipolar["uvs1"]
-        was_np = _is_np(first)
+        was_np = is_np(first)
         if was_np:
             _native.require_device()
         device = torch.device("cuda", torch.cuda.current_device()) if was_np else first.device
         rows = {k: sum(int(b[0].shape[0]) for b in blocks[k]) for k in viewds}
         total = sum(rows.values())
-        with torch.cuda.device(device):
-            buf = torch.empty((total, 4), dtype=torch.float64, device=device)
+        buf = torch.empty((total, 4), dtype=torch.float64, device=device)
         start, at = {}, 0
         for k in viewds:
             start[k] = at
@@ -268,9 +258,9 @@ class ReconstructionExtrinsics:
             viewd["T_re"][:3, 3] *= rate
         T0_target = np.eye(4)
         T0_target[2, 3] = -(_column_sum(buf, start[0], rows[0]) / rows[0])
-        host = hostio.to_host(buf) if was_np else None
+        rows_all = to_caller(buf, was_np)
         for k, viewd in viewds.items():
-            viewd["uvzis"] = (host if was_np else buf)[start[k]:start[k] + rows[k]]
+            viewd["uvzis"] = rows_all[start[k]:start[k] + rows[k]]
         self.apply_T(T=T0_target @ inv(viewds[0]["T_re"]))
 
     build_set2ds_by_flowds = staticmethod(eg.build_set2ds_by_flowds)
@@ -281,7 +271,7 @@ class ReconstructionExtrinsics:
         for viewd in self.viewds.values():
             if T is None:
                 uvzis = viewd["uvzis"]
-                if _is_np(uvzis):
+                if is_np(uvzis):
                     uvzis[:, 2] *= rate
                 else:
                     _column_scale(uvzis, 0, int(uvzis.shape[0]), rate)

@@ -7,7 +7,7 @@ torch CUDA tensors in, tensors out.
 """
 import numbers
 
-from . import _native
+from ._native import call
 
 
 def target_hw(shape_hw, arg):
@@ -34,17 +34,13 @@ def resize(img, arg, batched=False):
     sh, sw = img.shape[lead:lead + 2]
     dh, dw = hw
     head = tuple(img.shape[:lead])
-    with torch.cuda.device(img.device):
-        if img.dtype == torch.uint8:
-            cn = 1 if img.dim() == lead + 2 else img.shape[lead + 2]
-            out = torch.empty(head + (dh, dw) + tuple(img.shape[lead + 2:]), dtype=torch.uint8, device=img.device)
-            rc = _native.lib().camd_resize_linear_u8(img.data_ptr(), sw, sh, cn, out.data_ptr(), dw, dh, n,
-                                                     _native.current_stream())
-        elif img.dtype == torch.float32 and img.dim() == lead + 2:
-            out = torch.empty(head + (dh, dw), dtype=torch.float32, device=img.device)
-            rc = _native.lib().camd_resize_linear_f32(img.data_ptr(), sw, sh, out.data_ptr(), dw, dh, n,
-                                                      _native.current_stream())
-        else:
-            raise ValueError("resize: unsupported dtype/shape %s %s" % (img.dtype, tuple(img.shape)))
-    _native.check(rc, "resize")
+    if img.dtype == torch.uint8:
+        cn = 1 if img.dim() == lead + 2 else img.shape[lead + 2]
+        out = torch.empty(head + (dh, dw) + tuple(img.shape[lead + 2:]), dtype=torch.uint8, device=img.device)
+        call("camd_resize_linear_u8", img.device, img.data_ptr(), sw, sh, cn, out.data_ptr(), dw, dh, n, what="resize")
+    elif img.dtype == torch.float32 and img.dim() == lead + 2:
+        out = torch.empty(head + (dh, dw), dtype=torch.float32, device=img.device)
+        call("camd_resize_linear_f32", img.device, img.data_ptr(), sw, sh, out.data_ptr(), dw, dh, n, what="resize")
+    else:
+        raise ValueError("resize: unsupported dtype/shape %s %s" % (img.dtype, tuple(img.shape)))
     return out

@@ -9,9 +9,9 @@ Mirrors the part of cv2's interface the reference touches
 import collections
 import ctypes
 
-import numpy as np
-
-from . import _native, hostio
+from . import _native
+from ._arrays import is_np, to_caller, to_device
+from ._native import call
 
 MODE_SGBM = _native.MODE_SGBM
 MODE_HH = _native.MODE_HH
@@ -83,8 +83,8 @@ class StereoSGBM:
 
     def status(self):
         """Synchronise and raise if a device-side bounded wait timed out (fused path)."""
-        for hd, _, _ in list(self._cache.values()):
-            _native.check(_native.lib().camd_sgbm_status(hd, _native.current_stream()), "StereoSGBM")
+        for key, (hd, _, _) in list(self._cache.items()):
+            call("camd_sgbm_status", key[3], hd, what="StereoSGBM")
 
     # -- cv2-style accessors ---------------------------------------------------------------------
     def _get(self, k):
@@ -183,21 +183,14 @@ class StereoSGBM:
     def compute(self, left, right, out=None):
         """disparity * 16 as int16, shape (h, w) (or (n, h, w) for batched input)."""
         import torch
-        is_np = isinstance(left, np.ndarray)
-        if is_np != isinstance(right, np.ndarray):
+        was_np = is_np(left)
+        if was_np != is_np(right):
             raise ValueError("left and right must both be NumPy arrays or both torch tensors")
-        if is_np:
-            _native.require_device()
-            left_t = torch.from_numpy(np.ascontiguousarray(left)).cuda()
-            right_t = torch.from_numpy(np.ascontiguousarray(right)).cuda()
-        else:
-            left_t, right_t = left, right
+        left_t, right_t = to_device(left), to_device(right)
         if left_t.shape != right_t.shape or left_t.dtype != torch.uint8 or right_t.dtype != torch.uint8:
             # cv2: (-215:Assertion failed) left.size() == right.size() && left.type() == right.type() && depth == CV_8U
             raise ValueError("left and right must be uint8 images of identical shape, got %s %s and %s %s"
                              % (tuple(left_t.shape), left_t.dtype, tuple(right_t.shape), right_t.dtype))
-        if not left_t.is_cuda:
-            raise ValueError("tensor inputs must live on the GPU")
         nd = left_t.dim()
         # (h,w) | (h,w,c) | (n,h,w) with c not in (1,3) ... disambiguate by the last dimension
         if nd == 2:
@@ -210,27 +203,23 @@ class StereoSGBM:
             batched, cn = True, left_t.shape[-1]
         else:
             raise ValueError("unsupported image shape %s" % (tuple(left_t.shape),))
-        left_t, right_t = left_t.contiguous(), right_t.contiguous()
         n = left_t.shape[0] if batched else 1
         h, w = (left_t.shape[1], left_t.shape[2]) if batched else (left_t.shape[0], left_t.shape[1])
         dev = left_t.device.index or 0
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):  # camd_sgbm_create allocates on the current device
             self._ensure(w, h, cn, n, dev)
-            if out is None:
-                out = torch.empty((n, h, w), dtype=torch.int16, device=left_t.device)
-            elif out.dtype != torch.int16 or out.numel() != n * h * w or not out.is_contiguous():
-                raise ValueError("out must be a contiguous int16 tensor of %d elements" % (n * h * w))
-            rc = _native.lib().camd_sgbm_compute(
-                self._handle, left_t.data_ptr(), right_t.data_ptr(), w * cn, h * w * cn, out.data_ptr(),
-                w * 2, h * w * 2, n, _native.current_stream())
-            _native.check(rc, "StereoSGBM.compute")
+        if out is None:
+            out = torch.empty((n, h, w), dtype=torch.int16, device=left_t.device)
+        elif out.dtype != torch.int16 or out.numel() != n * h * w or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int16 tensor of %d elements" % (n * h * w))
+        call("camd_sgbm_compute", dev, self._handle, left_t.data_ptr(), right_t.data_ptr(), w * cn, h * w * cn, out.data_ptr(),
+             w * 2, h * w * 2, n, what="StereoSGBM.compute")
         if not self._options.get(6, 7) & 4:
             # (measurement hook 'phases' without the last part: nothing was written to `out`; hand back nothing rather than
             # an uninitialised buffer -- or, for ndarray input, a host copy of one)
             return None
-        res = out.view(n, h, w) if batched else out.view(h, w)
-        if is_np:
-            res = hostio.to_host(res)
+        res = to_caller(out.view(n, h, w) if batched else out.view(h, w), was_np)
+        if was_np:
             self.status()  # the copy synchronised: surface device-side timeouts here at no extra cost
         return res
 
@@ -250,8 +239,7 @@ class StereoSGBM:
         code = {"C": 0, "S": 1, "raw": 2}[which]
         shape = (h, w) if code == 2 else (h, max(g["width1"], 0), g["Dp"])
         buf = torch.empty(shape, dtype=torch.int16, device="cuda:%d" % self._key[3])
-        _native.check(_native.lib().camd_sgbm_debug_copy(self._handle, code, index, buf.data_ptr(),
-                                                         _native.current_stream()))
+        call("camd_sgbm_debug_copy", self._key[3], self._handle, code, index, buf.data_ptr(), what="")
         return buf if code == 2 else buf[..., :g["D"]]
 
     def set_profiling(self, enable=True):

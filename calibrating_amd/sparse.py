@@ -13,61 +13,18 @@ import ctypes
 import numpy as np
 
 from . import _native, hostio
+from ._arrays import VALUE_TYPES, Kinv9, check_array, dtype_name, is_np, mat, positive_hw, to_caller, to_device
+from ._native import call
 
-_VALUE_TYPES = {"float64": _native.VALUE_F64, "float32": _native.VALUE_F32, "uint8": _native.VALUE_U8}
 MAX_DISTANCE = _native.NEAREST_MAX_RADIUS  # interpolate_uvzs(inter_type="nearest"): the search window the kernel supports
 # the plane fit hands over to np.linalg.lstsq on the host when 1 - corr(u, v)^2 of the samples is not above this
 COLLINEAR_TOL = 1e-9
 
 
-def _is_np(a):
-    return isinstance(a, np.ndarray)
-
-
-def _dtype_name(a):
-    return str(a.dtype).replace("torch.", "")
-
-
-def _check_array(a, what):
-    """ndarray or CUDA tensor, checked without touching the device."""
-    if _is_np(a):
-        return
-    if not (hasattr(a, "is_cuda") and hasattr(a, "data_ptr")):
-        raise TypeError("%s must be a NumPy array or a torch CUDA tensor, got %s" % (what, type(a).__name__))
-    if not a.is_cuda:
-        raise ValueError("tensor inputs must live on the GPU (%s)" % what)
-
-
-def _dev(a, device=None, dtype=None):
-    """Contiguous CUDA tensor of an ndarray / CUDA tensor (``dtype``: a NumPy dtype name)."""
-    import torch
-    if _is_np(a):
-        a = np.ascontiguousarray(a, dtype=dtype)
-        _native.require_device()
-        t = torch.from_numpy(a)
-        return t.cuda() if device is None else t.to(device)
-    if dtype is not None:
-        a = a.to(getattr(torch, dtype))
-    if device is not None and a.device != device:
-        raise ValueError("inputs live on different devices: %s and %s" % (a.device, device))
-    return a.contiguous()
-
-
-def _out(t, was_np):
-    return hostio.to_host(t) if was_np else t
-
-
-def _hw(hw, what="hw"):
-    h, w = int(hw[0]), int(hw[1])
-    if h <= 0 or w <= 0:
-        raise ValueError("%s must be a positive (height, width), got %s" % (what, (hw[0], hw[1])))
-    return h, w
-
-
 def _require_finite(uv, what):
     """Non-finite coordinates are refused before any kernel is launched (for tensors: one flag read back)."""
     import torch
-    ok = bool(np.isfinite(uv).all()) if _is_np(uv) else bool(torch.isfinite(uv).all().item())
+    ok = bool(np.isfinite(uv).all()) if is_np(uv) else bool(torch.isfinite(uv).all().item())
     if not ok:
         raise ValueError("%s: u, v must be finite" % what)
 
@@ -80,13 +37,13 @@ def uvzs_to_arr2d(uvs, hw=None, bg_value=0, arr2d=None, values=None):
     ``np.ones(hw, dtype) * bg_value`` casts it.  A given ``arr2d`` is updated in place and returned.  ``hw=None`` is the
     reference's ``np.int32(uvs.max(0)[:2].round()) + 1``: (max u + 1, max v + 1) taken as (h, w) -- its quirk, kept."""
     import torch
-    _check_array(uvs, "uvs")
+    check_array(uvs, "uvs")
     if len(uvs.shape) != 2 or uvs.shape[1] < 2:
         raise ValueError("uvs must be (n, >= 2), got %s" % (tuple(uvs.shape),))
     if values is None:
         uvs, values = uvs[:, :2], uvs[:, 2:]
     else:
-        _check_array(values, "values")
+        check_array(values, "values")
     if len(values.shape) == 1:
         values = values[:, None]
     n = int(uvs.shape[0])
@@ -95,49 +52,46 @@ def uvzs_to_arr2d(uvs, hw=None, bg_value=0, arr2d=None, values=None):
     if n >= 2 ** 31:
         raise ValueError("%d rows do not fit the 32-bit row index" % n)
     channels = int(values.shape[1])
-    vname = _dtype_name(values)
+    vname = dtype_name(values)
     if arr2d is None:
-        if vname not in _VALUE_TYPES:
+        if vname not in VALUE_TYPES:
             raise ValueError("values must be float64, float32 or uint8, got %s" % vname)
         probe = np.ones((1,), vname) * bg_value  # NumPy decides the image's dtype and the background's value
         oname, bg = probe.dtype.name, float(probe[0])
         if hw is None and n == 0:
             raise ValueError("hw=None needs at least one row")
     else:
-        _check_array(arr2d, "arr2d")
-        oname, bg = _dtype_name(arr2d), 0.0
+        check_array(arr2d, "arr2d")
+        oname, bg = dtype_name(arr2d), 0.0
         want = tuple(arr2d.shape[:2]) + ((channels,) if channels >= 2 else ())
         if tuple(arr2d.shape) != want:
             raise ValueError("arr2d %s does not take values of %d channel(s): expected %s" % (tuple(arr2d.shape), channels, want))
-    if oname not in _VALUE_TYPES:
+    if oname not in VALUE_TYPES:
         raise ValueError("the image would be %s; float64, float32 and uint8 are supported" % oname)
     if oname != vname and not np.can_cast(vname, oname, "safe"):
         raise ValueError("values of %s cannot be stored exactly in an image of %s" % (vname, oname))
-    was_np = _is_np(uvs)
-    uv = _dev(uvs[:, :2], dtype="float64")
-    v = _dev(values, uv.device, dtype=oname)
+    was_np = is_np(uvs)
+    uv = to_device(uvs[:, :2], dtype="float64", cast=True)
+    v = to_device(values, dtype=oname, cast=True, device=uv.device)
     if arr2d is None:
         if hw is None:
             m = uv.max(0).values.cpu().numpy()
             if not np.isfinite(m).all():
                 raise ValueError("hw=None: u, v must be finite")
             hw = np.int32(m.round()) + 1
-        h, w = _hw(hw)
+        h, w = positive_hw(hw)
         out = torch.empty((h, w, channels) if channels >= 2 else (h, w), dtype=v.dtype, device=uv.device)
     else:
         h, w = int(arr2d.shape[0]), int(arr2d.shape[1])
-        out = _dev(arr2d, uv.device)
+        out = to_device(arr2d, device=uv.device)
         if h == 0 or w == 0:
             return arr2d
-    with torch.cuda.device(uv.device):
-        owner = torch.empty((h, w), dtype=torch.int32, device=uv.device)
-        rc = _native.lib().camd_uvzs_to_arr2d(uv.data_ptr(), n, 2, w, h, v.data_ptr(), channels, _VALUE_TYPES[oname], bg,
-                                              0 if arr2d is None else 1, out.data_ptr(), owner.data_ptr(),
-                                              _native.current_stream())
-    _native.check(rc, "uvzs_to_arr2d")
+    owner = torch.empty((h, w), dtype=torch.int32, device=uv.device)
+    call("camd_uvzs_to_arr2d", uv.device, uv.data_ptr(), n, 2, w, h, v.data_ptr(), channels, VALUE_TYPES[oname], bg,
+         0 if arr2d is None else 1, out.data_ptr(), owner.data_ptr(), what="uvzs_to_arr2d")
     if arr2d is None:
-        return _out(out, was_np)
-    if _is_np(arr2d):
+        return to_caller(out, was_np)
+    if is_np(arr2d):
         np.copyto(arr2d, hostio.to_host(out))
     elif out.data_ptr() != arr2d.data_ptr():
         arr2d.copy_(out)
@@ -150,37 +104,34 @@ def arr2d_to_uvzs(arr2d, mask=None):
     pixels in row-major order.  The dtype is NumPy's promotion of int64 grids with ``arr2d`` (float -> float64,
     integers / bool -> int64).  A mask of any dtype is taken as boolean."""
     import torch
-    _check_array(arr2d, "arr2d")
+    check_array(arr2d, "arr2d")
     if len(arr2d.shape) != 2:
         raise ValueError("arr2d must be (h, w), got %s" % (tuple(arr2d.shape),))
     h, w = (int(s) for s in arr2d.shape)
-    oname = np.result_type(np.int64, np.dtype(_dtype_name(arr2d))).name
+    oname = np.result_type(np.int64, np.dtype(dtype_name(arr2d))).name
     if oname not in ("float64", "int64"):
-        raise ValueError("arr2d of %s is not supported" % _dtype_name(arr2d))
+        raise ValueError("arr2d of %s is not supported" % dtype_name(arr2d))
     if mask is not None:
-        _check_array(mask, "mask")
+        check_array(mask, "mask")
         if tuple(mask.shape) != (h, w):
             raise ValueError("mask %s does not match arr2d %s" % (tuple(mask.shape), (h, w)))
-    was_np = _is_np(arr2d)
+    was_np = is_np(arr2d)
     if h == 0 or w == 0:
         return np.zeros((0, 3), oname) if was_np else torch.zeros((0, 3), dtype=getattr(torch, oname), device=arr2d.device)
-    a = _dev(arr2d, dtype=oname)
+    a = to_device(arr2d, dtype=oname, cast=True)
     lib = _native.lib()
-    with torch.cuda.device(a.device):
-        if mask is None:
-            rows = torch.empty((h * w, 3), dtype=a.dtype, device=a.device)
-            rc = lib.camd_arr2d_to_uvzs(a.data_ptr(), w, h, int(oname == "int64"), rows.data_ptr(), _native.current_stream())
-            _native.check(rc, "arr2d_to_uvzs")
-            return _out(rows, was_np)
-        m = _dev(np.asarray(mask != 0) if _is_np(mask) else (mask != 0), a.device).view(torch.uint8)
+    if mask is None:
         rows = torch.empty((h * w, 3), dtype=a.dtype, device=a.device)
-        count = torch.zeros(1, dtype=torch.int64, device=a.device)
-        ws = torch.empty(lib.camd_arr2d_mask_workspace_bytes(h), dtype=torch.uint8, device=a.device)
-        rc = lib.camd_arr2d_to_uvzs_masked(a.data_ptr(), m.data_ptr(), w, h, int(oname == "int64"), rows.data_ptr(), h * w,
-                                           count.data_ptr(), ws.data_ptr(), _native.current_stream())
-    _native.check(rc, "arr2d_to_uvzs")
+        call("camd_arr2d_to_uvzs", a.device, a.data_ptr(), w, h, int(oname == "int64"), rows.data_ptr(), what="arr2d_to_uvzs")
+        return to_caller(rows, was_np)
+    m = to_device(np.asarray(mask != 0) if is_np(mask) else (mask != 0), device=a.device).view(torch.uint8)
+    rows = torch.empty((h * w, 3), dtype=a.dtype, device=a.device)
+    count = torch.zeros(1, dtype=torch.int64, device=a.device)
+    ws = torch.empty(lib.camd_arr2d_mask_workspace_bytes(h), dtype=torch.uint8, device=a.device)
+    call("camd_arr2d_to_uvzs_masked", a.device, a.data_ptr(), m.data_ptr(), w, h, int(oname == "int64"), rows.data_ptr(), h * w,
+         count.data_ptr(), ws.data_ptr(), what="arr2d_to_uvzs")
     n = int(count.item())  # synchronises: the output length is data dependent
-    return _out(rows[:n], was_np)
+    return to_caller(rows[:n], was_np)
 
 
 # ---- c. / d. interpolation -------------------------------------------------------------------------------------------
@@ -199,13 +150,13 @@ def interpolate_sparse2d(sparse2d, constrained_type=None, inter_type="lstsq"):
     """``interpolate_uvzs`` of the non-zero, finite pixels of an image (utils.py:347-353)."""
     import torch
     _check_interpolation(constrained_type, inter_type)
-    _check_array(sparse2d, "sparse2d")
+    check_array(sparse2d, "sparse2d")
     if len(sparse2d.shape) != 2:
         raise ValueError("sparse2d must be (h, w), got %s" % (tuple(sparse2d.shape),))
-    was_np = _is_np(sparse2d)
-    s = _dev(sparse2d)
+    was_np = is_np(sparse2d)
+    s = to_device(sparse2d)
     uvzs = arr2d_to_uvzs(s, (s != 0) & torch.isfinite(s))
-    return _out(interpolate_uvzs(uvzs, tuple(s.shape[:2]), constrained_type, inter_type), was_np)
+    return to_caller(interpolate_uvzs(uvzs, tuple(s.shape[:2]), constrained_type, inter_type), was_np)
 
 
 def interpolate_uvzs(uvzs, hw=None, constrained_type=None, inter_type="lstsq", distance=2, resize_hw=None):
@@ -222,7 +173,7 @@ def interpolate_uvzs(uvzs, hw=None, constrained_type=None, inter_type="lstsq", d
     ``FeatureMatchingAsStereoMatching`` does with its 1/8 grid, written once at full resolution."""
     import torch
     _check_interpolation(constrained_type, inter_type)
-    _check_array(uvzs, "uvzs")
+    check_array(uvzs, "uvzs")
     if len(uvzs.shape) != 2 or uvzs.shape[1] < 3 or (inter_type == "lstsq" and uvzs.shape[1] != 3):
         raise ValueError("uvzs must be (n, 3), got %s" % (tuple(uvzs.shape),))
     if resize_hw is not None and inter_type != "nearest":
@@ -231,7 +182,7 @@ def interpolate_uvzs(uvzs, hw=None, constrained_type=None, inter_type="lstsq", d
     if n >= 2 ** 31:
         raise ValueError("%d samples do not fit the 32-bit sample index" % n)
     distance = float(distance)
-    was_np = _is_np(uvzs)
+    was_np = is_np(uvzs)
     if hw is None:
         if n == 0:
             raise ValueError("hw=None needs at least one sample")
@@ -239,8 +190,8 @@ def interpolate_uvzs(uvzs, hw=None, constrained_type=None, inter_type="lstsq", d
         if not np.isfinite(m).all():
             raise ValueError("interpolate_uvzs: u, v must be finite")
         hw = int(m[1]) + 2, int(m[0]) + 2
-    h, w = _hw(hw)
-    oh, ow = (h, w) if resize_hw is None else _hw(resize_hw, "resize_hw")
+    h, w = positive_hw(hw)
+    oh, ow = (h, w) if resize_hw is None else positive_hw(resize_hw, "resize_hw")
     if n == 0:
         if was_np:
             return np.zeros((oh, ow), uvzs.dtype)
@@ -256,31 +207,28 @@ def interpolate_uvzs(uvzs, hw=None, constrained_type=None, inter_type="lstsq", d
         if h > 65535 or oh > 65535:
             raise ValueError("grids of more than 65535 rows are not supported")
     _require_finite(uvzs[:, :2], "interpolate_uvzs")
-    zname = "float32" if _dtype_name(uvzs) == "float32" else "float64"
-    uv = _dev(uvzs[:, :2], dtype="float64")
-    z = _dev(uvzs[:, 2], uv.device, dtype=zname)
-    st = _native.current_stream
-    with torch.cuda.device(uv.device):
-        out = torch.empty((oh, ow), dtype=torch.float32, device=uv.device)
-        if inter_type == "nearest":
-            ncell = bw.value * bh.value
-            counts = torch.empty(ncell, dtype=torch.int32, device=uv.device)
-            _native.check(lib.camd_sparse_bin_count(uv.data_ptr(), n, 2, w, h, distance, counts.data_ptr(), st()),
-                          "interpolate_uvzs")
-            start = torch.zeros(ncell + 1, dtype=torch.int32, device=uv.device)
-            torch.cumsum(counts, 0, dtype=torch.int32, out=start[1:])  # the exclusive scan between count and fill
-            cursor = start[:-1].clone()
-            suv = torch.empty((n, 2), dtype=torch.float64, device=uv.device)
-            sidx = torch.empty(n, dtype=torch.int32, device=uv.device)
-            _native.check(lib.camd_sparse_bin_fill(uv.data_ptr(), n, 2, w, h, distance, cursor.data_ptr(), n, suv.data_ptr(),
-                                                   sidx.data_ptr(), st()), "interpolate_uvzs")
-            rc = lib.camd_nearest_fill(suv.data_ptr(), sidx.data_ptr(), start.data_ptr(), z.data_ptr(), _VALUE_TYPES[zname],
-                                       w, h, distance, out.data_ptr(), ow, oh, st())
-            _native.check(rc, "interpolate_uvzs")
-        else:
-            a, b, c = _fit_plane(lib, uv, z, zname, n)
-            _native.check(lib.camd_plane_eval(a, b, c, w, h, out.data_ptr(), st()), "interpolate_uvzs")
-    return _out(out, was_np)
+    zname = "float32" if dtype_name(uvzs) == "float32" else "float64"
+    uv = to_device(uvzs[:, :2], dtype="float64", cast=True)
+    z = to_device(uvzs[:, 2], dtype=zname, cast=True, device=uv.device)
+    dev, who = uv.device, "interpolate_uvzs"
+    out = torch.empty((oh, ow), dtype=torch.float32, device=dev)
+    if inter_type == "nearest":
+        ncell = bw.value * bh.value
+        counts = torch.empty(ncell, dtype=torch.int32, device=dev)
+        call("camd_sparse_bin_count", dev, uv.data_ptr(), n, 2, w, h, distance, counts.data_ptr(), what=who)
+        start = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
+        torch.cumsum(counts, 0, dtype=torch.int32, out=start[1:])  # the exclusive scan between count and fill
+        cursor = start[:-1].clone()
+        suv = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        sidx = torch.empty(n, dtype=torch.int32, device=dev)
+        call("camd_sparse_bin_fill", dev, uv.data_ptr(), n, 2, w, h, distance, cursor.data_ptr(), n, suv.data_ptr(),
+             sidx.data_ptr(), what=who)
+        call("camd_nearest_fill", dev, suv.data_ptr(), sidx.data_ptr(), start.data_ptr(), z.data_ptr(), VALUE_TYPES[zname],
+             w, h, distance, out.data_ptr(), ow, oh, what=who)
+    else:
+        a, b, c = _fit_plane(lib, uv, z, zname, n)
+        call("camd_plane_eval", dev, a, b, c, w, h, out.data_ptr(), what=who)
+    return to_caller(out, was_np)
 
 
 def _fit_plane(lib, uv, z, zname, n):
@@ -290,8 +238,8 @@ def _fit_plane(lib, uv, z, zname, n):
     blocks = lib.camd_plane_sums_blocks(n)
     partials = torch.empty(blocks * 9, dtype=torch.float64, device=uv.device)
     sums = torch.empty(9, dtype=torch.float64, device=uv.device)
-    _native.check(lib.camd_plane_sums(uv.data_ptr(), 2, z.data_ptr(), _VALUE_TYPES[zname], n, partials.data_ptr(),
-                                      sums.data_ptr(), _native.current_stream()), "interpolate_uvzs")
+    call("camd_plane_sums", uv.device, uv.data_ptr(), 2, z.data_ptr(), VALUE_TYPES[zname], n, partials.data_ptr(),
+         sums.data_ptr(), what="interpolate_uvzs")
     suu, suv, su, svv, sv, cnt, suz, svz, sz = (float(x) for x in sums.cpu().numpy())
     mu, mv, mz = su / cnt, sv / cnt, sz / cnt
     cuu, cvv, cuv = suu - su * mu, svv - sv * mv, suv - su * mv
@@ -318,8 +266,8 @@ def matched_uvs_to_zs(uvs1, uvs2, K1, K2, T_1to2):
     (epipolar_geometry.py:84-97): per match the least-squares solution of [-R X1, X2] (z1, z2)^T = t.  ``uvs*`` (n, 2)
     pixels, ``T_1to2`` 4x4 (or 3x4) with X2 = R X1 + t.  float64."""
     import torch
-    _check_array(uvs1, "uvs1")
-    _check_array(uvs2, "uvs2")
+    check_array(uvs1, "uvs1")
+    check_array(uvs2, "uvs2")
     if len(uvs1.shape) != 2 or uvs1.shape[1] != 2 or tuple(uvs2.shape) != tuple(uvs1.shape):
         raise ValueError("uvs1, uvs2 must both be (n, 2), got %s and %s" % (tuple(uvs1.shape), tuple(uvs2.shape)))
     T = np.asarray(T_1to2, np.float64)
@@ -327,17 +275,13 @@ def matched_uvs_to_zs(uvs1, uvs2, K1, K2, T_1to2):
         raise ValueError("T_1to2 must be 4x4 or 3x4, got %s" % (T.shape,))
     T4 = np.eye(4)
     T4[:3] = T[:3]
-    Kinv = [np.ascontiguousarray(np.linalg.inv(np.asarray(K, np.float64)[:3, :3])).reshape(9) for K in (K1, K2)]
-    was_np = _is_np(uvs1)
+    Kinv = [Kinv9(K) for K in (K1, K2)]
     n = int(uvs1.shape[0])
-    a = _dev(uvs1, dtype="float64")
-    b = _dev(uvs2, a.device, dtype="float64")
-    T4 = np.ascontiguousarray(T4).reshape(16)
-    with torch.cuda.device(a.device):
-        zs = torch.empty((2, n), dtype=torch.float64, device=a.device)
-        rc = _native.lib().camd_matched_uvs_to_zs(a.data_ptr(), b.data_ptr(), n, Kinv[0].ctypes.data, Kinv[1].ctypes.data,
-                                                  T4.ctypes.data, zs[0].data_ptr(), zs[1].data_ptr(), _native.current_stream())
-    _native.check(rc, "matched_uvs_to_zs")
-    if was_np:
-        zs = hostio.to_host(zs)
+    a = to_device(uvs1, dtype="float64", cast=True)
+    b = to_device(uvs2, dtype="float64", cast=True, device=a.device)
+    T4 = mat(T4, 16)
+    zs = torch.empty((2, n), dtype=torch.float64, device=a.device)
+    call("camd_matched_uvs_to_zs", a.device, a.data_ptr(), b.data_ptr(), n, Kinv[0].ctypes.data, Kinv[1].ctypes.data,
+         T4.ctypes.data, zs[0].data_ptr(), zs[1].data_ptr(), what="matched_uvs_to_zs")
+    zs = to_caller(zs, is_np(uvs1))
     return dict(zs1=zs[0], zs2=zs[1])

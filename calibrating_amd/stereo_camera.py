@@ -22,7 +22,8 @@ in -> torch tensors out, zero-copy.
 """
 import numpy as np
 
-from . import _native, geometry, hostio, imgproc
+from . import geometry, hostio, imgproc
+from ._arrays import is_np, to_caller, to_device
 from .camera import Cam, read_record, write_record
 from .stereo_matching import SemiGlobalBlockMatching
 
@@ -322,23 +323,16 @@ class Stereo:
                 return np.array(im.convert("RGB"))
         return path_or_np
 
-    @staticmethod
-    def _to_dev(img):
-        import torch
-        if isinstance(img, np.ndarray):
-            # (a plain pageable copy: 0.12 ms per 1080p image on the GPU box; staging through a page-locked block
-            # was measured 10x slower, see hostio)
-            return torch.from_numpy(np.ascontiguousarray(img)).cuda(), True
-        return img, False
-
+    # (images go up as plain pageable copies, ``to_device``: 0.12 ms per 1080p image on the GPU box; staging through a
+    # page-locked block was measured 10x slower, see hostio)
     def rectify(self, img1, img2):
-        i1, np1 = self._to_dev(self._get_img(img1))
-        i2, _ = self._to_dev(self._get_img(img2))
+        img1, img2 = self._get_img(img1), self._get_img(img2)
+        i1, i2 = to_device(img1), to_device(img2)
         tb = self._tables(i1.device)
         shift = self.min_disparity if getattr(self, "translation_rectify_img", None) else 0
         rectify_img1 = imgproc.remap(i1, tb["map1x"], tb["map1y"], imgproc.INTER_LANCZOS4)
         rectify_img2 = imgproc.remap(i2, tb["map2x"], tb["map2y"], imgproc.INTER_LANCZOS4, x_shift=shift)
-        if np1:
+        if is_np(img1):
             return hostio.to_host(rectify_img1, rectify_img2)
         return [rectify_img1, rectify_img2]
 
@@ -351,20 +345,19 @@ class Stereo:
         return self._dev[key]
 
     def unrectify_depth(self, depth):
-        d, was_np = self._to_dev(depth)
+        d = to_device(depth)
         mx, my = self._unrectify_tables(d.device)
         M = self.R1.T @ np.linalg.inv(self.K)
-        out = imgproc.unrectify_depth(d, M[2], mx, my)
-        return hostio.to_host(out) if was_np else out
+        return to_caller(imgproc.unrectify_depth(d, M[2], mx, my), is_np(depth))
 
     def undistort_img(self, img1):
-        i1, was_np = self._to_dev(self._get_img(img1))
+        img1 = self._get_img(img1)
+        i1 = to_device(img1)
         key = "undist:" + str(i1.device)
         if key not in self._dev:
             self._dev[key] = imgproc.undistort_maps_device(self.cam1.K, self.cam1.D, self.cam1.xy, device=i1.device)
         mxy, ma = self._dev[key]
-        out = imgproc.remap_fixed_bilinear(i1, mxy, ma)
-        return hostio.to_host(out) if was_np else out
+        return to_caller(imgproc.remap_fixed_bilinear(i1, mxy, ma), is_np(img1))
 
     def _distort_table(self, device):
         """The int32 source-index table of ``distort_depth`` (imgproc.distort_index_map), built once per device and
@@ -400,11 +393,8 @@ class Stereo:
         gather.  ``depth``: (h, w) or (n, h, w) of camera 1's size, float64 or float32, ndarray -> ndarray, CUDA tensor
         -> tensor; shape and dtype are kept.  A rig with a target outside the image raises ``IndexError``."""
         self._check_distort_input(depth)
-        if isinstance(depth, np.ndarray):
-            _native.require_device()
-        d, was_np = self._to_dev(depth)
-        out = imgproc.distort_depth(d, self._distort_table(d.device))
-        return hostio.to_host(out) if was_np else out
+        d = to_device(depth)
+        return to_caller(imgproc.distort_depth(d, self._distort_table(d.device)), is_np(depth))
 
     def set_stereo_matching(self, stereo_matching, max_depth=None, translation_rectify_img=None):
         """Install the matcher plugin (:466-489).  ``max_depth`` (default MAX_DEPTH) fixes
@@ -495,7 +485,7 @@ class Stereo:
         want, return_unrectify_depth, distort = self._asked("get_depth", keys, return_unrectify_depth, return_distort_depth)
         distort_img1 = img1  # :530 hands back the argument itself
         img1, img2 = self._get_img(img1), self._get_img(img2)
-        was_np = isinstance(img1, np.ndarray)
+        was_np = is_np(img1)
         sink, result = None, {}
 
         def emit(**tensors):
@@ -506,7 +496,7 @@ class Stereo:
                         sink.send(k, t)
 
         # camera 1 first: its rectification and undistortion are queued before camera 2's pixels are copied
-        i1, _ = self._to_dev(img1)
+        i1 = to_device(img1)
         if was_np:
             sink = hostio.Sink(i1.device)
         tb = self._tables(i1.device)
@@ -516,7 +506,7 @@ class Stereo:
         emit(rectify_img1=rectify_img1)
         if return_unrectify_depth and want("undistort_img1"):
             emit(undistort_img1=self.undistort_img(i1))  # independent of the matcher: its copy hides under SGBM
-        i2, _ = self._to_dev(img2)
+        i2 = to_device(img2)
         shift = self.min_disparity if getattr(self, "translation_rectify_img", None) else 0
         rectify_img2 = imgproc.remap(i2, tb["map2x"], tb["map2y"], imgproc.INTER_LANCZOS4, x_shift=shift)
         emit(rectify_img2=rectify_img2)
@@ -587,8 +577,7 @@ class Stereo:
         assert hasattr(self, "stereo_matching"), "Please stereo.set_stereo_matching(stereo_matching)"
         want, return_unrectify_depth, distort = self._asked("get_depth_batch", keys, return_unrectify_depth,
                                                             return_distort_depth)
-        i1, was_np = self._to_dev(imgs1)
-        i2, _ = self._to_dev(imgs2)
+        i1, i2, was_np = to_device(imgs1), to_device(imgs2), is_np(imgs1)
         # (the two cameras of a rig may differ in resolution -- each is rectified through its own maps,
         # stereo_camera.py:159-165,216-228 -- so only the pair count and the channel count have to agree)
         if i1.dim() != 4 or i2.dim() != 4 or i1.shape[0] != i2.shape[0] or i1.shape[3] != i2.shape[3]:

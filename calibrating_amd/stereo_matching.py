@@ -12,7 +12,8 @@ gets NumPy arrays, as in the reference.  ``FeatureMatchingAsStereoMatching`` (:1
 """
 import numpy as np
 
-from . import hostio, resize as _resize
+from . import resize as _resize
+from ._arrays import is_np, to_caller, to_device
 from .sgbm import MODE_SGBM, StereoSGBM_create
 
 
@@ -85,14 +86,11 @@ class SemiGlobalBlockMatching(MetaStereoMatching):
         return self._disparity_from_disp16(sdisp16, hw, sw, batched=True)
 
     def __call__(self, img1, img2):
-        import torch
-        is_np = isinstance(img1, np.ndarray)
-        if is_np:
-            img1, img2 = torch.from_numpy(np.ascontiguousarray(img1)).cuda(), \
-                torch.from_numpy(np.ascontiguousarray(img2)).cuda()
+        was_np = is_np(img1)
+        if was_np:
+            img1, img2 = to_device(img1), to_device(img2)
         sdisp16, sw = self.compute_disp16(img1, img2)
-        disparity = self._disparity_from_disp16(sdisp16, tuple(img1.shape[:2]), sw)
-        return hostio.to_host(disparity) if is_np else disparity
+        return to_caller(self._disparity_from_disp16(sdisp16, tuple(img1.shape[:2]), sw), was_np)
 
 
 class FeatureMatchingAsStereoMatching(MetaStereoMatching):
