@@ -5,9 +5,10 @@
 //   Cam.project_cam2_depth       (camera.py:298-309)  the three above composed; here ONE fused scatter kernel
 //   utils.point_cloud_to_arr2d   (utils.py:254-317)   the same z-buffer carrying a payload (values of the winning point)
 //   utils.get_reproject_remap    (utils.py:332-344)   ... whose payload is the (u, v) of the source grid cell
-// float64 throughout like the reference's NumPy.  Matrix products are evaluated left to right without
-// contraction; NumPy's BLAS may order / fuse them differently, so parity with the oracle is to ~1 ulp on the
-// points and exact on the z-buffer except where a projection lands within rounding error of x.5.
+// float64 throughout like the reference's NumPy.  Every matrix product is the chain dot3 / dot4 below: left to right,
+// a plain first product, then fused multiply-adds.  oracle/pointcloud_ref.c states the same arithmetic as serial loops,
+// and the tests hold every entry point of this file to it bit for bit, on every point and every pixel -- ties, image
+// edges, half-way projections and NaN / inf included; that oracle in turn reproduces the reference's recorded runs.
 #include "common.hpp"
 #include "compact.hpp"
 

@@ -91,9 +91,11 @@ def point_cloud_to_depth(points, K, xy, bg_value=0):
 
 def project_depth(depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
     """depth image of camera 2 seen from camera 1: depth_to_point_cloud -> apply_T -> point_cloud_to_depth
-    (camera.py:298-309) as one scatter pass over the sampling grid."""
+    (camera.py:298-309) as one scatter pass over the sampling grid.  uint16 depth is millimetres, as in the
+    ``depth_to_point_cloud`` the reference composes it from."""
     import torch
-    d, was_np = _f64(depth2)
+    check_array(depth2, "depth2")
+    d, was_np = _depth_metres(depth2, dtype_name(depth2)), is_np(depth2)
     h2, w2 = d.shape
     w1, h1 = int(xy1[0]), int(xy1[1])
     K2inv, Tm, K1m = Kinv9(K2), mat(T_2in1, 16), K9(K1)

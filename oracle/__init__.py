@@ -35,7 +35,8 @@ class Switches(ctypes.Structure):
 
 def build(force=False):
     """Compile oracle/*.c with gcc (Makefile in this directory)."""
-    srcs = [os.path.join(_HERE, f) for f in ("sgbm_ref.c", "remap_ref.c", "depth_ref.c", "resize_ref.c", "oracle.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("sgbm_ref.c", "remap_ref.c", "depth_ref.c", "resize_ref.c",
+                                             "pointcloud_ref.c", "oracle.h")]
     stale = force or not os.path.exists(_LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(_LIB_PATH) for s in srcs)
     if stale:
@@ -258,6 +259,130 @@ def unrectify_depth(depth, M_row2, mapx, mapy):
                                  _p(mapx, ctypes.c_float), _p(mapy, ctypes.c_float),
                                  _p(out, ctypes.c_double), ow, oh)
     return out
+
+
+# ---- the point-cloud and z-buffer family (pointcloud_ref.c): the exact oracle of calibrating_amd.pointcloud ----------
+def _metres(depth):
+    """float64 (h, w) depth; uint16 is millimetres through float32, as in the reference (utils.py:218-219)."""
+    depth = np.asarray(depth)
+    assert depth.ndim == 2
+    if depth.dtype == np.uint16:
+        depth = np.float32(depth / 1000.0)
+    return np.ascontiguousarray(depth, np.float64)
+
+
+def _mat(m, n):
+    a = np.ascontiguousarray(m, np.float64).reshape(-1)
+    assert a.size == n, (a.size, n)
+    return a
+
+
+def _K9(K):
+    return _mat(np.asarray(K, np.float64)[:3, :3], 9)
+
+
+def _Kinv9(K):
+    return _mat(np.linalg.inv(np.asarray(K, np.float64)[:3, :3]), 9)
+
+
+def point_cloud_grid(w, h, rate):
+    gw, gh = ctypes.c_int(), ctypes.c_int()
+    if lib().oracle_point_cloud_grid(int(w), int(h), ctypes.c_double(rate), ctypes.byref(gw), ctypes.byref(gh)):
+        raise ValueError("oracle_point_cloud_grid: bad size / interpolation rate")
+    return gw.value, gh.value
+
+
+def depth_to_point_cloud(depth, K, interpolation_rate=1, return_xyzuv=False):
+    """utils.depth_to_point_cloud: (N, 3) points of the non-zero cells in row-major order, or (N, 5) xyzuv."""
+    d = _metres(depth)
+    h, w = d.shape
+    rate = float(interpolation_rate)
+    gw, gh = point_cloud_grid(w, h, rate)
+    pts = np.empty((gw * gh, 3), np.float64)
+    uv = np.empty((gw * gh, 2), np.float64)
+    fn = lib().oracle_depth_to_point_cloud
+    fn.restype = ctypes.c_longlong
+    n = fn(_p(d, ctypes.c_double), w, h, _p(_Kinv9(K), ctypes.c_double), ctypes.c_double(rate),
+           _p(pts, ctypes.c_double), _p(uv, ctypes.c_double))
+    assert 0 <= n <= gw * gh
+    return np.concatenate([pts[:n], uv[:n]], 1) if return_xyzuv else pts[:n].copy()
+
+
+def apply_T_to_point_cloud(T, cloud):
+    """utils.apply_T_to_point_cloud: (T @ [p, 1])[:3] per row, extra columns carried over."""
+    cloud = np.asarray(cloud, np.float64)
+    xyz = np.ascontiguousarray(cloud[:, :3])
+    out = np.empty_like(xyz)
+    lib().oracle_apply_T(_p(xyz, ctypes.c_double), ctypes.c_size_t(len(xyz)), _p(_mat(T, 16), ctypes.c_double),
+                         _p(out, ctypes.c_double))
+    return np.concatenate([out, cloud[:, 3:]], 1) if cloud.shape[1] > 3 else out
+
+
+def zbuffer_points(points, K, xy):
+    """-> (owner int64 (h, w): the row of ``points`` that holds each pixel, -1 where nobody; zs (h, w): its depth)."""
+    p = np.ascontiguousarray(points, np.float64)
+    assert p.ndim == 2 and p.shape[1] >= 3
+    w, h = int(xy[0]), int(xy[1])
+    owner, zs = np.empty((h, w), np.int64), np.empty((h, w), np.float64)
+    if lib().oracle_zbuffer_points(_p(p, ctypes.c_double), ctypes.c_size_t(p.shape[0]), int(p.shape[1]),
+                                   _p(_K9(K), ctypes.c_double), w, h, _p(owner, ctypes.c_int64), _p(zs, ctypes.c_double)):
+        raise ValueError("oracle_zbuffer_points: bad arguments")
+    return owner, zs
+
+
+def zbuffer_grid(depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
+    """-> (owner int64 (h1, w1): the row-major cell of camera 2's sampling grid, -1 where nobody; zs (h1, w1))."""
+    d = _metres(depth2)
+    h2, w2 = d.shape
+    w1, h1 = int(xy1[0]), int(xy1[1])
+    owner, zs = np.empty((h1, w1), np.int64), np.empty((h1, w1), np.float64)
+    if lib().oracle_zbuffer_grid(_p(d, ctypes.c_double), w2, h2, _p(_Kinv9(K2), ctypes.c_double),
+                                 _p(_mat(T_2in1, 16), ctypes.c_double), _p(_K9(K1), ctypes.c_double),
+                                 ctypes.c_double(interpolation_rate), w1, h1, _p(owner, ctypes.c_int64),
+                                 _p(zs, ctypes.c_double)):
+        raise ValueError("oracle_zbuffer_grid: bad arguments")
+    return owner, zs
+
+
+def _gather(owner, payload, bg_value):
+    """Image of payload[owner] (``payload`` (N,) or (N, C)), ``bg_value`` where owner < 0."""
+    payload = np.asarray(payload)
+    if payload.ndim == 2 and payload.shape[1] == 1:
+        payload = payload[:, 0]
+    out = np.full(owner.shape + payload.shape[1:], bg_value, payload.dtype)
+    hit = owner >= 0
+    out[hit] = payload[owner[hit]]
+    return out
+
+
+def point_cloud_to_depth(points, K, xy, bg_value=0):
+    owner, zs = zbuffer_points(points, K, xy)
+    return np.where(owner >= 0, zs, np.float64(bg_value))
+
+
+def point_cloud_to_arr2d(points, K, xy, values=None, bg_value=0):
+    if values is None:
+        return point_cloud_to_depth(points, K, xy, bg_value)
+    return _gather(zbuffer_points(points, K, xy)[0], values, bg_value)
+
+
+def project_depth(depth2, K2, T_2in1, K1, xy1, interpolation_rate=1):
+    owner, zs = zbuffer_grid(depth2, K2, T_2in1, K1, xy1, interpolation_rate)
+    return np.where(owner >= 0, zs, 0.0)
+
+
+def get_reproject_remap(K1, K2, T_2in1, depth2, xy1, interpolation_rate=1):
+    """(2, h1, w1) float32: np.float32(x / rate), np.float32(y / rate) of the winning grid cell, -1 where nobody."""
+    d = _metres(depth2)
+    rate = float(interpolation_rate)
+    gw, _ = point_cloud_grid(d.shape[1], d.shape[0], rate)
+    owner, _ = zbuffer_grid(d, K2, T_2in1, K1, xy1, rate)
+    hit = owner >= 0
+    maps = np.full((2,) + owner.shape, -1, np.float32)
+    x, y = owner[hit] % gw, owner[hit] // gw
+    maps[0][hit] = np.float32(x if rate == 1 else x / rate)
+    maps[1][hit] = np.float32(y if rate == 1 else y / rate)
+    return maps
 
 
 def set_switches(lanczos_fix_group_lo=4, bt_border_raw_tab0=1, cost_saturate=1, way3_stripes=4, way3_simd_lanes=8):

@@ -123,6 +123,24 @@ void oracle_disp_to_depth(const int16_t* disp16, const uint8_t* valid_mask, int 
 void oracle_unrectify_depth(const double* depth, int w, int h, const double Mrow2[3],
                             const float* mapx, const float* mapy, double* out, int ow, int oh);
 
+/* ---- the point-cloud and z-buffer family (pointcloud_ref.c): serial loops in index order, every dot product the
+ * chain fma(a2,b2, fma(a1,b1, a0*b0)) that csrc/pointcloud.hip documents.  The z-buffers return WINNERS, not images:
+ * owner[pix] = index of the source that holds the pixel (-1: nobody), zs[pix] = its projected depth (0 where nobody). */
+/* utils.depth_to_point_cloud: points (n, 3) and uv (n, 2) of the non-zero cells of the sampling grid in row-major
+ * order (either may be NULL); room for gw * gh rows.  Returns n, or -1 on a bad size / rate. */
+long long oracle_depth_to_point_cloud(const double* depth, int w, int h, const double Kinv[9], double rate,
+                                      double* points, double* uv);
+/* utils.apply_T_to_point_cloud on packed (n, 3) rows */
+void oracle_apply_T(const double* points, size_t n, const double T[16], double* out);
+/* utils.point_cloud_to_arr2d's scatter: source = row of `points` (rows `stride` doubles apart) */
+int oracle_zbuffer_points(const double* points, size_t n, int stride, const double K[9], int w, int h,
+                          int64_t* owner, double* zs);
+/* Cam.project_cam2_depth / utils.get_reproject_remap: source = row-major cell of camera 2's sampling grid */
+int oracle_zbuffer_grid(const double* depth2, int w2, int h2, const double K2inv[9], const double T[16],
+                        const double K1[9], double rate, int w1, int h1, int64_t* owner, double* zs);
+/* the sampling grid of a w x h depth at `rate` */
+int oracle_point_cloud_grid(int w, int h, double rate, int* gw, int* gh);
+
 #ifdef __cplusplus
 }
 #endif

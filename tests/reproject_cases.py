@@ -19,8 +19,9 @@ RATE_NATIVE = 420 / 380 * 1.5     # what get_appropriate_interpolation_rate give
 PRECONDITION_RATES = (1, 1.5, RATE_NATIVE)
 GPU_RATES = (1, 1.5, 0.75)
 GOLDEN_RATES = (1, 1.5)           # the two rates the reference itself was run at (tests/golden/reference_reproject.npz)
-CAP = 0.9999                      # share of pixels that must be bit-equal: the cap of test_project_cam2_depth, for
-                                  # projections that land within rounding error of x.5
+CAP = 0.9999                      # share of pixels that must be bit-equal with a NUMPY restatement, and only with one:
+                                  # its matrix products are NumPy's BLAS, whose rounding belongs to the machine.  The
+                                  # kernels are held to the exact C oracle (oracle/pointcloud_ref.c) on every pixel.
 
 
 def scene_depth(seed, h, w, holes=0.2):

@@ -1,7 +1,8 @@
 """The shared compaction (csrc/compact.hpp: row count -> exclusive scan -> ordered emit) through every entry point that
 uses it, at the sizes where it can go wrong: the edges of a 64-lane wave and of a 256-element chunk in a row (widths),
 the carry of the scan between its 256-row iterations (heights), and a capacity below the total (-m gpu).  Expected values
-are plain NumPy; every index, coordinate and order is compared with array_equal."""
+are plain NumPy; every index, coordinate and order is compared with array_equal, and the points of
+depth_to_point_cloud -- a matrix product in NumPy -- bit for bit with the exact C oracle (oracle/pointcloud_ref.c)."""
 import numpy as np
 import pytest
 import torch
@@ -61,7 +62,7 @@ def test_flow_to_matched_uvs(h, w):
 
 @pytest.mark.parametrize("rate", [1, 1.5])  # 1.5: the sampling grid is wider than the depth
 @pytest.mark.parametrize("h,w", SHAPES)
-def test_depth_to_point_cloud(h, w, rate):
+def test_depth_to_point_cloud(h, w, rate, oracle):
     z = 1.0 + np.random.default_rng(w * 13 + h).random((h, w))
     for name, mask in _masks(h, w).items():
         depth = np.where(mask, z, 0.0)
@@ -70,6 +71,7 @@ def test_depth_to_point_cloud(h, w, rate):
         assert got.shape == want.shape and got.dtype == np.float64, name
         assert np.array_equal(got[:, 3:], want[:, 3:]), name                          # same pixels in the same order
         assert np.allclose(got[:, :3], want[:, :3], rtol=1e-13, atol=1e-13), name     # BLAS vs left-to-right products
+        assert got.tobytes() == oracle.depth_to_point_cloud(depth, K, rate, return_xyzuv=True).tobytes(), name
 
 
 def _matching_np(uvs1, uvs2):
