@@ -194,4 +194,18 @@ static_assert(2 * CAMD_MAX_FTZERO + 63 < 0x8000, "a pixel cost must fit a 16-bit
 
 static inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// cv2's fixed-point map encoding: 1/32-pixel phases (remap.hip reads them, tables.hip writes them)
+enum { INTER_BITS = 5, INTER_TAB_SIZE = 1 << INTER_BITS };
+
+// images per workgroup of the batch-inner kernels (remap.hip, depth.hip, distort.hip): all of them (up to 16) while the
+// grid still fills the chip
+static inline int images_per_group(long long groups_per_image, int batch)
+{
+    int zb = batch < 16 ? batch : 16;
+    while (zb > 1 && groups_per_image * div_up(batch, zb) < 4096) zb = (zb + 1) / 2;
+    return zb;
+}
+
+static inline bool float_type_ok(int value_type) { return value_type == CAMD_VALUE_F64 || value_type == CAMD_VALUE_F32; }
+
 }  // namespace camd

@@ -120,8 +120,7 @@ int camd_unrectify_depth(const double* depth, int w, int h, const double M[3], c
     }
     int rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
-    int zb = batch < 16 ? batch : 16;  // all images of the batch (up to 16) per workgroup while the grid fills the chip
-    while (zb > 1 && (long long)div_up(ow, 256) * oh * div_up(batch, zb) < 4096) zb = (zb + 1) / 2;
+    const int zb = images_per_group((long long)div_up(ow, 256) * oh, batch);
     hipLaunchKernelGGL(k_unrectify, dim3(div_up(ow, 256), oh, div_up(batch, zb)), dim3(256), 0, (hipStream_t)stream,
                        depth, w, h, M[0], M[1], M[2], mapx, mapy, out, ow, oh, batch, zb);
     CAMD_LAUNCH_CHECK();

@@ -13,14 +13,13 @@
 // float32 where cv2 hands an array over, the products and sums in cv2's order, no contraction (-ffp-contract=off).
 #include <climits>
 
-#include "common.hpp"
+#include "camera_model.hpp"
 
 namespace camd {
 
 struct DistortArgs {
-    double ifx, ify;  // 1. / fx, 1. / fy (cv2 multiplies by the reciprocal)
-    double fx, fy, cx, cy;
-    double k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4;
+    Pinhole cam;
+    Lens k;
     int w, h;
 };
 
@@ -58,16 +57,12 @@ __global__ __launch_bounds__(256) void k_distort_index_scatter(DistortArgs a, ui
     if (i < n) {
         const int v = i / a.w, u = i - v * a.w;
         // cv2.undistortPoints(points, K, None): no distortion, no R, no P -> one multiply by the reciprocal; float32 out
-        const double x = (double)(float)(((double)u - a.cx) * a.ifx);
-        const double y = (double)(float)(((double)v - a.cy) * a.ify);
+        const double x = (double)(float)(((double)u - a.cam.cx) * a.cam.ifx);
+        const double y = (double)(float)(((double)v - a.cam.cy) * a.cam.ify);
         // cv2.projectPoints((x, y, 1), rvec = 0, tvec = 0, K, D): R = I exactly, z = 1
-        const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-        const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-        const double cdist = 1 + a.k1 * r2 + a.k2 * r4 + a.k3 * r6;
-        const double icdist2 = __ddiv_rn(1., 1 + a.k4 * r2 + a.k5 * r4 + a.k6 * r6);
-        const double xd = x * cdist * icdist2 + a.p1 * a1 + a.p2 * a2 + a.s1 * r2 + a.s2 * r4;
-        const double yd = y * cdist * icdist2 + a.p1 * a3 + a.p2 * a1 + a.s3 * r2 + a.s4 * r4;
-        const float U = (float)(xd * a.fx + a.cx), V = (float)(yd * a.fy + a.cy);
+        double xd, yd;
+        distort_forward(a.k, x, y, xd, yd);
+        const float U = (float)(xd * a.cam.fx + a.cam.cx), V = (float)(yd * a.cam.fy + a.cam.cy);
         if (!__builtin_isfinite(U) || !__builtin_isfinite(V)) {
             atomicAdd(&s[ST_N_OUT], 1);
             atomicAdd(&s[ST_N_NONFINITE], 1);
@@ -129,8 +124,7 @@ static void launch_gather(const void* in, const int32_t* idx, void* out, int n, 
     // 16-byte stores need every image of the batch to start on a 16-byte boundary (n % V == 0 with an aligned base)
     const bool vec = n % V == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)idx % (4 * V) == 0;
     const int lanes = vec ? n / V : n;
-    int zb = batch < 16 ? batch : 16;  // as k_unrectify: share the index loads while the grid still fills the chip
-    while (zb > 1 && (long long)div_up(lanes, 256) * div_up(batch, zb) < 4096) zb = (zb + 1) / 2;
+    const int zb = images_per_group(div_up(lanes, 256), batch);  // as k_unrectify: the images share the index loads
     const dim3 grid(div_up(lanes, 256), div_up(batch, zb));
     if (vec)
         hipLaunchKernelGGL((k_gather_by_index<T, V>), grid, dim3(256), 0, stream, (const T*)in, idx, (T*)out, n, batch, zb);
@@ -152,19 +146,11 @@ int camd_distort_index_map(const double K[9], const double* dist, int ndist, int
         set_error("camd_distort_index_map: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    double dv[14] = {0};
-    for (int i = 0; i < ndist; i++) dv[i] = dist[i];
-    if (dv[12] != 0. || dv[13] != 0.) {
-        set_error("camd_distort_index_map: tilted-sensor distortion (tauX, tauY) not implemented");
-        return CAMD_ERR_UNSUPPORTED;
-    }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
     DistortArgs a;
-    a.fx = K[0], a.fy = K[4], a.cx = K[2], a.cy = K[5];
-    a.ifx = 1. / a.fx, a.ify = 1. / a.fy;
-    a.k1 = dv[0], a.k2 = dv[1], a.p1 = dv[2], a.p2 = dv[3], a.k3 = dv[4], a.k4 = dv[5], a.k5 = dv[6], a.k6 = dv[7];
-    a.s1 = dv[8], a.s2 = dv[9], a.s3 = dv[10], a.s4 = dv[11];
+    int rc = unpack_camera("camd_distort_index_map", K, dist, ndist, &a.cam, &a.k);
+    if (rc != CAMD_OK) return rc;
+    rc = camd_device_ok();
+    if (rc != CAMD_OK) return rc;
     a.w = w, a.h = h;
     const int n = w * h;
     const dim3 grid(div_up(n > ST_WORDS ? n : ST_WORDS, 256));

@@ -349,7 +349,6 @@ static int make_window(EpWin* w, int cu0, int cv0, int cells_w, int cells_h, con
     return CAMD_OK;
 }
 
-static bool uv_type_ok(int t) { return t == CAMD_VALUE_F64 || t == CAMD_VALUE_F32; }
 
 template <bool FIRST>
 static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, int uv_stride, double d, int cu0, int cv0,
@@ -358,7 +357,7 @@ static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, i
     EpWin w;
     int rc = make_window(&w, cu0, cv0, cells_w, cells_h, who);
     if (rc != CAMD_OK) return rc;
-    if (!grid || !outside || uv_stride < 2 || (n && !uv) || !uv_type_ok(uv_type) || !(d > 0.0) || (unsigned long long)n >= 0xffffffffull) {
+    if (!grid || !outside || uv_stride < 2 || (n && !uv) || !float_type_ok(uv_type) || !(d > 0.0) || (unsigned long long)n >= 0xffffffffull) {
         set_error("%s: bad arguments", who);
         return CAMD_ERR_BAD_ARG;
     }
@@ -398,7 +397,7 @@ static int check_sets(const char* who, const camd_cell_set* sets, int nsets, con
     *max_n = 0;
     for (int k = 0; k < nsets; k++) {
         const camd_cell_set& s = sets[k];
-        if (!uv_type_ok(s.uv_type) || s.n >= 0xffffffffull || (s.n && !s.uv)) {
+        if (!float_type_ok(s.uv_type) || s.n >= 0xffffffffull || (s.n && !s.uv)) {
             set_error("%s: set %d: bad type, rows or pointer", who, k);
             return CAMD_ERR_BAD_ARG;
         }
@@ -501,7 +500,7 @@ int camd_overlap_keep(const void* uv1, const void* uv2, int uv_type, size_t n, i
     EpWin w;
     int rc = make_window(&w, cu0, cv0, cells_w, cells_h, "camd_overlap_keep");
     if (rc != CAMD_OK) return rc;
-    if (!population1 || !population2 || uv_stride < 2 || !uv_type_ok(uv_type) || (unsigned long long)n >= 0xffffffffull ||
+    if (!population1 || !population2 || uv_stride < 2 || !float_type_ok(uv_type) || (unsigned long long)n >= 0xffffffffull ||
         (n && (!uv1 || !uv2 || !keep || !blockcount))) {
         set_error("camd_overlap_keep: bad arguments");
         return CAMD_ERR_BAD_ARG;
@@ -523,7 +522,7 @@ int camd_overlap_keep(const void* uv1, const void* uv2, int uv_type, size_t n, i
 int camd_overlap_emit(const void* uv1, const void* uv2, int uv_type, size_t n, int uv_stride, const uint8_t* keep,
                       const long long* start, void* out1, void* out2, size_t capacity, unsigned long long* count, void* stream)
 {
-    if (!count || uv_stride < 2 || !uv_type_ok(uv_type) || (unsigned long long)n >= 0xffffffffull ||
+    if (!count || uv_stride < 2 || !float_type_ok(uv_type) || (unsigned long long)n >= 0xffffffffull ||
         (n && (!uv1 || !uv2 || !keep || !start)) || (capacity && (!out1 || !out2))) {
         set_error("camd_overlap_emit: bad arguments");
         return CAMD_ERR_BAD_ARG;
@@ -593,7 +592,7 @@ int camd_vector_sum(const double* z, size_t z_len, const long long* idx, size_t 
 int camd_flow_to_matched_uvs(const void* flow_abs, int flow_type, const uint8_t* mask, int w, int h, double* uvs_from,
                              double* uvs_to, size_t capacity, unsigned long long* count, void* workspace, void* stream)
 {
-    if (!flow_abs || !mask || !count || !workspace || w <= 0 || h <= 0 || !uv_type_ok(flow_type) ||
+    if (!flow_abs || !mask || !count || !workspace || w <= 0 || h <= 0 || !float_type_ok(flow_type) ||
         (capacity && (!uvs_from || !uvs_to))) {
         set_error("camd_flow_to_matched_uvs: bad arguments");
         return CAMD_ERR_BAD_ARG;
@@ -615,7 +614,7 @@ int camd_flow_to_matched_uvs(const void* flow_abs, int flow_type, const uint8_t*
 
 int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, float* flow_normal, void* stream)
 {
-    if (!flow_abs || !flow_normal || w <= 0 || h <= 0 || !uv_type_ok(flow_type)) {
+    if (!flow_abs || !flow_normal || w <= 0 || h <= 0 || !float_type_ok(flow_type)) {
         set_error("camd_flow_abs_to_normal: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
@@ -635,7 +634,7 @@ int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, f
 int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h, double target_w, double target_h,
                             double* flow_abs, void* stream)
 {
-    if (!flow_normal || !flow_abs || w <= 0 || h <= 0 || !uv_type_ok(flow_type)) {
+    if (!flow_normal || !flow_abs || w <= 0 || h <= 0 || !float_type_ok(flow_type)) {
         set_error("camd_flow_normal_to_abs: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
@@ -732,7 +731,7 @@ int camd_cell_intersect_emit_batch(const uint32_t* grids, size_t grid_cells, con
 int camd_uvzi_pack(const void* uv, int uv_type, const double* z, size_t n, double other_view, double* rows, size_t rows_total,
                    size_t row_offset, void* stream)
 {
-    if (!rows || !uv_type_ok(uv_type) || row_offset > rows_total || n > rows_total - row_offset || (n && (!uv || !z))) {
+    if (!rows || !float_type_ok(uv_type) || row_offset > rows_total || n > rows_total - row_offset || (n && (!uv || !z))) {
         set_error("camd_uvzi_pack: bad arguments (rows %zu + %zu of %zu)", row_offset, n, rows_total);
         return CAMD_ERR_BAD_ARG;
     }

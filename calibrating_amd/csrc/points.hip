@@ -10,28 +10,16 @@
 // cv2 hands an array over, products and sums in cv2's order, no contraction (-ffp-contract=off), divisions rounded once.
 #include <climits>
 
-#include "common.hpp"
+#include "camera_model.hpp"
 
 namespace camd {
 
 struct PointsArgs {
-    double ifx, ify;  // 1. / fx, 1. / fy (cv2 multiplies by the reciprocal)
-    double fx, fy, cx, cy;
-    double k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4;
+    Pinhole cam;
+    Lens k;
     double R[9], t[3];  // camd_project_points only
     int ndist, iters, pixels;  // camd_undistort_points only
 };
-
-// the forward model of cv2.projectPoints on a normalised point, in the order k_distort_index_scatter (distort.hip) applies it
-__device__ __forceinline__ void distort_normalised(const PointsArgs& a, double x, double y, double& xd, double& yd)
-{
-    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-    const double cdist = 1 + a.k1 * r2 + a.k2 * r4 + a.k3 * r6;
-    const double icdist2 = __ddiv_rn(1., 1 + a.k4 * r2 + a.k5 * r4 + a.k6 * r6);
-    xd = x * cdist * icdist2 + a.p1 * a1 + a.p2 * a2 + a.s1 * r2 + a.s2 * r4;
-    yd = y * cdist * icdist2 + a.p1 * a3 + a.p2 * a1 + a.s3 * r2 + a.s4 * r4;
-}
 
 // (u, v) of a row: one 8- / 16-byte access when every row starts on such a boundary (VEC), two scalar loads otherwise
 template <typename T, bool VEC>
@@ -66,16 +54,17 @@ __global__ __launch_bounds__(256) void k_undistort_points(PointsArgs a, const TI
     if (i >= n) return;
     double u, v;
     load_pair<TI, VEC>(uv + i * stride, u, v);
-    const double xs = (u - a.cx) * a.ifx, ys = (v - a.cy) * a.ify;
+    const Lens& k = a.k;
+    const double xs = (u - a.cam.cx) * a.cam.ifx, ys = (v - a.cam.cy) * a.cam.ify;
     double x = xs, y = ys;
     if (a.ndist) {
         // the trip count is the same for every lane: a lane that met icdist < 0 keeps its start value through selects
         bool done = false;
         for (int j = 0; j < a.iters; j++) {
             const double r2 = x * x + y * y;
-            const double icdist = __ddiv_rn(1 + ((a.k6 * r2 + a.k5) * r2 + a.k4) * r2, 1 + ((a.k3 * r2 + a.k2) * r2 + a.k1) * r2);
-            const double dX = 2 * a.p1 * x * y + a.p2 * (r2 + 2 * x * x) + a.s1 * r2 + a.s2 * r2 * r2;
-            const double dY = a.p1 * (r2 + 2 * y * y) + 2 * a.p2 * x * y + a.s3 * r2 + a.s4 * r2 * r2;
+            const double icdist = __ddiv_rn(1 + ((k.k6 * r2 + k.k5) * r2 + k.k4) * r2, 1 + ((k.k3 * r2 + k.k2) * r2 + k.k1) * r2);
+            const double dX = 2 * k.p1 * x * y + k.p2 * (r2 + 2 * x * x) + k.s1 * r2 + k.s2 * r2 * r2;
+            const double dY = k.p1 * (r2 + 2 * y * y) + 2 * k.p2 * x * y + k.s3 * r2 + k.s4 * r2 * r2;
             const bool neg = icdist < 0;
             const double xn = neg ? xs : (xs - dX) * icdist, yn = neg ? ys : (ys - dY) * icdist;
             x = done ? x : xn;
@@ -84,7 +73,7 @@ __global__ __launch_bounds__(256) void k_undistort_points(PointsArgs a, const TI
         }
     }
     x = (double)(TI)x, y = (double)(TI)y;
-    if (a.pixels) x = x * a.fx + a.cx, y = y * a.fy + a.cy;
+    if (a.pixels) x = x * a.cam.fx + a.cam.cx, y = y * a.cam.fy + a.cam.cy;
     store_pair<TO>(out + i * 2, x, y);
 }
 
@@ -115,38 +104,27 @@ __global__ __launch_bounds__(256) void k_project_points(PointsArgs a, const T* _
     const double iz = z != 0. ? __ddiv_rn(1., z) : 1.;  // (z ? 1. / z : 1: a NaN z is "true" and divides)
     x *= iz, y *= iz;
     double xd, yd;
-    distort_normalised(a, x, y, xd, yd);
-    store_pair<T>(out + i * 2, xd * a.fx + a.cx, yd * a.fy + a.cy);
+    distort_forward(a.k, x, y, xd, yd);
+    store_pair<T>(out + i * 2, xd * a.cam.fx + a.cam.cx, yd * a.cam.fy + a.cam.cy);
 }
 
-static bool value_type_ok(int t) { return t == CAMD_VALUE_F64 || t == CAMD_VALUE_F32; }
 static size_t value_bytes(int t) { return t == CAMD_VALUE_F64 ? 8 : 4; }
 
-// K, dist -> a; CAMD_OK, or the status with the message set
+// the point calls take cv2's own coefficient counts only; then K, dist -> a
 static int camera_args(const char* who, const double K[9], const double* dist, int ndist, PointsArgs& a)
 {
     if (!K || (ndist != 0 && ndist != 4 && ndist != 5 && ndist != 8 && ndist != 12 && ndist != 14) || (ndist > 0 && !dist)) {
         set_error("%s: bad arguments (K is 9 host doubles; ndist is 0, 4, 5, 8, 12 or 14, got %d)", who, ndist);
         return CAMD_ERR_BAD_ARG;
     }
-    double dv[14] = {0};
-    for (int i = 0; i < ndist; i++) dv[i] = dist[i];
-    if (dv[12] != 0. || dv[13] != 0.) {
-        set_error("%s: tilted-sensor distortion (tauX, tauY) not implemented", who);
-        return CAMD_ERR_UNSUPPORTED;
-    }
-    a.fx = K[0], a.fy = K[4], a.cx = K[2], a.cy = K[5];
-    a.ifx = 1. / a.fx, a.ify = 1. / a.fy;
-    a.k1 = dv[0], a.k2 = dv[1], a.p1 = dv[2], a.p2 = dv[3], a.k3 = dv[4], a.k4 = dv[5], a.k5 = dv[6], a.k6 = dv[7];
-    a.s1 = dv[8], a.s2 = dv[9], a.s3 = dv[10], a.s4 = dv[11];
     a.ndist = ndist;
-    return CAMD_OK;
+    return unpack_camera(who, K, dist, ndist, &a.cam, &a.k);
 }
 
 // rows of `stride` elements of `type` starting at `in`, n of them, at least `need` elements each; out: [n][2] of out_type
 static bool rows_ok(const void* in, int type, size_t n, int stride, int need, const void* out, int out_type)
 {
-    return value_type_ok(type) && value_type_ok(out_type) && stride >= need && n <= (size_t)INT_MAX &&
+    return float_type_ok(type) && float_type_ok(out_type) && stride >= need && n <= (size_t)INT_MAX &&
            (n == 0 || (in && out && (uintptr_t)in % value_bytes(type) == 0 && (uintptr_t)out % (2 * value_bytes(out_type)) == 0));
 }
 

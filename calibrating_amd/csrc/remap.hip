@@ -15,7 +15,7 @@
 
 namespace camd {
 
-enum { INTER_BITS = 5, INTER_TAB_SIZE = 32, COEF_BITS = 15, COEF_SCALE = 1 << 15 };
+enum { COEF_BITS = 15, COEF_SCALE = 1 << 15 };
 
 static inline short sat_short(int v) { return (short)(v < -32768 ? -32768 : v > 32767 ? 32767 : v); }
 
@@ -415,30 +415,6 @@ __global__ __launch_bounds__(256) void k_remap_fixed_bilinear(const uint8_t* __r
                                  dst + (size_t)z0 * dst_stride + (size_t)y * dst_pitch + (size_t)x * CN, dst_stride, nz);
 }
 
-// images per workgroup of the batch-inner kernels: all of them (up to 16) while the grid still fills the chip
-static int images_per_group(int groups_per_image, int batch)
-{
-    int zb = std::min(batch, 16);
-    while (zb > 1 && (long long)groups_per_image * div_up(batch, zb) < 4096) zb = (zb + 1) / 2;
-    return zb;
-}
-
-// host: one row of initUndistortRectifyMap's inner loop (X/Y/W accumulate per column, float64)
-struct Dist { double k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4; };
-
-static void inv3(const double m[9], double o[9])
-{
-    double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
-               m[2] * (m[3] * m[7] - m[4] * m[6]);
-    d = d != 0. ? 1. / d : 0.;
-    double t[9] = {(m[4] * m[8] - m[5] * m[7]) * d, (m[2] * m[7] - m[1] * m[8]) * d,
-                   (m[1] * m[5] - m[2] * m[4]) * d, (m[5] * m[6] - m[3] * m[8]) * d,
-                   (m[0] * m[8] - m[2] * m[6]) * d, (m[2] * m[3] - m[0] * m[5]) * d,
-                   (m[3] * m[7] - m[4] * m[6]) * d, (m[1] * m[6] - m[0] * m[7]) * d,
-                   (m[0] * m[4] - m[1] * m[3]) * d};
-    for (int i = 0; i < 9; i++) o[i] = t[i];
-}
-
 }  // namespace camd
 
 using namespace camd;
@@ -537,54 +513,6 @@ int camd_remap_fixed_bilinear_u8(const uint8_t* src, int sw, int sh, int cn, siz
         hipLaunchKernelGGL((k_remap_fixed_bilinear<3>), grid, block, 0, st, src, sw, sh, src_pitch, src_stride,
                            mapxy, mapa, dst, dw, dh, dst_pitch, dst_stride, tb, batch, zb);
     CAMD_LAUNCH_CHECK();
-    return CAMD_OK;
-}
-
-int camd_undistort_maps_host(const double K[9], const double* dist, int ndist, int w, int h,
-                             int16_t* mapxy, uint16_t* mapa)
-{
-    if (!K || !mapxy || !mapa || w <= 0 || h <= 0 || ndist < 0 || ndist > 14 || (ndist > 0 && !dist)) {
-        set_error("camd_undistort_maps_host: bad arguments");
-        return CAMD_ERR_BAD_ARG;
-    }
-    double dv[14] = {0};
-    for (int i = 0; i < ndist; i++) dv[i] = dist[i];
-    if (ndist > 12 && (dv[12] != 0. || dv[13] != 0.)) {
-        set_error("tilted-sensor distortion (tauX, tauY) not implemented");
-        return CAMD_ERR_UNSUPPORTED;
-    }
-    const Dist k = {dv[0], dv[1], dv[2], dv[3], dv[4], dv[5], dv[6], dv[7], dv[8], dv[9], dv[10], dv[11]};
-    // cv2.undistort works in stripes of rows and folds the stripe offset into the new camera matrix
-    int stripe0 = (1 << 12) / (w > 1 ? w : 1);
-    if (stripe0 < 1) stripe0 = 1;
-    if (stripe0 > h) stripe0 = h;
-    double Ar[9], ir[9];
-    for (int i = 0; i < 9; i++) Ar[i] = K[i];
-    const double fx = K[0], fy = K[4], u0 = K[2], v0 = K[5], cy0 = K[5];
-    for (int y = 0; y < h; y += stripe0) {
-        int stripe = stripe0 < h - y ? stripe0 : h - y;
-        Ar[5] = cy0 - y;
-        inv3(Ar, ir);
-        for (int i = 0; i < stripe; i++) {
-            double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
-            int16_t* mxy = mapxy + (size_t)(y + i) * w * 2;
-            uint16_t* ma = mapa + (size_t)(y + i) * w;
-            for (int j = 0; j < w; j++, _x += ir[0], _y += ir[3], _w += ir[6]) {
-                double ww = 1. / _w, x = _x * ww, yy = _y * ww;
-                double x2 = x * x, y2 = yy * yy;
-                double r2 = x2 + y2, _2xy = 2 * x * yy;
-                double kr = (1 + ((k.k3 * r2 + k.k2) * r2 + k.k1) * r2) /
-                            (1 + ((k.k6 * r2 + k.k5) * r2 + k.k4) * r2);
-                double xd = (x * kr + k.p1 * _2xy + k.p2 * (r2 + 2 * x2) + k.s1 * r2 + k.s2 * r2 * r2);
-                double yd = (yy * kr + k.p1 * (r2 + 2 * y2) + k.p2 * _2xy + k.s3 * r2 + k.s4 * r2 * r2);
-                double u = fx * xd + u0, v = fy * yd + v0;
-                int iu = (int)lrint(u * INTER_TAB_SIZE), iv = (int)lrint(v * INTER_TAB_SIZE);
-                mxy[j * 2] = (int16_t)(iu >> INTER_BITS);
-                mxy[j * 2 + 1] = (int16_t)(iv >> INTER_BITS);
-                ma[j] = (uint16_t)((iv & (INTER_TAB_SIZE - 1)) * INTER_TAB_SIZE + (iu & (INTER_TAB_SIZE - 1)));
-            }
-        }
-    }
     return CAMD_OK;
 }
 

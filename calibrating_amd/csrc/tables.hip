@@ -1,40 +1,26 @@
 // tables.hip -- the rig's lookup tables built on the GPU: cv2.initUndistortRectifyMap
 // (CV_32FC1 maps, stereo_camera.py:159-165 and utils.py:184-191) with the rectify valid mask
 // (stereo_camera.py:167-176) fused, and the CV_16SC2 + CV_16UC1 maps cv2.undistort builds internally
-// (stereo_camera.py:430-431).  Bit-identical to the host construction (geometry.py / camd_undistort_maps_host)
-// and to the oracle: float64, no contraction (-ffp-contract=off), correctly rounded division.
+// (stereo_camera.py:430-431).  Bit-identical to the host construction (geometry.py; camd_undistort_maps_host at the
+// end of this file runs the kernel's own per-pixel functions, camera_model.hpp) and to the oracle: float64, no
+// contraction (-ffp-contract=off), correctly rounded division.
 //
 // OpenCV accumulates X, Y, W along a row by repeated addition (_x += ir[0] ...).  That recurrence is the
 // only sequential part: a workgroup owns one row, three of its lanes run the three chains for a chunk of
 // columns into LDS (a few microseconds; all rows run in parallel), then all 256 lanes do the per-pixel
 // distortion arithmetic from LDS.
-#include "common.hpp"
+#include "camera_model.hpp"
 
 namespace camd {
 
-struct DistK { double k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4; };
-
 struct TableArgs {
-    double A[9];     // camera matrix of the SOURCE image (fx, fy, cx, cy used)
+    Pinhole cam;     // camera matrix of the SOURCE image
+    Lens k;
     double New[9];   // new camera matrix * R (its inverse maps destination pixels to rays)
-    DistK k;
     int w, h;        // destination size
     int src_w, src_h;  // valid-mask bounds (mask != nullptr)
     int stripe;      // fixed-point variant: rows per stripe (cv2.undistort folds the stripe offset into cy)
 };
-
-__host__ __device__ inline void inv3_rm(const double* m, double* o)
-{
-    double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
-               m[2] * (m[3] * m[7] - m[4] * m[6]);
-    d = d != 0. ? 1. / d : 0.;
-    double t[9] = {(m[4] * m[8] - m[5] * m[7]) * d, (m[2] * m[7] - m[1] * m[8]) * d,
-                   (m[1] * m[5] - m[2] * m[4]) * d, (m[5] * m[6] - m[3] * m[8]) * d,
-                   (m[0] * m[8] - m[2] * m[6]) * d, (m[2] * m[3] - m[0] * m[5]) * d,
-                   (m[3] * m[7] - m[4] * m[6]) * d, (m[1] * m[6] - m[0] * m[7]) * d,
-                   (m[0] * m[4] - m[1] * m[3]) * d};
-    for (int i = 0; i < 9; i++) o[i] = t[i];
-}
 
 static constexpr int TAB_CHUNK = 1024;  // columns per chunk: 3 x 8 KB of LDS
 
@@ -50,18 +36,12 @@ __global__ __launch_bounds__(256) void k_undistort_rectify_map(TableArgs a, floa
     double ir[9];
     int i = row;
     if (FIXED) {
-        // stripe y0 = row - row % stripe: Ar = K with cy - y0, R = I
         const int y0 = row - row % a.stripe;
-        double Ar[9];
-        for (int q = 0; q < 9; q++) Ar[q] = a.New[q];
-        Ar[5] = a.New[5] - y0;
-        inv3_rm(Ar, ir);
+        stripe_inverse(a.New, y0, ir);
         i = row - y0;
     } else {
-        inv3_rm(a.New, ir);
+        inv3(a.New, ir);
     }
-    const double fx = a.A[0], fy = a.A[4], u0 = a.A[2], v0 = a.A[5];
-    const DistK k = a.k;
     if (threadIdx.x < 3) {
         const int c = threadIdx.x;
         carry[c] = i * ir[3 * c + 1] + ir[3 * c + 2];
@@ -81,21 +61,12 @@ __global__ __launch_bounds__(256) void k_undistort_rectify_map(TableArgs a, floa
         }
         __syncthreads();
         for (int j = threadIdx.x; j < n; j += 256) {
-            const double _x = sX[j], _y = sY[j], _w = sW[j];
-            const double ww = 1. / _w, x = _x * ww, y = _y * ww;
-            const double x2 = x * x, y2 = y * y;
-            const double r2 = x2 + y2, _2xy = 2 * x * y;
-            const double kr = (1 + ((k.k3 * r2 + k.k2) * r2 + k.k1) * r2) / (1 + ((k.k6 * r2 + k.k5) * r2 + k.k4) * r2);
-            const double xd = (x * kr + k.p1 * _2xy + k.p2 * (r2 + 2 * x2) + k.s1 * r2 + k.s2 * r2 * r2);
-            const double yd = (y * kr + k.p1 * (r2 + 2 * y2) + k.p2 * _2xy + k.s3 * r2 + k.s4 * r2 * r2);
-            const double u = fx * xd + u0, v = fy * yd + v0;
             const size_t o = (size_t)row * a.w + j0 + j;
             if (FIXED) {
-                const int iu = (int)rint(u * 32), iv = (int)rint(v * 32);  // cvRound(u * INTER_TAB_SIZE)
-                mapxy[o * 2] = (int16_t)(iu >> 5);
-                mapxy[o * 2 + 1] = (int16_t)(iv >> 5);
-                mapa[o] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+                ray_to_fixed_cell(a.cam, a.k, sX[j], sY[j], sW[j], mapxy + o * 2, mapa + o);
             } else {
+                double u, v;
+                ray_to_pixel(a.cam, a.k, sX[j], sY[j], sW[j], u, v);
                 const float fu = (float)u, fv = (float)v;
                 mapx[o] = fu;
                 mapy[o] = fv;
@@ -113,18 +84,12 @@ static int fill_args(TableArgs* a, const double A[9], const double* dist, int nd
         set_error("%s: bad arguments", who);
         return CAMD_ERR_BAD_ARG;
     }
-    double dv[14] = {0};
-    for (int i = 0; i < ndist; i++) dv[i] = dist[i];
-    if (dv[12] != 0. || dv[13] != 0.) {
-        set_error("%s: tilted-sensor distortion (tauX, tauY) not implemented", who);
-        return CAMD_ERR_UNSUPPORTED;
-    }
-    for (int i = 0; i < 9; i++) a->A[i] = A[i];
-    a->k = {dv[0], dv[1], dv[2], dv[3], dv[4], dv[5], dv[6], dv[7], dv[8], dv[9], dv[10], dv[11]};
+    const int rc = unpack_camera(who, A, dist, ndist, &a->cam, &a->k);
+    if (rc != CAMD_OK) return rc;
     a->w = w;
     a->h = h;
     a->src_w = a->src_h = 0;
-    a->stripe = 1;
+    a->stripe = undistort_stripe_rows(w, h);
     return CAMD_OK;
 }
 
@@ -170,13 +135,30 @@ int camd_undistort_maps(const double K[9], const double* dist, int ndist, int w,
     rc = camd_device_ok();
     if (rc != CAMD_OK) return rc;
     for (int i = 0; i < 9; i++) a.New[i] = K[i];
-    int stripe0 = (1 << 12) / (w > 1 ? w : 1);
-    if (stripe0 < 1) stripe0 = 1;
-    if (stripe0 > h) stripe0 = h;
-    a.stripe = stripe0;
     hipLaunchKernelGGL((k_undistort_rectify_map<true>), dim3(h), dim3(256), 0, (hipStream_t)stream, a, (float*)nullptr,
                        (float*)nullptr, (uint8_t*)nullptr, mapxy, mapa);
     CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+// the same maps on the host: one text with the kernel (camera_model.hpp), the row recurrence a plain loop
+int camd_undistort_maps_host(const double K[9], const double* dist, int ndist, int w, int h, int16_t* mapxy,
+                             uint16_t* mapa)
+{
+    if (!mapxy || !mapa) { set_error("camd_undistort_maps_host: bad arguments"); return CAMD_ERR_BAD_ARG; }
+    TableArgs a;
+    const int rc = fill_args(&a, K, dist, ndist, w, h, "camd_undistort_maps_host");
+    if (rc != CAMD_OK) return rc;
+    for (int y0 = 0; y0 < h; y0 += a.stripe) {
+        double ir[9];
+        stripe_inverse(K, y0, ir);
+        for (int i = 0; i < a.stripe && y0 + i < h; i++) {
+            double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+            const size_t o = (size_t)(y0 + i) * w;
+            for (int j = 0; j < w; j++, _x += ir[0], _y += ir[3], _w += ir[6])
+                ray_to_fixed_cell(a.cam, a.k, _x, _y, _w, mapxy + (o + j) * 2, mapa + o + j);
+        }
+    }
     return CAMD_OK;
 }
 

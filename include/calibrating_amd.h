@@ -160,7 +160,8 @@ int camd_remap_fixed_bilinear_u8(const uint8_t* src, int sw, int sh, int cn, siz
                                  size_t src_stride, const int16_t* mapxy, const uint16_t* mapa,
                                  uint8_t* dst, int dw, int dh, size_t dst_pitch, size_t dst_stride,
                                  int batch, void* stream);
-/* host, init time: the stripe-wise fixed-point maps of cv2.undistort (2*w*h int16 + w*h uint16) */
+/* host, init time: the stripe-wise fixed-point maps of cv2.undistort (2*w*h int16 + w*h uint16); csrc/tables.hip,
+ * beside its device twin camd_undistort_maps                                                      */
 int camd_undistort_maps_host(const double K[9], const double* dist, int ndist, int w, int h,
                              int16_t* mapxy_host, uint16_t* mapa_host);
 /* ---- rig tables on the GPU (init time, or per batch when the rig / target size changes) -------------

@@ -13,6 +13,8 @@ torch = pytest.importorskip("torch")
 import calibrating_amd as ca  # noqa: E402
 from calibrating_amd import imgproc, synthetic  # noqa: E402
 
+import camera_model_cases as cmc  # noqa: E402
+
 DEPTH_TOL = 1e-4  # metres, BASELINE.json north_star
 
 
@@ -337,6 +339,25 @@ def test_tables_built_on_gpu_are_bit_identical(oracle):
         hxy, ha = imgproc.undistort_maps(K, dist, (w, h))
         dxy, da = imgproc.undistort_maps_device(K, dist, (w, h))
         assert np.array_equal(dxy.cpu().numpy(), hxy) and np.array_equal(da.cpu().numpy().view(np.uint16), ha)
+
+
+@pytest.mark.parametrize("size", cmc.STRIPE_SIZES, ids=lambda s: "%dx%d" % s)
+def test_tables_on_the_edges_of_the_stripe_rule(oracle, size):
+    """Device maps == host maps where cv2.undistort's stripe rule changes its answer (4097 columns also cross the
+    kernel's 1024-column chunk four times); the host maps are pinned to the oracle in tests/test_camera_model_cpu.py.
+    On the two one-stripe-per-row / two-stripe extremes the float maps and the mask are the oracle's too."""
+    w, h = size
+    for ndist in (0, 5, 12):
+        K, D = cmc.stripe_rig(w, h, ndist)
+        hxy, ha = imgproc.undistort_maps(K, D, (w, h))
+        dxy, da = imgproc.undistort_maps_device(K, D, (w, h))
+        assert np.array_equal(dxy.cpu().numpy(), hxy) and np.array_equal(da.cpu().numpy().view(np.uint16), ha), ndist
+        if size in ((4097, 3), (1, 5000)):
+            mx, my, mask = imgproc.init_undistort_rectify_map(K, D, None, K, (w, h), valid_for=(w, h))
+            ox, oy = oracle.init_undistort_rectify_map(K, D, None, K, (w, h))
+            assert np.array_equal(mx.cpu().numpy(), ox) and np.array_equal(my.cpu().numpy(), oy), ndist
+            ref_mask = (-0.5 < ox) & (ox < w - 0.5) & (-0.5 < oy) & (oy < h - 0.5)
+            assert np.array_equal(mask.cpu().numpy().astype(bool), ref_mask), ndist
 
 
 def test_stereo_device_tables_match_host_properties():

@@ -14,6 +14,7 @@ torch = pytest.importorskip("torch")
 import calibrating_amd as ca  # noqa: E402
 from calibrating_amd import _native, geometry, imgproc  # noqa: E402
 
+import distort_depth_ref as dref  # noqa: E402
 import epipolar_cases as ec  # noqa: E402
 import points_cases as pc  # noqa: E402
 import points_ref as ref  # noqa: E402
@@ -95,6 +96,29 @@ def test_every_distortion_model(dtype, ndist):
         assert same(imgproc.undistort_points(uv, pc.K, np.zeros(0)), und)
     else:
         assert not same(und, imgproc.undistort_points(uv, pc.K, None))
+
+
+@pytest.mark.parametrize("ndist", pc.NDIST)
+def test_project_points_rebuilds_the_distort_index_table(ndist):
+    """k_project_points and k_distort_index_scatter call one forward model (csrc/camera_model.hpp): the pixels of a 16 x 12
+    image, normalised and rounded to float32 as U21 does, projected in float64 with R = I, t = 0 and truncated the way
+    distort.hip truncates, give ``distort_index_map``'s table -- first index wins, -1 in holes."""
+    w, h = 16, 12
+    K, D = np.array([[10.3, 0, 7.8], [0, 10.1, 5.7], [0, 0, 1.0]]), pc.lens(ndist)
+    assert dref.target_stats(K, D, w, h)["n_out"] == 0  # (CPU: every target of this rig stays inside the image)
+    v, u = np.mgrid[0:h, 0:w]
+    x = ((u.ravel() - K[0, 2]) * (1.0 / K[0, 0])).astype(np.float32).astype(np.float64)
+    y = ((v.ravel() - K[1, 2]) * (1.0 / K[1, 1])).astype(np.float32).astype(np.float64)
+    UV = imgproc.project_points(np.stack([x, y, np.ones_like(x)], 1), EYE, ZERO, K, D)
+    assert UV.dtype == np.float64
+    t = UV.astype(np.float32).astype(np.int32)  # (float) of the float64 pixel, then truncation toward zero
+    want = np.full(w * h, w * h, np.int64)
+    np.minimum.at(want, t[:, 1] * w + t[:, 0], np.arange(w * h))
+    want[want == w * h] = -1
+    got = imgproc.distort_index_map(K, D, (w, h)).cpu().numpy()
+    assert got.dtype == np.int32 and np.array_equal(got.reshape(-1), want)
+    assert (want < 0).any() and (want >= 0).any()  # holes are part of the comparison (without a lens: rounding alone)
+    assert np.array_equal(got, dref.index_map_minimum_at(K, D, w, h))
 
 
 def test_tilted_sensor_is_refused():
