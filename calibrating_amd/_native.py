@@ -140,6 +140,10 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     "camd_flow_abs_to_normal": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "camd_flow_normal_to_abs": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
+    "camd_warp_flow_backward_u8": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_int, c_size_t, c_void_p, c_int, c_int,
+                                           c_size_t, c_size_t, c_int, c_int, c_void_p]),
+    "camd_warp_flow_forward_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_size_t, c_void_p,
+                                          c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_int, c_void_p]),
     "camd_uv_bounds_blocks": (c_int, []),
     "camd_uv_bounds_batch": (c_int, [ctypes.POINTER(CellSet), c_int, c_void_p, c_void_p, c_void_p]),
     "camd_cell_first_index_batch": (c_int, [ctypes.POINTER(CellSet), c_int, c_void_p, c_double, c_void_p, c_size_t, c_void_p,

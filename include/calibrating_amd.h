@@ -410,6 +410,31 @@ int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, f
 /* replaces flow_utils.flow_normal_to_abs: [2][h][w] -> float64 [h][w][2], float64(flow) * (target_w, target_h)    */
 int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h, double target_w, double target_h,
                             double* flow_abs, void* stream);
+/* ---- flow_utils.warp_flow (csrc/flow.hip): an image moved through a normalised flow, no map in memory -----------------
+ * flow: [batch][2][h][w] of flow_type (CAMD_VALUE_F64 / CAMD_VALUE_F32), x in units of w, y in units of h; image b's two
+ * planes start at flow + b * flow_stride (elements) -- every image of a batch has its own flow.  Pixel (x, y) maps to
+ * m = float64(x) + float64(flow_x) * float64(w), likewise y and h (NumPy's promotion of flow * [[[w]], [[h]]],
+ * flow_utils.py:111-112): product and sum rounded once each in float64, never fused.  Images are u8 HWC, cn 1 or 3, with
+ * the pitch / stride / batch conventions of camd_remap_u8; interp: CAMD_INTER_NEAREST / _LINEAR / _LANCZOS4, anything else
+ * is CAMD_ERR_UNSUPPORTED.  CAMD_ERR_BAD_ARG: cn other than 1 or 3, a side >= 32768 (cv2.remap's short coordinates),
+ * w * h > 2^31 - 1, batch > 65535.
+ *
+ * replaces flow_utils.py:127-129 (img2 given): cv2.remap(img2, float32(m_x), float32(m_y), interp), BORDER_CONSTANT 0, for
+ * an img2 that already has the flow's size (the boxx.resize of :128 is camd_resize_linear_u8).  A pixel whose map * 32 is
+ * NaN, infinite or beyond int32 is 0: cvRound on x86 sends it to a cell outside every image.                        */
+int camd_warp_flow_backward_u8(const uint8_t* img2, int cn, size_t src_pitch, size_t src_stride, const void* flow,
+                               int flow_type, size_t flow_stride, uint8_t* dst, int w, int h, size_t dst_pitch,
+                               size_t dst_stride, int interp, int batch, void* stream);
+/* replaces flow_utils.py:113-125 (img1 given): t = int32(round_half_even(m)); a source pixel with a non-zero flow
+ * (-0.0 counts as zero) and a target inside w x h writes its own (x, y) into the identity map at t, the last writer in
+ * row-major source order winning, then cv2.remap(img1, map, interp).  The map holds integers, so all three
+ * interpolations copy the winning pixel of img1 (sw x sh, which need not be w x h), or give 0 where that position lies
+ * outside img1.  Sources whose target is NaN, infinite or beyond int32 are skipped.  winner_ws: batch * w * h int32 of
+ * scratch (set to -1 on the stream, then atomicMax of the source's y * w + x: the largest index IS the last writer, so
+ * identical calls give identical bytes).                                                                           */
+int camd_warp_flow_forward_u8(const uint8_t* img1, int sw, int sh, int cn, size_t src_pitch, size_t src_stride,
+                              const void* flow, int flow_type, size_t flow_stride, uint8_t* dst, int w, int h,
+                              size_t dst_pitch, size_t dst_stride, int interp, int32_t* winner_ws, int batch, void* stream);
 
 /* ---- all triples of a multi-view reconstruction in one pass (csrc/epipolar.hip; reconstruction_epipolar_geometry.py) ----
  * The batched form of the three camd_cell_* steps above: many point sets / many pairs of grids per launch, chosen by
