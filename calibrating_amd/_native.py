@@ -39,6 +39,7 @@ INTER_NEAREST = 0
 INTER_LINEAR = 1
 INTER_LANCZOS4 = 4
 VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_arr2d / camd_uvzs_to_arr2d
+VALUE_U16 = 3  # a uint16 depth in millimetres: camd_vis_depth only
 NEAREST_MAX_RADIUS = 32  # CAMD_NEAREST_MAX_RADIUS
 POINTS_PIXELS = 0x100  # CAMD_POINTS_PIXELS, or-ed into camd_undistort_points' out_type
 
@@ -144,6 +145,17 @@ SIGNATURES = {
                                            c_size_t, c_size_t, c_int, c_int, c_void_p]),
     "camd_warp_flow_forward_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_size_t, c_size_t, c_void_p, c_int, c_size_t, c_void_p,
                                           c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "camd_vis_l1_error": (c_int, [c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_vis_l1_limit_workspace_bytes": (c_size_t, [c_int]),
+    "camd_vis_l1_limit": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_vis_l1_bar": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_vis_l1_colour": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "camd_vis_depth_range": (c_int, [c_void_p, c_int, c_size_t, c_int, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "camd_vis_depth": (c_int, [c_void_p, c_int, c_size_t, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p,
+                               c_int, c_double, c_double, c_void_p, c_int, c_void_p, c_void_p]),
+    "camd_vis_lines": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                               c_size_t, c_size_t, c_size_t, c_void_p]),
     "camd_uv_bounds_blocks": (c_int, []),
     "camd_uv_bounds_batch": (c_int, [ctypes.POINTER(CellSet), c_int, c_void_p, c_void_p, c_void_p]),
     "camd_cell_first_index_batch": (c_int, [ctypes.POINTER(CellSet), c_int, c_void_p, c_double, c_void_p, c_size_t, c_void_p,

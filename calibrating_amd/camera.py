@@ -6,7 +6,8 @@ Only the record format of the reference's ``Cam`` is mirrored (``Cam.load`` / ``
 free-form keys ``name``, ``T_in_main_cam``, ``retval``.  Intrinsic calibration itself
 (cv2.calibrateCamera, boards, caches) is outside the stereo-depth hot path.
 Two point methods of the reference's ``Cam`` run on the GPU: ``undistort_points`` and ``project_points``
-(camera.py:275-287; csrc/points.hip), the step between a matcher's raw pixels and the epipolar path.
+(camera.py:275-287; csrc/points.hip), the step between a matcher's raw pixels and the epipolar path.  So do its two
+alignment pictures, ``vis_depth_alignment`` and ``vis_reproject_img_alignment`` (camera.py:311-342; csrc/vis.hip).
 """
 import copy
 
@@ -144,3 +145,39 @@ class Cam(dict):
         from . import pointcloud
         rate = pointcloud.get_appropriate_interpolation_rate(cam1, cam2, interpolation)
         return pointcloud.reproject_img(img2, depth2, cam2.K, T, cam1.K, cam1.xy, interpolation_rate=rate)
+
+    def undistort_img(self, img):
+        """``cv2.undistort(img, K, D)`` of this camera's raw image on the GPU (uint8, ndarray or CUDA tensor)."""
+        from . import imgproc
+        from ._arrays import is_np, to_caller, to_device
+        i = to_device(img)
+        mxy, ma = imgproc.undistort_maps_device(self.K, self.D, self.xy, device=i.device)
+        return to_caller(imgproc.remap_fixed_bilinear(i, mxy, ma), is_np(img))
+
+    def vis_depth_alignment(self, img, depth):
+        """Do ``img`` (raw, not undistorted) and ``depth`` line up? (camera.py:311-320), on the GPU: the undistorted image
+        and the depth -- clipped to 5 m (5000 for uint16), divided by its maximum from a device reduction, * 255, through
+        JET * 0.75 -- as the four tiles of ``vis.vis_align``.  A depth without a positive pixel is index 0 throughout."""
+        from . import vis
+        from ._arrays import is_np, to_caller, to_device
+        n, h, w, batched, name = vis._plane(depth, "depth", vis._DEPTH_TYPES)
+        if is_np(img) != is_np(depth):
+            raise TypeError("img and depth must both be NumPy arrays or both be CUDA tensors")
+        i = self.undistort_img(to_device(img))
+        d = to_device(depth, device=i.device)
+        table = vis._device_table(vis._jet_bgr_075(), d.device)
+        pic = vis._depth_picture(d, name, n, h * w, table, clip=(0.0, 5000.0 if name == "uint16" else 5.0),
+                                 range_mode=vis._RANGE_MAX, scale=255.0, zero_mask=False, what="vis_depth_alignment")
+        tiles = vis.vis_align(i, pic.view(((n,) if batched else ()) + (h, w, 3)))
+        return [to_caller(t, is_np(img)) for t in tiles]
+
+    def vis_reproject_img_alignment(cam1, cam2, depth2, img2, img1, T=None, interpolation=1.5):
+        """Does ``img2`` of ``cam2``, brought here through ``depth2``, line up with this camera's ``img1`` (both raw)?
+        (camera.py:322-342), on the GPU: ``vis.vis_align(cam1.undistort_img(img1), cam1.reproject_img(...))``.  ``T`` = pose
+        of cam2 in this camera, required as in ``project_cam2_depth``; a distorted ``cam2`` is refused."""
+        from . import vis
+        if np.any(cam2.D):
+            raise ValueError(f"cam2.D has distort: {cam2.D}")
+        if T is None:
+            raise NotImplementedError("pass T (cam2 in cam1): board-based extrinsics are outside the MI355X path")
+        return vis.vis_align(cam1.undistort_img(img1), cam1.reproject_img(cam2, depth2, img2, T, interpolation))

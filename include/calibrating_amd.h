@@ -283,7 +283,7 @@ int camd_reproject_remap(const double* depth2, int w2, int h2, size_t depth_stri
  * values: [n][channels] of value_type, channels >= 1, contiguous; out: [h][w][channels] of the same type; pixels
  * nobody reaches get bg_value cast to that type (for CAMD_VALUE_U8 it must be an integer in 0..255).
  * keys_ws: w * h * 8 bytes, owner_ws: w * h * 4 bytes.                                                            */
-enum { CAMD_VALUE_F64 = 0, CAMD_VALUE_F32 = 1, CAMD_VALUE_U8 = 2 };
+enum { CAMD_VALUE_F64 = 0, CAMD_VALUE_F32 = 1, CAMD_VALUE_U8 = 2, CAMD_VALUE_U16 = 3 /* depth of camd_vis_depth only */ };
 int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, const double K_host[9], int w, int h,
                               const void* values, int channels, int value_type, double bg_value, void* out,
                               unsigned long long* keys_ws, uint32_t* owner_ws, void* stream);
@@ -435,6 +435,61 @@ int camd_warp_flow_backward_u8(const uint8_t* img2, int cn, size_t src_pitch, si
 int camd_warp_flow_forward_u8(const uint8_t* img1, int sw, int sh, int cn, size_t src_pitch, size_t src_stride,
                               const void* flow, int flow_type, size_t flow_stride, uint8_t* dst, int w, int h,
                               size_t dst_pitch, size_t dst_stride, int interp, int32_t* winner_ws, int batch, void* stream);
+
+/* ---- pictures (csrc/vis.hip; utils.py:463-575, 673-719): depth error, depth through a colour table, lined tiles ---------
+ * Planes are packed: image b of a batch starts at b * w * h elements (pictures: * 3 bytes, RGB).  w * h < 2^31, batch <=
+ * 65535.  Float64 arithmetic is NumPy's: every product, sum and quotient rounded once, nothing contracted.
+ *
+ * vis_depth_l1 runs in stages that share two planes, l1 (float64) and valid (uint8):
+ *   camd_vis_l1_error    l1 = (re - gt) * valid, valid = (re != 0) & (gt != 0) (utils.py:512-513).  re / gt: value_type
+ *                        CAMD_VALUE_F64 / _F32 (widened exactly); gt == NULL: the number gt_value everywhere.  With
+ *                        bar_place != CAMD_BAR_NONE the colour bar np.linspace(-bar_max_l1 * 1.1, bar_max_l1 * 1.1, length)
+ *                        is written over both planes (:519-548; bar_width = (h + w) / 100 in the reference; a bar wider than
+ *                        the side it lies along is CAMD_ERR_BAD_ARG).  maxkey[batch]: the bits of each image's largest
+ *                        |l1|, bar included.  *nonfinite: how many pixels had a NaN or an infinity in re or gt.
+ *   camd_vis_l1_limit    limit[batch] (float64): CAMD_LIMIT_FIXED = value (> 0); CAMD_LIMIT_MAX = the maximum of |l1| (from
+ *                        maxkey); CAMD_LIMIT_TOP = the |l1| at descending rank k = int(value * valid_num) among the valid
+ *                        pixels (:556-561 with value = -max_l1 inside (0, 1); k is kept below valid_num), 1.0 for an image
+ *                        without a valid pixel.  An exact radix select, 8 passes of 8 bits over the key's bit pattern,
+ *                        state per image in workspace (camd_vis_l1_limit_workspace_bytes), nothing read back.
+ *   camd_vis_l1_bar      the bar written from the limit ON THE DEVICE: max_l1=None with a colour bar, where the reference
+ *                        raises (it negates None); defined as "resolve the limit without the bar, then paint it".
+ *   camd_vis_l1_colour   :564-575: red l1 > 0, green l1 < 0, clip(0, limit) / limit * 0.9 + 0.1, masked, * 255, truncated;
+ *                        with overexposed, |l1| > limit gives G, B = 255, 0 (positive) or R, B = 230, 230 (negative).  A
+ *                        limit of 0 (0 / 0 in the reference) is defined as the normalised value 0.                  */
+enum { CAMD_BAR_NONE = 0, CAMD_BAR_UP = 1, CAMD_BAR_DOWN = 2, CAMD_BAR_LEFT = 3, CAMD_BAR_RIGHT = 4 };
+enum { CAMD_LIMIT_FIXED = 0, CAMD_LIMIT_MAX = 1, CAMD_LIMIT_TOP = 2 };
+int camd_vis_l1_error(const void* re, const void* gt, double gt_value, int value_type, int w, int h, int batch, int bar_place,
+                      int bar_width, double bar_max_l1, double* l1, uint8_t* valid, unsigned long long* maxkey,
+                      unsigned int* nonfinite, void* stream);
+size_t camd_vis_l1_limit_workspace_bytes(int batch);
+int camd_vis_l1_limit(const double* l1, const uint8_t* valid, size_t npix, int batch, int mode, double value,
+                      const unsigned long long* maxkey, void* workspace, double* limit, void* stream);
+int camd_vis_l1_bar(double* l1, uint8_t* valid, int w, int h, int batch, int bar_place, int bar_width, const double* limit,
+                    void* stream);
+int camd_vis_l1_colour(const double* l1, const uint8_t* valid, size_t npix, int batch, const double* limit, int overexposed,
+                       uint8_t* dst, void* stream);
+/* vis_depth (utils.py:466-482; camera.py:317-319): d = depth / divisor (value_type CAMD_VALUE_F64 / _F32 / _U16; divisor 1
+ * leaves it alone), zero = (d == 0), d clipped to [clip_lo, clip_hi] (+-infinity: no clip), n = (d - lo) / den, with
+ * slicen != 0 n = (n * slicen) mod 1, index = uint8(n * scale), dst = table[index] (table: 256 x 3 bytes in device
+ * memory), 0 where zero_mask and zero.  An index that is NaN (a constant image's 0 / 0) or outside 0 .. 255 is 0.
+ * range_mode CAMD_RANGE_GIVEN: lo and den are the arguments; CAMD_RANGE_NORMA: lo = min, den = max - min;
+ * CAMD_RANGE_MAX: lo = 0, den = max -- of keys[batch][2], which camd_vis_depth_range fills per image from the same d
+ * (integer atomics on order-preserving keys: exact, no host read).                                                  */
+enum { CAMD_RANGE_GIVEN = 0, CAMD_RANGE_NORMA = 1, CAMD_RANGE_MAX = 2 };
+int camd_vis_depth_range(const void* depth, int value_type, size_t npix, int batch, double divisor, double clip_lo,
+                         double clip_hi, unsigned long long* keys, void* stream);
+int camd_vis_depth(const void* depth, int value_type, size_t npix, int batch, double divisor, double clip_lo, double clip_hi,
+                   double lo, double den, const unsigned long long* keys, int range_mode, double slicen, double scale,
+                   const uint8_t* table, int zero_mask, uint8_t* dst, void* stream);
+/* vis_stereo (tiles = 2: img1 | img2) and vis_align (tiles = 4: img1 | img2 over img2 | img1) (utils.py:673-719).  Images
+ * are packed u8, w x h, cn1 / cn2 = 1 (replicated) or 3.  rows[h] / cols[2 * w] (cols NULL: none): the colour index 0 .. 5
+ * of the line through that row of a tile / that column of the mosaic, -1 for none; the host computes them in integers
+ * as the reference's loop does; columns win.  Tile t of image b is written at dst + b * image_stride + t * tile_stride
+ * with rows dst_pitch bytes apart.                                                                                 */
+int camd_vis_lines(const uint8_t* img1, int cn1, const uint8_t* img2, int cn2, int w, int h, int batch, const int8_t* rows,
+                   const int8_t* cols, int tiles, uint8_t* dst, size_t dst_pitch, size_t tile_stride, size_t image_stride,
+                   void* stream);
 
 /* ---- all triples of a multi-view reconstruction in one pass (csrc/epipolar.hip; reconstruction_epipolar_geometry.py) ----
  * The batched form of the three camd_cell_* steps above: many point sets / many pairs of grids per launch, chosen by
