@@ -34,6 +34,13 @@ void set_error(const char* fmt, ...);
         }                                                                               \
     } while (0)
 
+// every entry that launches: no usable gfx950 device -> the probe's status, its message left in place
+#define CAMD_NEED_DEVICE()                                                              \
+    do {                                                                                \
+        const int rc_ = camd_device_ok();                                               \
+        if (rc_ != CAMD_OK) return rc_;                                                 \
+    } while (0)
+
 // ---- packed 16-bit arithmetic on a dword (two u16 lanes: lo = even element, hi = odd element) ----
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 typedef short s16x2_t __attribute__((ext_vector_type(2)));
@@ -206,6 +213,34 @@ static inline int images_per_group(long long groups_per_image, int batch)
     return zb;
 }
 
-static inline bool float_type_ok(int value_type) { return value_type == CAMD_VALUE_F64 || value_type == CAMD_VALUE_F32; }
+// ---- value types: the one place a CAMD_VALUE_* code becomes a C++ type ------------------------------------------------
+// An entry checks its code with the *_type_ok of the set it accepts, then with_<set>(code, f) calls the generic callable
+// f with a value of the chosen type, so a typed launch is written once:
+//     with_float(t, [&](auto v) { using T = decltype(v); hipLaunchKernelGGL((k<T>), ..., (const T*)p, ...); });
+// and returns what f returns.  A code outside the set (the caller's check was skipped) takes the float32 arm.
+// with_float also serves the batched cell kernels (epipolar.hip), whose type code arrives per table entry on the device.
+// A new value type is a new set here (its *_type_ok and its with_*), beside the sets it extends.
+static inline bool float_type_ok(int t) { return t == CAMD_VALUE_F64 || t == CAMD_VALUE_F32; }
+static inline bool float_u8_type_ok(int t) { return float_type_ok(t) || t == CAMD_VALUE_U8; }    // owner_gather's payloads
+static inline bool float_u16_type_ok(int t) { return float_type_ok(t) || t == CAMD_VALUE_U16; }  // vis_depth's depths
+
+template <typename F>
+__host__ __device__ static inline auto with_float(int t, F&& f)
+{
+    if (t == CAMD_VALUE_F64) return f(double{});
+    return f(float{});
+}
+template <typename F>
+static inline auto with_float_u8(int t, F&& f)
+{
+    if (t == CAMD_VALUE_U8) return f(uint8_t{});
+    return with_float(t, f);
+}
+template <typename F>
+static inline auto with_float_u16(int t, F&& f)
+{
+    if (t == CAMD_VALUE_U16) return f(uint16_t{});
+    return with_float(t, f);
+}
 
 }  // namespace camd

@@ -71,20 +71,15 @@ void fill(T* p, size_t n, T v, unsigned long long* zero, hipStream_t st)
 template void fill<uint32_t>(uint32_t*, size_t, uint32_t, unsigned long long*, hipStream_t);
 template void fill<unsigned long long>(unsigned long long*, size_t, unsigned long long, unsigned long long*, hipStream_t);
 
-template <typename V>
-static void gather(const uint32_t* owner, size_t npix, const void* values, int channels, V bg, int keep, void* out,
-                   hipStream_t st)
-{
-    hipLaunchKernelGGL((k_owner_gather<V>), dim3(div_up((long long)npix, 256)), dim3(256), 0, st, owner, npix,
-                       (const V*)values, channels, bg, keep, (V*)out);
-}
-
 void owner_gather(int value_type, const uint32_t* owner, size_t npix, const void* values, int channels, double bg_value,
                   int keep, void* out, hipStream_t st)
 {
-    if (value_type == CAMD_VALUE_F64) gather<double>(owner, npix, values, channels, bg_value, keep, out, st);
-    else if (value_type == CAMD_VALUE_F32) gather<float>(owner, npix, values, channels, (float)bg_value, keep, out, st);
-    else gather<uint8_t>(owner, npix, values, channels, keep ? (uint8_t)0 : (uint8_t)bg_value, keep, out, st);
+    with_float_u8(value_type, [&](auto v) {
+        using V = decltype(v);
+        const V bg = keep ? V(0) : (V)bg_value;  // (unread with keep, and unchecked then: it need not fit a uint8)
+        hipLaunchKernelGGL((k_owner_gather<V>), dim3(div_up((long long)npix, 256)), dim3(256), 0, st, owner, npix,
+                           (const V*)values, channels, bg, keep, (V*)out);
+    });
 }
 
 }  // namespace camd

@@ -1,6 +1,6 @@
 // compact.hpp -- the building blocks that pointcloud.hip, sparse.hip and epipolar.hip share: order-preserving compaction
-// (count -> exclusive scan -> emit), the fixed-order block sum, the owner gather and the typed fill.  Every block here
-// is 256 threads = 4 waves of 64.
+// (count -> exclusive scan -> emit), the fixed-order block sum, the owner gather, the typed fill, and (with vis.hip) the
+// wave reductions and the order key of a double.  Every block here is 256 threads = 4 waves of 64.
 //
 // A compaction writes the elements that pass a predicate, in their own order, to consecutive slots:
 //   1  k_row_count   rowcount[y] = how many elements of row y pass               (one workgroup per row)
@@ -20,6 +20,35 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t c)
 {
     for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
     return c;
+}
+// likewise the largest / the smallest of the lanes' numbers
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long u = __shfl_down(v, o);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long u = __shfl_down(v, o);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
+// order-preserving map double -> u64 and back (total order of the reals; -0.0 < +0.0): doubles as keys of the integer
+// atomicMin / atomicMax, which are exact whatever order they are served in
+__device__ __forceinline__ unsigned long long order_key(double d)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double order_value(unsigned long long k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? k & 0x7fffffffffffffffull : ~k));
 }
 
 // the four waves' numbers (lane 0 of each holds its wave's) added up, returned to every thread.  part: __shared__

@@ -101,8 +101,7 @@ int camd_disp_to_depth(const int16_t* disp16, const uint8_t* valid_mask, int w, 
         set_error("camd_disp_to_depth: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     int n = w * h;
     hipLaunchKernelGGL(k_disp_to_depth, dim3(div_up(div_up(n, 2), 256), batch), dim3(256), 0, (hipStream_t)stream, disp16,
                        valid_mask, n, (float)(sgbm_min_disparity * 16), (float)add_min_disparity, translate,
@@ -118,8 +117,7 @@ int camd_unrectify_depth(const double* depth, int w, int h, const double M[3], c
         set_error("camd_unrectify_depth: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const int zb = images_per_group((long long)div_up(ow, 256) * oh, batch);
     hipLaunchKernelGGL(k_unrectify, dim3(div_up(ow, 256), oh, div_up(batch, zb)), dim3(256), 0, (hipStream_t)stream,
                        depth, w, h, M[0], M[1], M[2], mapx, mapy, out, ow, oh, batch, zb);

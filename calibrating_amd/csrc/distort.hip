@@ -149,8 +149,7 @@ int camd_distort_index_map(const double K[9], const double* dist, int ndist, int
     DistortArgs a;
     int rc = unpack_camera("camd_distort_index_map", K, dist, ndist, &a.cam, &a.k);
     if (rc != CAMD_OK) return rc;
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     a.w = w, a.h = h;
     const int n = w * h;
     const dim3 grid(div_up(n > ST_WORDS ? n : ST_WORDS, 256));
@@ -171,8 +170,7 @@ int camd_distort_depth(const void* depth, int elem_bytes, int w, int h, const in
         set_error("camd_distort_depth: bad arguments (elem_bytes is 4 or 8; out must not alias depth; batch <= 2^19)");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     if (elem_bytes == 8)
         launch_gather<double>(depth, src_index, out, w * h, batch, (hipStream_t)stream);
     else

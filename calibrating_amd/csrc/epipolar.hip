@@ -235,8 +235,7 @@ __global__ __launch_bounds__(256) void k_ep_bounds_batch(const camd_cell_set* __
     const camd_cell_set s = sets[blockIdx.y];
     double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
     int nan = 0;
-    if (s.uv_type == CAMD_VALUE_F64) ep_bounds_rows((const double*)s.uv, (size_t)s.n, lo, hi, &nan);
-    else ep_bounds_rows((const float*)s.uv, (size_t)s.n, lo, hi, &nan);
+    with_float(s.uv_type, [&](auto v) { ep_bounds_rows((const decltype(v)*)s.uv, (size_t)s.n, lo, hi, &nan); });
     double v[4] = {lo[0], lo[1], -hi[0], -hi[1]};  // four minima
     for (int k = 0; k < 4; k++) {
         for (int o = 32; o > 0; o >>= 1) v[k] = fmin(v[k], __shfl_down(v[k], o));
@@ -258,8 +257,10 @@ __global__ __launch_bounds__(256) void k_ep_first_batch(const camd_cell_set* __r
     if (i >= s.n) return;
     const EpWin w = {s.cu0, s.cv0, s.cells_w, s.cells_h};
     size_t cell;
-    const bool in = s.uv_type == CAMD_VALUE_F64 ? ep_cell((const double*)s.uv, i, 2, d, w, &cell)
-                                                : ep_cell((const float*)s.uv, i, 2, (float)d, w, &cell);
+    const bool in = with_float(s.uv_type, [&](auto v) {
+        using T = decltype(v);
+        return ep_cell((const T*)s.uv, i, 2, (T)d, w, &cell);
+    });
     if (!in) { atomicAdd(outside, 1ull); return; }
     atomicMin(grids + s.grid_offset + cell, (uint32_t)i);
 }
@@ -361,18 +362,16 @@ static int cells_entry(const char* who, const void* uv, int uv_type, size_t n, i
         set_error("%s: bad arguments", who);
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t ncell = (size_t)cells_w * cells_h;
     fill(grid, ncell, FIRST ? EP_EMPTY : 0u, outside, st);
     if (n) {
         const dim3 g(div_up((long long)n, 256));
-        if (uv_type == CAMD_VALUE_F64)
-            hipLaunchKernelGGL((k_ep_cells<double, FIRST>), g, dim3(256), 0, st, (const double*)uv, n, uv_stride, d, w, grid, outside);
-        else
-            hipLaunchKernelGGL((k_ep_cells<float, FIRST>), g, dim3(256), 0, st, (const float*)uv, n, uv_stride, (float)d, w, grid,
-                               outside);
+        with_float(uv_type, [&](auto v) {
+            using T = decltype(v);
+            hipLaunchKernelGGL((k_ep_cells<T, FIRST>), g, dim3(256), 0, st, (const T*)uv, n, uv_stride, (T)d, w, grid, outside);
+        });
     }
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
@@ -466,8 +465,7 @@ int camd_cell_intersect_count(const uint32_t* first1, const uint32_t* first2, in
     int rc = make_window(&w, 0, 0, cells_w, cells_h, "camd_cell_intersect_count");
     if (rc != CAMD_OK) return rc;
     if (!first1 || !first2 || !colcount) { set_error("camd_cell_intersect_count: NULL argument"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     row_count(EpIsect{first1, first2, cells_h, nullptr, nullptr}, cells_h, cells_w, colcount, (hipStream_t)stream);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
@@ -483,8 +481,7 @@ int camd_cell_intersect_emit(const uint32_t* first1, const uint32_t* first2, int
         set_error("camd_cell_intersect_emit: NULL argument");
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     row_emit(EpIsect{first1, first2, cells_h, idx1, idx2}, cells_h, cells_w, (const unsigned long long*)start, capacity, count,
              (hipStream_t)stream);
     CAMD_LAUNCH_CHECK();
@@ -506,15 +503,13 @@ int camd_overlap_keep(const void* uv1, const void* uv2, int uv_type, size_t n, i
         return CAMD_ERR_BAD_ARG;
     }
     if (n == 0) return CAMD_OK;
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const dim3 g(camd_overlap_blocks(n));
-    if (uv_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_ep_overlap_keep<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)uv1, (const double*)uv2,
-                           n, uv_stride, w, population1, population2, keep, blockcount);
-    else
-        hipLaunchKernelGGL((k_ep_overlap_keep<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)uv1, (const float*)uv2, n,
+    with_float(uv_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_ep_overlap_keep<T>), g, dim3(256), 0, (hipStream_t)stream, (const T*)uv1, (const T*)uv2, n,
                            uv_stride, w, population1, population2, keep, blockcount);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -527,19 +522,17 @@ int camd_overlap_emit(const void* uv1, const void* uv2, int uv_type, size_t n, i
         set_error("camd_overlap_emit: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
         fill((uint32_t*)nullptr, 0, 0u, count, st);
     } else {
         const dim3 g(camd_overlap_blocks(n));
-        if (uv_type == CAMD_VALUE_F64)
-            hipLaunchKernelGGL((k_ep_overlap_emit<double>), g, dim3(256), 0, st, (const double*)uv1, (const double*)uv2, n, uv_stride,
-                               keep, start, (double*)out1, (double*)out2, capacity, count);
-        else
-            hipLaunchKernelGGL((k_ep_overlap_emit<float>), g, dim3(256), 0, st, (const float*)uv1, (const float*)uv2, n, uv_stride,
-                               keep, start, (float*)out1, (float*)out2, capacity, count);
+        with_float(uv_type, [&](auto v) {
+            using T = decltype(v);
+            hipLaunchKernelGGL((k_ep_overlap_emit<T>), g, dim3(256), 0, st, (const T*)uv1, (const T*)uv2, n, uv_stride, keep,
+                               start, (T*)out1, (T*)out2, capacity, count);
+        });
     }
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
@@ -554,8 +547,7 @@ int camd_epipolar_sums(const double* uv1, const double* uv2, size_t n, const dou
         set_error("camd_epipolar_sums: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     EpPoses m;
     for (int i = 0; i < 9; i++) { m.k1[i] = K1inv[i]; m.k2[i] = K2inv[i]; }
     for (int c = 0; c < 4; c++) {
@@ -579,8 +571,7 @@ int camd_vector_sum(const double* z, size_t z_len, const long long* idx, size_t 
         set_error("camd_vector_sum: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const int g = sum_blocks(n);
     hipLaunchKernelGGL(k_ep_vector_partials, dim3(g), dim3(256), 0, st, z, idx, n, z_len, partials_ws);
@@ -597,17 +588,16 @@ int camd_flow_to_matched_uvs(const void* flow_abs, int flow_type, const uint8_t*
         set_error("camd_flow_to_matched_uvs: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const RowWorkspace ws(workspace, h);
     const MaskOn on = {mask, w};
     mask_row_count(on, h, ws.rowcount, st);
     row_scan(ws.rowcount, h, ws.rowoff, count, st);
-    if (flow_type == CAMD_VALUE_F64)
-        row_emit(FlowRows<double>{on, (const double*)flow_abs, uvs_from, uvs_to}, w, h, ws.rowoff, capacity, nullptr, st);
-    else
-        row_emit(FlowRows<float>{on, (const float*)flow_abs, uvs_from, uvs_to}, w, h, ws.rowoff, capacity, nullptr, st);
+    with_float(flow_type, [&](auto v) {
+        using T = decltype(v);
+        row_emit(FlowRows<T>{on, (const T*)flow_abs, uvs_from, uvs_to}, w, h, ws.rowoff, capacity, nullptr, st);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -618,15 +608,13 @@ int camd_flow_abs_to_normal(const void* flow_abs, int flow_type, int w, int h, f
         set_error("camd_flow_abs_to_normal: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const dim3 g(div_up((long long)w * h, 256));
-    if (flow_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_ep_flow_abs_to_normal<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)flow_abs, w, h,
+    with_float(flow_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_ep_flow_abs_to_normal<T>), g, dim3(256), 0, (hipStream_t)stream, (const T*)flow_abs, w, h,
                            flow_normal);
-    else
-        hipLaunchKernelGGL((k_ep_flow_abs_to_normal<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)flow_abs, w, h,
-                           flow_normal);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -638,15 +626,13 @@ int camd_flow_normal_to_abs(const void* flow_normal, int flow_type, int w, int h
         set_error("camd_flow_normal_to_abs: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const dim3 g(div_up((long long)w * h, 256));
-    if (flow_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_ep_flow_normal_to_abs<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)flow_normal, w, h,
+    with_float(flow_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_ep_flow_normal_to_abs<T>), g, dim3(256), 0, (hipStream_t)stream, (const T*)flow_normal, w, h,
                            target_w, target_h, flow_abs);
-    else
-        hipLaunchKernelGGL((k_ep_flow_normal_to_abs<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)flow_normal, w, h,
-                           target_w, target_h, flow_abs);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -659,8 +645,7 @@ int camd_uv_bounds_batch(const camd_cell_set* sets_host, int nsets, camd_cell_se
     int rc = check_sets("camd_uv_bounds_batch", sets_host, nsets, sets_dev, false, 0, &max_n);
     if (rc != CAMD_OK) return rc;
     if (!bounds) { set_error("camd_uv_bounds_batch: NULL argument"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     rc = upload(sets_host, sizeof(camd_cell_set) * nsets, sets_dev, st, "camd_uv_bounds_batch");
     if (rc != CAMD_OK) return rc;
@@ -676,8 +661,7 @@ int camd_cell_first_index_batch(const camd_cell_set* sets_host, int nsets, camd_
     int rc = check_sets("camd_cell_first_index_batch", sets_host, nsets, sets_dev, true, grid_cells, &max_n);
     if (rc != CAMD_OK) return rc;
     if (!grids || !outside || !(max_distance > 0.0)) { set_error("camd_cell_first_index_batch: bad arguments"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     rc = upload(sets_host, sizeof(camd_cell_set) * nsets, sets_dev, st, "camd_cell_first_index_batch");
     if (rc != CAMD_OK) return rc;
@@ -696,8 +680,7 @@ int camd_cell_intersect_count_batch(const uint32_t* grids, size_t grid_cells, co
     int rc = check_triples("camd_cell_intersect_count_batch", triples_host, ntriples, triples_dev, grid_cells, ncols, &max_w);
     if (rc != CAMD_OK) return rc;
     if (!grids || !colcount) { set_error("camd_cell_intersect_count_batch: NULL argument"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     rc = upload(triples_host, sizeof(camd_cell_triple) * ntriples, triples_dev, st, "camd_cell_intersect_count_batch");
     if (rc != CAMD_OK) return rc;
@@ -717,8 +700,7 @@ int camd_cell_intersect_emit_batch(const uint32_t* grids, size_t grid_cells, con
         set_error("camd_cell_intersect_emit_batch: NULL argument");
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     rc = upload(triples_host, sizeof(camd_cell_triple) * ntriples, triples_dev, st, "camd_cell_intersect_emit_batch");
     if (rc != CAMD_OK) return rc;
@@ -736,14 +718,13 @@ int camd_uvzi_pack(const void* uv, int uv_type, const double* z, size_t n, doubl
         return CAMD_ERR_BAD_ARG;
     }
     if (n == 0) return CAMD_OK;
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const dim3 g(div_up((long long)n, 256));
     double* out = rows + row_offset * 4;
-    if (uv_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_ep_uvzi_pack<double>), g, dim3(256), 0, (hipStream_t)stream, (const double*)uv, z, n, other_view, out);
-    else
-        hipLaunchKernelGGL((k_ep_uvzi_pack<float>), g, dim3(256), 0, (hipStream_t)stream, (const float*)uv, z, n, other_view, out);
+    with_float(uv_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_ep_uvzi_pack<T>), g, dim3(256), 0, (hipStream_t)stream, (const T*)uv, z, n, other_view, out);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -762,8 +743,7 @@ int camd_column_sum(const double* rows, size_t rows_total, int columns, int colu
         set_error("camd_column_sum: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const int g = sum_blocks(n);
     hipLaunchKernelGGL(k_ep_column_partials, dim3(g), dim3(256), 0, st, rows + row_offset * columns + column, n, columns, partials_ws);
@@ -780,8 +760,7 @@ int camd_column_scale(double* rows, size_t rows_total, int columns, int column, 
         return CAMD_ERR_BAD_ARG;
     }
     if (n == 0) return CAMD_OK;
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipLaunchKernelGGL(k_ep_column_scale, dim3(div_up((long long)n, 256)), dim3(256), 0, (hipStream_t)stream,
                        rows + row_offset * columns + column, n, columns, rate);
     CAMD_LAUNCH_CHECK();

@@ -128,7 +128,8 @@ static int check_warp(const char* fn, const void* img, int sw, int sh, int cn, s
         set_error("%s: interpolation %d not implemented", fn, interp);
         return CAMD_ERR_UNSUPPORTED;
     }
-    return camd_device_ok();
+    CAMD_NEED_DEVICE();
+    return CAMD_OK;
 }
 
 template <typename T>
@@ -171,11 +172,11 @@ int camd_warp_flow_backward_u8(const uint8_t* img2, int cn, size_t src_pitch, si
     const int rc = check_warp("camd_warp_flow_backward_u8", img2, w, h, cn, src_pitch, flow, flow_type, dst, w, h, dst_pitch,
                               interp, batch);
     if (rc != CAMD_OK) return rc;
-    if (flow_type == CAMD_VALUE_F64)
-        return warp_backward(img2, cn, src_pitch, src_stride, (const double*)flow, flow_stride, dst, w, h, dst_pitch,
-                             dst_stride, interp, batch, (hipStream_t)stream);
-    return warp_backward(img2, cn, src_pitch, src_stride, (const float*)flow, flow_stride, dst, w, h, dst_pitch, dst_stride,
-                         interp, batch, (hipStream_t)stream);
+    return with_float(flow_type, [&](auto v) {
+        using T = decltype(v);
+        return warp_backward(img2, cn, src_pitch, src_stride, (const T*)flow, flow_stride, dst, w, h, dst_pitch, dst_stride,
+                             interp, batch, (hipStream_t)stream);
+    });
 }
 
 int camd_warp_flow_forward_u8(const uint8_t* img1, int sw, int sh, int cn, size_t src_pitch, size_t src_stride,
@@ -189,10 +190,10 @@ int camd_warp_flow_forward_u8(const uint8_t* img1, int sw, int sh, int cn, size_
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(div_up(w, 256), h, batch), block(256);
     CAMD_HIP(hipMemsetAsync(winner_ws, 0xff, (size_t)batch * w * h * sizeof(int32_t), st));  // -1: nobody yet
-    if (flow_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_warp_forward_claim<double>), grid, block, 0, st, (const double*)flow, flow_stride, w, h, winner_ws);
-    else
-        hipLaunchKernelGGL((k_warp_forward_claim<float>), grid, block, 0, st, (const float*)flow, flow_stride, w, h, winner_ws);
+    with_float(flow_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_warp_forward_claim<T>), grid, block, 0, st, (const T*)flow, flow_stride, w, h, winner_ws);
+    });
     if (cn == 1)
         hipLaunchKernelGGL((k_warp_forward_copy<1>), grid, block, 0, st, img1, sw, sh, src_pitch, src_stride, winner_ws, dst, w,
                            h, dst_pitch, dst_stride);

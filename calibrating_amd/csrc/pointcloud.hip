@@ -31,7 +31,6 @@ __device__ __forceinline__ double pc_sample(const double* __restrict__ depth, co
     return depth[(size_t)sy * g.w + sx];
 }
 
-// order-preserving map double -> u64 (total order of the reals; -0.0 < +0.0)
 // Matrix products the way NumPy's matmul rounds them: the reference's (K^-1 @ P.T).T, (T @ P4.T).T and P @ K.T are BLAS
 // dgemm calls whose x86-64 kernels accumulate the k terms in order with fused multiply-adds, starting from the plain
 // first product.  Measured against the reference's own run (tests/golden/reference_plumbing.npz) and against NumPy on
@@ -45,16 +44,7 @@ __device__ __forceinline__ double dot4(double a0, double a1, double a2, double a
     return __fma_rn(a3, b3, __fma_rn(a2, b2, __fma_rn(a1, b1, __dmul_rn(a0, b0))));
 }
 
-__device__ __forceinline__ unsigned long long zkey(double z)
-{
-    unsigned long long b = (unsigned long long)__double_as_longlong(z);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double zkey_inv(unsigned long long k)
-{
-    unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
+// the z-buffers hold order_key(zs) (compact.hpp)
 static constexpr unsigned long long ZKEY_EMPTY = 0xffffffffffffffffull;
 
 // depth_to_point_cloud as a compaction (compact.hpp): the grid cells with a non-zero depth, in row-major order
@@ -95,7 +85,7 @@ __device__ __forceinline__ bool project_pixel(double X, double Y, double Z, cons
     const double ru = rint(u), rv = rint(v);  // np.round: half to even
     if (!(ru >= 0.0 && ru < (double)w && rv >= 0.0 && rv < (double)h)) return false;  // also drops NaN / inf
     *pix = (size_t)(int)rv * w + (int)ru;
-    *key = zkey(zs);
+    *key = order_key(zs);
     return true;
 }
 
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(256) void k_pc_resolve(const unsigned long long* __
                                                     double* __restrict__ depth)
 {
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) depth[i] = keys[i] == ZKEY_EMPTY ? bg : zkey_inv(keys[i]);
+    if (i < n) depth[i] = keys[i] == ZKEY_EMPTY ? bg : order_value(keys[i]);
 }
 
 __global__ __launch_bounds__(256) void k_apply_T(const double* __restrict__ src, size_t n, Mat34 T, double* __restrict__ dst)
@@ -167,7 +157,7 @@ __global__ __launch_bounds__(256) void k_project_depth(const double* __restrict_
 // ---- the z-buffer that remembers its winner (point_cloud_to_arr2d with values, get_reproject_remap) -----------------
 // The reference sorts the points far to near and lets the later write win (utils.py:280-288, 312-316); what arrives in
 // a pixel is the PAYLOAD of the nearest point.  Three passes over caller-provided buffers:
-//   1  keys[pix]  = min over the sources of zkey(zs)                       (atomicMin, u64; ZKEY_EMPTY = nobody)
+//   1  keys[pix]  = min over the sources of order_key(zs)                  (atomicMin, u64; ZKEY_EMPTY = nobody)
 //   2  owner[pix] = 1 + max index of the sources whose key equals keys[pix] (atomicMax, u32; 0 = nobody)
 //   3  one thread per target pixel gathers the owner's payload, or the background value
 // Two atomics passes because a 64-bit atomicMin cannot carry a 64-bit depth AND an index, and depth bits may not be
@@ -276,8 +266,7 @@ int camd_depth_to_point_cloud(const double* depth, int w, int h, const double Ki
     int rc = make_grid(&g, w, h, rate, "camd_depth_to_point_cloud");
     if (rc != CAMD_OK) return rc;
     if (!depth || !Kinv || !points || !count || !workspace) { set_error("camd_depth_to_point_cloud: NULL argument"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const RowWorkspace ws(workspace, g.gh);
     PcRows f;
@@ -294,8 +283,7 @@ int camd_apply_T_to_point_cloud(const double* points, size_t n, const double T[1
 {
     if (!T || (n && (!points || !out))) { set_error("camd_apply_T_to_point_cloud: NULL argument"); return CAMD_ERR_BAD_ARG; }
     if (n == 0) return CAMD_OK;
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     Mat34 M;
     for (int i = 0; i < 12; i++) M.m[i] = T[i];
     hipLaunchKernelGGL(k_apply_T, dim3(div_up((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, points, n, M, out);
@@ -310,8 +298,7 @@ int camd_point_cloud_to_depth(const double* points, size_t n, int point_stride, 
         set_error("camd_point_cloud_to_depth: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w * h;
     Mat33 Km;
@@ -334,8 +321,7 @@ int camd_project_depth(const double* depth2, int w2, int h2, const double K2inv[
         set_error("camd_project_depth: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w1 * h1;
     Mat33 Ki, Km;
@@ -367,8 +353,7 @@ int camd_reproject_remap(const double* depth2, int w2, int h2, size_t depth_stri
         set_error("camd_reproject_remap: a sampling grid of %d x %d cells does not fit the 32-bit owner index", g.gw, g.gh);
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w1 * h1;
     Mat33 Ki, Km;
@@ -397,7 +382,7 @@ int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, 
         set_error("camd_point_cloud_to_arr2d: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    if (value_type != CAMD_VALUE_F64 && value_type != CAMD_VALUE_F32 && value_type != CAMD_VALUE_U8) {
+    if (!float_u8_type_ok(value_type)) {
         set_error("camd_point_cloud_to_arr2d: value_type %d is none of float64 / float32 / uint8", value_type);
         return CAMD_ERR_BAD_ARG;
     }
@@ -409,8 +394,7 @@ int camd_point_cloud_to_arr2d(const double* points, size_t n, int point_stride, 
         set_error("camd_point_cloud_to_arr2d: %zu points do not fit the 32-bit owner index", n);
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w * h;
     Mat33 Km;

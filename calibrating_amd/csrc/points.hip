@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_project_points(PointsArgs a, const T* _
     store_pair<T>(out + i * 2, xd * a.cam.fx + a.cam.cx, yd * a.cam.fy + a.cam.cy);
 }
 
-static size_t value_bytes(int t) { return t == CAMD_VALUE_F64 ? 8 : 4; }
+static size_t value_bytes(int t) { return with_float(t, [](auto v) { return sizeof(v); }); }
 
 // the point calls take cv2's own coefficient counts only; then K, dist -> a
 static int camera_args(const char* who, const double K[9], const double* dist, int ndist, PointsArgs& a)
@@ -173,13 +173,11 @@ int camd_undistort_points(const void* uv, int uv_type, size_t n, int uv_stride, 
     if (rc != CAMD_OK) return rc;
     a.iters = iters, a.pixels = pixels;
     if (n == 0) return CAMD_OK;
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const hipStream_t st = (hipStream_t)stream;
-    if (uv_type == CAMD_VALUE_F64 && out_type == CAMD_VALUE_F64) launch_undistort<double, double>(a, uv, n, uv_stride, out, st);
-    else if (uv_type == CAMD_VALUE_F64) launch_undistort<double, float>(a, uv, n, uv_stride, out, st);
-    else if (out_type == CAMD_VALUE_F64) launch_undistort<float, double>(a, uv, n, uv_stride, out, st);
-    else launch_undistort<float, float>(a, uv, n, uv_stride, out, st);
+    with_float(uv_type, [&](auto vi) {
+        with_float(out_type, [&](auto vo) { launch_undistort<decltype(vi), decltype(vo)>(a, uv, n, uv_stride, out, st); });
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -198,12 +196,8 @@ int camd_project_points(const void* xyz, int xyz_type, size_t n, int xyz_stride,
     for (int i = 0; i < 9; i++) a.R[i] = R[i];
     for (int i = 0; i < 3; i++) a.t[i] = t[i];
     if (n == 0) return CAMD_OK;
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
-    if (xyz_type == CAMD_VALUE_F64)
-        launch_project<double>(a, xyz, n, xyz_stride, out, (hipStream_t)stream);
-    else
-        launch_project<float>(a, xyz, n, xyz_stride, out, (hipStream_t)stream);
+    CAMD_NEED_DEVICE();
+    with_float(xyz_type, [&](auto v) { launch_project<decltype(v)>(a, xyz, n, xyz_stride, out, (hipStream_t)stream); });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }

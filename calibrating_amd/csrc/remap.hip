@@ -263,10 +263,9 @@ int camd_remap_u8(const uint8_t* src, int sw, int sh, int cn, size_t src_pitch, 
         set_error("camd_remap_u8: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const int16_t *tl = nullptr, *tb = nullptr;
-    rc = get_tables(&tl, &tb);
+    const int rc = get_tables(&tl, &tb);
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up(dw, 256), dh, batch), block(256);
@@ -300,10 +299,9 @@ int camd_remap_fixed_bilinear_u8(const uint8_t* src, int sw, int sh, int cn, siz
         set_error("camd_remap_fixed_bilinear_u8: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const int16_t *tl = nullptr, *tb = nullptr;
-    rc = get_tables(&tl, &tb);
+    const int rc = get_tables(&tl, &tb);
     if (rc != CAMD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int zb = images_per_group(div_up(dw, 256) * dh, batch);

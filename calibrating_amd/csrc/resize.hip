@@ -172,8 +172,7 @@ int camd_resize_linear_u8(const uint8_t* src, int sw, int sh, int cn, uint8_t* d
         set_error("camd_resize_linear_u8: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     if (sw == dw && sh == dh) {
         CAMD_HIP(hipMemcpyAsync(dst, src, (size_t)batch * sw * sh * cn, hipMemcpyDeviceToDevice, st));
@@ -194,8 +193,7 @@ int camd_resize_linear_f32(const float* src, int sw, int sh, float* dst, int dw,
         set_error("camd_resize_linear_f32: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     if (sw == dw && sh == dh) {
         CAMD_HIP(hipMemcpyAsync(dst, src, (size_t)batch * sw * sh * 4, hipMemcpyDeviceToDevice, st));
@@ -221,8 +219,7 @@ int camd_disp16_resized_to_depth(const int16_t* disp16, int sw, int sh, const ui
         set_error("camd_disp16_resized_to_depth: exact 2:1 reduction is not a case of the matcher's resize back");
         return CAMD_ERR_UNSUPPORTED;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipLaunchKernelGGL(k_disp16_up_to_depth, dim3(div_up(w, 256), div_up(h, RESIZE_ROWS), batch), dim3(256), 0, (hipStream_t)stream, disp16, sw,
                        sh, valid_mask, w, h, (double)sw / w, (double)sh / h, (float)(sgbm_min_disparity * 16),
                        (float)add_min_disparity, translate, (float)w, (float)sw, baseline_fx, max_depth, disparity,

@@ -950,8 +950,7 @@ int camd_sgbm_create(const camd_sgbm_params* p, int width, int height, int chann
     int rc = normalise(p, width, height, channels, &g);
     if (rc != CAMD_OK) return rc;
     if (max_batch <= 0) { set_error("max_batch must be > 0"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     WorkspacePlan w;
     rc = plan_workspace(g, *p, max_batch, &w);
     if (rc != CAMD_OK) return rc;

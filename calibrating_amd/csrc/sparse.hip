@@ -218,8 +218,6 @@ static int make_bins(SpBins* b, int w, int h, double distance, const char* who)
     return CAMD_OK;
 }
 
-static bool value_type_ok(int t) { return t == CAMD_VALUE_F64 || t == CAMD_VALUE_F32 || t == CAMD_VALUE_U8; }
-
 }  // namespace camd
 
 using namespace camd;
@@ -233,7 +231,7 @@ int camd_uvzs_to_arr2d(const double* uv, size_t n, int uv_stride, int w, int h, 
         set_error("camd_uvzs_to_arr2d: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    if (!value_type_ok(value_type)) {
+    if (!float_u8_type_ok(value_type)) {
         set_error("camd_uvzs_to_arr2d: value_type %d is none of float64 / float32 / uint8", value_type);
         return CAMD_ERR_BAD_ARG;
     }
@@ -245,8 +243,7 @@ int camd_uvzs_to_arr2d(const double* uv, size_t n, int uv_stride, int w, int h, 
         set_error("camd_uvzs_to_arr2d: %zu rows do not fit the 32-bit owner index", n);
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w * h;
     fill(owner_ws, npix, 0u, nullptr, st);
@@ -259,8 +256,7 @@ int camd_uvzs_to_arr2d(const double* uv, size_t n, int uv_stride, int w, int h, 
 int camd_arr2d_to_uvzs(const void* arr2d, int w, int h, int as_int64, void* rows, void* stream)
 {
     if (!arr2d || !rows || w <= 0 || h <= 0) { set_error("camd_arr2d_to_uvzs: bad arguments"); return CAMD_ERR_BAD_ARG; }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const dim3 grid(div_up((long long)w * h, 256));
     if (as_int64)
         hipLaunchKernelGGL((k_sp_all_rows<long long>), grid, dim3(256), 0, (hipStream_t)stream, (const long long*)arr2d, w, h,
@@ -281,8 +277,7 @@ int camd_arr2d_to_uvzs_masked(const void* arr2d, const uint8_t* mask, int w, int
         set_error("camd_arr2d_to_uvzs_masked: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const RowWorkspace ws(workspace, h);
     const MaskOn on = {mask, w};
@@ -317,8 +312,7 @@ int camd_sparse_bin_count(const double* uv, size_t n, int uv_stride, int w, int 
         set_error("camd_sparse_bin_count: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t ncell = (size_t)b.bw * b.bh;
     fill(counts, ncell, 0u, nullptr, st);
@@ -338,8 +332,7 @@ int camd_sparse_bin_fill(const double* uv, size_t n, int uv_stride, int w, int h
         return CAMD_ERR_BAD_ARG;
     }
     if (n == 0) return CAMD_OK;
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipLaunchKernelGGL(k_sp_bin_fill, dim3(div_up((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, uv, n, uv_stride, b,
                        cursor, capacity, sorted_uv, sorted_idx);
     CAMD_LAUNCH_CHECK();
@@ -352,12 +345,11 @@ int camd_nearest_fill(const double* sorted_uv, const uint32_t* sorted_idx, const
     SpBins b;
     int rc = make_bins(&b, w, h, distance, "camd_nearest_fill");
     if (rc != CAMD_OK) return rc;
-    if (!start || !out || out_w <= 0 || out_h <= 0 || out_h > 65535 || (z_type != CAMD_VALUE_F64 && z_type != CAMD_VALUE_F32)) {
+    if (!start || !out || out_w <= 0 || out_h <= 0 || out_h > 65535 || !float_type_ok(z_type)) {
         set_error("camd_nearest_fill: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     SpOut o;
     o.ow = out_w; o.oh = out_h;
     o.scaled = (out_w != w || out_h != h) ? 1 : 0;
@@ -365,12 +357,11 @@ int camd_nearest_fill(const double* sorted_uv, const uint32_t* sorted_idx, const
     o.ify = 1.0 / ((double)out_h / h);
     o.mul = (float)out_w; o.div = (float)w;
     const dim3 grid(div_up(out_w, 256), out_h);
-    if (z_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_sp_nearest<double>), grid, dim3(256), 0, (hipStream_t)stream, sorted_uv, sorted_idx, start,
-                           (const double*)z, b, distance, o, out);
-    else
-        hipLaunchKernelGGL((k_sp_nearest<float>), grid, dim3(256), 0, (hipStream_t)stream, sorted_uv, sorted_idx, start,
-                           (const float*)z, b, distance, o, out);
+    with_float(z_type, [&](auto v) {
+        using Z = decltype(v);
+        hipLaunchKernelGGL((k_sp_nearest<Z>), grid, dim3(256), 0, (hipStream_t)stream, sorted_uv, sorted_idx, start,
+                           (const Z*)z, b, distance, o, out);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -380,18 +371,17 @@ int camd_plane_sums_blocks(size_t n) { return sum_blocks(n); }
 int camd_plane_sums(const double* uv, int uv_stride, const void* z, int z_type, size_t n, double* partials_ws, double* sums,
                     void* stream)
 {
-    if (!uv || !z || !partials_ws || !sums || n == 0 || uv_stride < 2 || (z_type != CAMD_VALUE_F64 && z_type != CAMD_VALUE_F32)) {
+    if (!uv || !z || !partials_ws || !sums || n == 0 || uv_stride < 2 || !float_type_ok(z_type)) {
         set_error("camd_plane_sums: bad arguments");
         return CAMD_ERR_BAD_ARG;
     }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const int g = sum_blocks(n);
-    if (z_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_sp_plane_partials<double>), dim3(g), dim3(256), 0, st, uv, uv_stride, (const double*)z, n, partials_ws);
-    else
-        hipLaunchKernelGGL((k_sp_plane_partials<float>), dim3(g), dim3(256), 0, st, uv, uv_stride, (const float*)z, n, partials_ws);
+    with_float(z_type, [&](auto v) {
+        using Z = decltype(v);
+        hipLaunchKernelGGL((k_sp_plane_partials<Z>), dim3(g), dim3(256), 0, st, uv, uv_stride, (const Z*)z, n, partials_ws);
+    });
     hipLaunchKernelGGL(k_sp_plane_final, dim3(1), dim3(64), 0, st, partials_ws, g, sums);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
@@ -400,8 +390,7 @@ int camd_plane_sums(const double* uv, int uv_stride, const void* z, int z_type, 
 int camd_plane_eval(double a, double b, double c, int w, int h, float* out, void* stream)
 {
     if (!out || w <= 0 || h <= 0 || h > 65535) { set_error("camd_plane_eval: bad arguments"); return CAMD_ERR_BAD_ARG; }
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipLaunchKernelGGL(k_sp_plane_eval, dim3(div_up(w, 256), h), dim3(256), 0, (hipStream_t)stream, a, b, c, w, out);
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
@@ -415,8 +404,7 @@ int camd_matched_uvs_to_zs(const double* uv1, const double* uv2, size_t n, const
         return CAMD_ERR_BAD_ARG;
     }
     if (n == 0) return CAMD_OK;
-    int rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     SpTri m;
     for (int i = 0; i < 9; i++) { m.k1[i] = K1inv[i]; m.k2[i] = K2inv[i]; m.R[i] = T_1to2[(i / 3) * 4 + i % 3]; }
     for (int i = 0; i < 3; i++) m.t[i] = T_1to2[i * 4 + 3];

@@ -107,8 +107,7 @@ int camd_init_undistort_rectify_map(const double A[9], const double* dist, int n
     int rc = fill_args(&a, A, dist, ndist, w, h, "camd_init_undistort_rectify_map");
     if (rc != CAMD_OK) return rc;
     if (!Anew || !mapx || !mapy) { set_error("camd_init_undistort_rectify_map: NULL argument"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     const double* Rm = R ? R : I3;
     for (int i = 0; i < 3; i++)  // Anew * R, the accumulation order of a plain triple loop (s = 0; s += a*b)
@@ -132,8 +131,7 @@ int camd_undistort_maps(const double K[9], const double* dist, int ndist, int w,
     int rc = fill_args(&a, K, dist, ndist, w, h, "camd_undistort_maps");
     if (rc != CAMD_OK) return rc;
     if (!mapxy || !mapa) { set_error("camd_undistort_maps: NULL argument"); return CAMD_ERR_BAD_ARG; }
-    rc = camd_device_ok();
-    if (rc != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     for (int i = 0; i < 9; i++) a.New[i] = K[i];
     hipLaunchKernelGGL((k_undistort_rectify_map<true>), dim3(h), dim3(256), 0, (hipStream_t)stream, a, (float*)nullptr,
                        (float*)nullptr, (uint8_t*)nullptr, mapxy, mapa);

@@ -53,23 +53,6 @@ __device__ __forceinline__ bool in_bar(const L1Bar& b, int x, int y)
     return x >= b.x0 && x < b.x0 + b.bw && y >= b.y0 && y < b.y0 + b.bh;
 }
 
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = __shfl_down(v, o);
-        v = u > v ? u : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = __shfl_down(v, o);
-        v = u < v ? u : v;
-    }
-    return v;
-}
-
 // ---- vis_depth_l1, error pass ----------------------------------------------------------------------------------------
 // l1 = (re - gt) * mask_valid, the bar written over it when its limit is known on the host (paint), the largest |l1| of
 // the image (bits, atomicMax: exact whatever the order) and the count of non-finite inputs.  gt == NULL: the number
@@ -236,17 +219,6 @@ __global__ __launch_bounds__(256) void k_l1_colour(const double* __restrict__ l1
 }
 
 // ---- vis_depth ---------------------------------------------------------------------------------------------------------
-// doubles as unsigned keys in their own order (for integer atomicMin / atomicMax: exact whatever the order)
-__device__ __forceinline__ unsigned long long order_key(double d)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
-}
-__device__ __forceinline__ double order_value(unsigned long long k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? k & 0x7fffffffffffffffull : ~k));
-}
-
 __device__ __forceinline__ double depth_value(double d, double divisor, double clip_lo, double clip_hi, bool* zero)
 {
     if (divisor != 1.0) d = __ddiv_rn(d, divisor);
@@ -390,8 +362,6 @@ static int reduce_blocks(size_t npix, int cap)
     return (int)(g < 1 ? 1 : g > (size_t)cap ? (size_t)cap : g);
 }
 
-static inline bool depth_type_ok(int t) { return float_type_ok(t) || t == CAMD_VALUE_U16; }
-
 }  // namespace camd
 
 using namespace camd;
@@ -411,19 +381,18 @@ int camd_vis_l1_error(const void* re, const void* gt, double gt_value, int value
     }
     L1Bar bar{0, 0, 0, 0, 0, 0};
     if (bar_place != CAMD_BAR_NONE && (rc = make_bar(fn, bar_place, bar_width, w, h, &bar)) != CAMD_OK) return rc;
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     const size_t npix = (size_t)w * h;
     CAMD_HIP(hipMemsetAsync(maxkey, 0, (size_t)batch * sizeof(unsigned long long), st));
     CAMD_HIP(hipMemsetAsync(nonfinite, 0, sizeof(unsigned int), st));
     const dim3 grid(reduce_blocks(npix, REDUCE_MAX_BLOCKS), batch);
     const int paint = bar_place != CAMD_BAR_NONE && bar.bw > 0 && bar.bh > 0;
-    if (value_type == CAMD_VALUE_F64)
-        hipLaunchKernelGGL((k_l1_error<double>), grid, dim3(256), 0, st, (const double*)re, (const double*)gt, gt_value, w, npix,
-                           bar, paint, bar_max_l1, l1, valid, maxkey, nonfinite);
-    else
-        hipLaunchKernelGGL((k_l1_error<float>), grid, dim3(256), 0, st, (const float*)re, (const float*)gt, gt_value, w, npix, bar,
-                           paint, bar_max_l1, l1, valid, maxkey, nonfinite);
+    with_float(value_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_l1_error<T>), grid, dim3(256), 0, st, (const T*)re, (const T*)gt, gt_value, w, npix, bar, paint,
+                           bar_max_l1, l1, valid, maxkey, nonfinite);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -440,7 +409,7 @@ int camd_vis_l1_bar(double* l1, uint8_t* valid, int w, int h, int batch, int bar
     }
     L1Bar bar;
     if ((rc = make_bar(fn, bar_place, bar_width, w, h, &bar)) != CAMD_OK) return rc;
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const size_t nbar = (size_t)bar.bw * bar.bh;
     if (nbar == 0) return CAMD_OK;
     hipLaunchKernelGGL(k_l1_bar, dim3(div_up((long long)nbar, 256), batch), dim3(256), 0, (hipStream_t)stream, l1, valid, w,
@@ -476,7 +445,7 @@ int camd_vis_l1_limit(const double* l1, const uint8_t* valid, size_t npix, int b
         set_error("%s: the top fraction must lie inside (0, 1), with planes and a workspace", fn);
         return CAMD_ERR_BAD_ARG;
     }
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     if (mode == CAMD_LIMIT_FIXED) {
         hipLaunchKernelGGL(k_limit_fixed, dim3(div_up(batch, 256)), dim3(256), 0, st, limit, batch, value);
@@ -506,7 +475,7 @@ int camd_vis_l1_colour(const double* l1, const uint8_t* valid, size_t npix, int 
         set_error("%s: bad arguments", fn);
         return CAMD_ERR_BAD_ARG;
     }
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipLaunchKernelGGL(k_l1_colour, dim3(div_up((long long)npix, 256), batch), dim3(256), 0, (hipStream_t)stream, l1, valid,
                        npix, limit, overexposed, dst);
     CAMD_LAUNCH_CHECK();
@@ -519,20 +488,18 @@ int camd_vis_depth_range(const void* depth, int value_type, size_t npix, int bat
     static const char* fn = "camd_vis_depth_range";
     int rc = check_pixels(fn, npix, batch);
     if (rc != CAMD_OK) return rc;
-    if (!depth || !keys || !depth_type_ok(value_type) || !(divisor > 0.0) || !(clip_lo <= clip_hi)) {
+    if (!depth || !keys || !float_u16_type_ok(value_type) || !(divisor > 0.0) || !(clip_lo <= clip_hi)) {
         set_error("%s: bad arguments", fn);
         return CAMD_ERR_BAD_ARG;
     }
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_range_init, dim3(div_up(batch, 256)), dim3(256), 0, st, keys, batch);
     const dim3 grid(reduce_blocks(npix, REDUCE_MAX_BLOCKS), batch);
-#define RANGE(T) \
-    hipLaunchKernelGGL((k_depth_range<T>), grid, dim3(256), 0, st, (const T*)depth, npix, divisor, clip_lo, clip_hi, keys)
-    if (value_type == CAMD_VALUE_F64) RANGE(double);
-    else if (value_type == CAMD_VALUE_F32) RANGE(float);
-    else RANGE(uint16_t);
-#undef RANGE
+    with_float_u16(value_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_depth_range<T>), grid, dim3(256), 0, st, (const T*)depth, npix, divisor, clip_lo, clip_hi, keys);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -544,21 +511,19 @@ int camd_vis_depth(const void* depth, int value_type, size_t npix, int batch, do
     static const char* fn = "camd_vis_depth";
     int rc = check_pixels(fn, npix, batch);
     if (rc != CAMD_OK) return rc;
-    if (!depth || !table || !dst || !depth_type_ok(value_type) || !(divisor > 0.0) || !(clip_lo <= clip_hi) ||
+    if (!depth || !table || !dst || !float_u16_type_ok(value_type) || !(divisor > 0.0) || !(clip_lo <= clip_hi) ||
         range_mode < CAMD_RANGE_GIVEN || range_mode > CAMD_RANGE_MAX || (range_mode != CAMD_RANGE_GIVEN && !keys) ||
         !(scale > 0.0 && scale < 256.0) || !(slicen >= 0.0)) {
         set_error("%s: bad arguments", fn);
         return CAMD_ERR_BAD_ARG;
     }
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     const dim3 grid(div_up((long long)npix, 256), batch);
-#define DEPTH(T)                                                                                                          \
-    hipLaunchKernelGGL((k_vis_depth<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)depth, npix, divisor, clip_lo, \
-                       clip_hi, lo, den, keys, range_mode, slicen, scale, table, zero_mask, dst)
-    if (value_type == CAMD_VALUE_F64) DEPTH(double);
-    else if (value_type == CAMD_VALUE_F32) DEPTH(float);
-    else DEPTH(uint16_t);
-#undef DEPTH
+    with_float_u16(value_type, [&](auto v) {
+        using T = decltype(v);
+        hipLaunchKernelGGL((k_vis_depth<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)depth, npix, divisor, clip_lo,
+                           clip_hi, lo, den, keys, range_mode, slicen, scale, table, zero_mask, dst);
+    });
     CAMD_LAUNCH_CHECK();
     return CAMD_OK;
 }
@@ -575,7 +540,7 @@ int camd_vis_lines(const uint8_t* img1, int cn1, const uint8_t* img2, int cn2, i
         set_error("%s: bad arguments (images have 1 or 3 channels, 2 or 4 tiles, a pitch of at least a row)", fn);
         return CAMD_ERR_BAD_ARG;
     }
-    if ((rc = camd_device_ok()) != CAMD_OK) return rc;
+    CAMD_NEED_DEVICE();
     hipLaunchKernelGGL(k_vis_lines, dim3(div_up((long long)w * h, 256), batch, tiles), dim3(256), 0, (hipStream_t)stream, img1,
                        cn1, img2, cn2, w, (size_t)w * h, rows, cols, dst, dst_pitch, tile_stride, image_stride);
     CAMD_LAUNCH_CHECK();
