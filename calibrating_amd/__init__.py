@@ -16,6 +16,8 @@ from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, f
                                 matching_uvs_in_one_img_batch)
 from .reconstruction_epipolar_geometry import ReconstructionExtrinsics
 from .flow_utils import warp_flow
+from .geometry import mean_Ts
+from .pnp import solve_pnp_batch
 from .vis import resolve_max_l1, vis_align, vis_depth, vis_depth_l1, vis_stereo
 
 __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "StereoSGBM",
@@ -23,4 +25,4 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "FeatureMatchingAsStereoMatching", "EssentialMatrixStereo", "filter_overlap_uvs", "matching_uvs_in_one_img",
            "flow_abs_to_normal", "flow_normal_to_abs", "flow_to_matched_uvs", "build_set2ds_by_flowds",
            "matching_uvs_in_one_img_batch", "ReconstructionExtrinsics", "warp_flow", "vis_depth", "vis_depth_l1",
-           "resolve_max_l1", "vis_stereo", "vis_align"]
+           "resolve_max_l1", "vis_stereo", "vis_align", "solve_pnp_batch", "mean_Ts"]

@@ -60,6 +60,12 @@ class CellTriple(ctypes.Structure):  # camd_cell_triple
                 ("cells_w", c_int), ("cells_h", c_int)]
 
 
+class PnpPoints(ctypes.Structure):  # camd_pnp_points
+    _fields_ = [("object", c_void_p), ("image", c_void_p), ("start", c_void_p), ("object_rows", ctypes.c_ulonglong),
+                ("image_rows", ctypes.c_ulonglong), ("object_type", c_int), ("image_type", c_int), ("object_stride", c_int),
+                ("image_stride", c_int), ("object_shared", c_int), ("frames", c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/calibrating_amd.h declares
 SIGNATURES = {
     "camd_last_error": (ctypes.c_char_p, []),
@@ -185,6 +191,9 @@ SIGNATURES = {
                                       c_void_p]),
     "camd_project_points": (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                     c_void_p]),
+    "camd_pnp_init": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_pnp_refine": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

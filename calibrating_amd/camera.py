@@ -7,7 +7,9 @@ free-form keys ``name``, ``T_in_main_cam``, ``retval``.  Intrinsic calibration i
 (cv2.calibrateCamera, boards, caches) is outside the stereo-depth hot path.
 Two point methods of the reference's ``Cam`` run on the GPU: ``undistort_points`` and ``project_points``
 (camera.py:275-287; csrc/points.hip), the step between a matcher's raw pixels and the epipolar path.  So do its two
-alignment pictures, ``vis_depth_alignment`` and ``vis_reproject_img_alignment`` (camera.py:311-342; csrc/vis.hip).
+alignment pictures, ``vis_depth_alignment`` and ``vis_reproject_img_alignment`` (camera.py:311-342; csrc/vis.hip), and the
+pose of a target from its detected points: ``perspective_n_point``, ``solve_poses`` for every stored frame in one launch,
+``get_T_cam2_in_self`` (camera.py:266-273, 289-296; csrc/pnp.hip).  Detecting the points stays with the caller.
 """
 import copy
 
@@ -125,12 +127,83 @@ class Cam(dict):
         from . import imgproc
         return imgproc.undistort_points(uvs, self.K, self.D, iters=iters, pixels=True)
 
+    # ---- poses from points (camera.py:148-149, 266-273, 289-296, 371-372; csrc/pnp.hip) ----
+    @property
+    def valid_keys(self):
+        """The frames in which the target was seen: keys whose record holds at least one image point (or id)."""
+        return {key for key, frame in self.items() if len(frame.get("image_points", ()))}
+
+    def valid_keys_intersection(cam1, cam2):
+        """The frames in which both cameras saw the target, sorted."""
+        return sorted(cam1.valid_keys & cam2.valid_keys)
+
+    def perspective_n_point_batch(self, image_points, object_points, counts=None, T0=None):
+        """``pnp.solve_pnp_batch`` with this camera's K and D: the poses of one target in many frames, one launch."""
+        from . import pnp
+        return pnp.solve_pnp_batch(object_points, image_points, self.K, self.D, counts=counts, T0=T0)
+
+    def perspective_n_point(self, image_points, object_points):
+        """The pose of a target from its points (camera.py:266-273: cv2.solvePnPGeneric), on the GPU -> the reference's
+        ``dict(T=(4, 4), retval=1, reprojection_error=...)``.  The points are (n, 2) / (n, 3) arrays or the reference's
+        id -> points dicts, joined in sorted-key order.  ``T`` is the float64 pose itself (the reference rounds it through
+        a float32 Rodrigues vector).  A frame that cannot be solved raises ``ValueError`` with its status."""
+        from . import geometry, pnp
+        image_points = geometry.join_points(image_points)
+        object_points = geometry.join_points(object_points)
+        if getattr(image_points, "ndim", 0) == 3 and image_points.shape[1] == 1:
+            image_points = image_points[:, 0]
+        res = self.perspective_n_point_batch(image_points[None], object_points[None])
+        status = int(res["status"][0])
+        if status != pnp.STATUS_OK:
+            raise ValueError("perspective_n_point: status %d (%s)" % (status, pnp.STATUS_TEXT[status]))
+        return dict(T=res["T"][0], retval=1, reprojection_error=res["reprojection_error"][0])
+
+    def solve_poses(self):
+        """``cam[key]["T"]`` and ``cam[key]["reprojection_error"]`` for every valid key whose record also holds
+        ``object_points`` (a valid key without them is left alone), in ONE launch over all frames.  The stored points are
+        host data -- ndarrays, or id -> ndarray dicts --, as the reference's detectors leave them; points on the GPU go
+        through ``perspective_n_point_batch``.  Returns key -> status word; a frame whose status is not 0 gets no pose
+        (and loses an earlier one)."""
+        from . import geometry
+        keys = sorted(k for k in self.valid_keys if "object_points" in self[k])
+        if not keys:
+            return {}
+        uvs = [np.asarray(geometry.join_points(self[k]["image_points"])).reshape(-1, 2) for k in keys]
+        xyzs = [np.asarray(geometry.join_points(self[k]["object_points"])).reshape(-1, 3) for k in keys]
+        for k, a, b in zip(keys, uvs, xyzs):
+            if len(a) != len(b):
+                raise ValueError("%r: %d image points and %d object points" % (k, len(a), len(b)))
+        res = self.perspective_n_point_batch(np.concatenate(uvs), np.concatenate(xyzs), counts=[len(a) for a in uvs])
+        for i, k in enumerate(keys):
+            d = self[k]
+            if res["status"][i] == 0:
+                d["T"], d["reprojection_error"] = res["T"][i], float(res["reprojection_error"][i])
+            else:
+                d.pop("T", None)
+                d.pop("reprojection_error", None)
+        return {k: int(s) for k, s in zip(keys, res["status"])}
+
+    def _pose_keys(cam1, cam2):
+        return [k for k in cam1.valid_keys_intersection(cam2) if "T" in cam1[k] and "T" in cam2[k]]
+
+    def get_T_cam2_in_self(cam1, cam2):
+        """The pose of ``cam2`` in this camera from the frames both have a pose for (camera.py:289-296): per common key
+        ``cam1[key]["T"] @ inv(cam2[key]["T"])``, then ``geometry.mean_Ts``.  Host, float64."""
+        from . import geometry
+        return geometry.mean_Ts([cam1[key]["T"] @ np.linalg.inv(cam2[key]["T"]) for key in cam1._pose_keys(cam2)])
+
+    def _resolve_T_cam2(cam1, cam2, T):
+        if T is not None:
+            return T
+        if not (isinstance(cam2, Cam) and cam1._pose_keys(cam2)):
+            raise NotImplementedError("pass T (cam2 in cam1): board-based extrinsics are outside the MI355X path")
+        return cam1.get_T_cam2_in_self(cam2)
+
     def project_cam2_depth(cam1, cam2, depth2, T=None, interpolation=1.5):
         """Depth image of ``cam2`` re-projected into this camera (camera.py:298-309), on the GPU.
-        ``T`` = pose of cam2 in this camera (4x4); the reference's fallback that derives it from calibration
-        board detections (``get_T_cam2_in_self``) is outside the MI355X path, so ``T`` is required."""
-        if T is None:
-            raise NotImplementedError("pass T (cam2 in cam1): board-based extrinsics are outside the MI355X path")
+        ``T`` = pose of cam2 in this camera (4x4); None resolves through ``get_T_cam2_in_self`` when both cameras carry
+        poses under a common key (``solve_poses``), and is refused otherwise: detecting a board is the caller's."""
+        T = cam1._resolve_T_cam2(cam2, T)
         from . import pointcloud
         rate = pointcloud.get_appropriate_interpolation_rate(cam1, cam2, interpolation)
         return pointcloud.project_depth(depth2, cam2.K, T, cam1.K, cam1.xy, interpolation_rate=rate)
@@ -140,8 +213,7 @@ class Cam(dict):
         ``vis_reproject_img_alignment`` (camera.py:322-342), on the GPU; ``Stereo.undistort_img`` gives the other half.
         ``T`` = pose of cam2 in this camera (4x4), required as in ``project_cam2_depth``."""
         assert not np.any(cam2.D), f"cam2.D has distort: {cam2.D}"
-        if T is None:
-            raise NotImplementedError("pass T (cam2 in cam1): board-based extrinsics are outside the MI355X path")
+        T = cam1._resolve_T_cam2(cam2, T)
         from . import pointcloud
         rate = pointcloud.get_appropriate_interpolation_rate(cam1, cam2, interpolation)
         return pointcloud.reproject_img(img2, depth2, cam2.K, T, cam1.K, cam1.xy, interpolation_rate=rate)
@@ -178,6 +250,5 @@ class Cam(dict):
         from . import vis
         if np.any(cam2.D):
             raise ValueError(f"cam2.D has distort: {cam2.D}")
-        if T is None:
-            raise NotImplementedError("pass T (cam2 in cam1): board-based extrinsics are outside the MI355X path")
+        T = cam1._resolve_T_cam2(cam2, T)
         return vis.vis_align(cam1.undistort_img(img1), cam1.reproject_img(cam2, depth2, img2, T, interpolation))

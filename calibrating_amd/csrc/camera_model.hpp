@@ -3,7 +3,8 @@
 // Two forward forms, because cv2's two call sites order the polynomial differently and every bit matters (a one-ulp
 // difference moves a pixel across a truncation border): distort_forward is cv2.projectPoints (powers
 // r2, r4, r6 and a reciprocal; U22 / U24), distort_horner is cv2.initUndistortRectifyMap (Horner chains and a quotient).
-// The iteration of cv2.undistortPoints (U23) is a third order, used once: it stays in points.hip and only reads the Lens.
+// The iteration of cv2.undistortPoints (U23) is a third order: undistort_iterate, for points.hip and the start pose of pnp.hip.
+// distort_forward_jacobian is the analytic derivative of distort_forward, for the Levenberg-Marquardt of pnp.hip.
 #pragma once
 
 #include <cmath>
@@ -40,6 +41,41 @@ __device__ __forceinline__ void distort_forward(const Lens& k, double x, double 
     const double icdist2 = __ddiv_rn(1., 1 + k.k4 * r2 + k.k5 * r4 + k.k6 * r6);
     xd = x * cdist * icdist2 + k.p1 * a1 + k.p2 * a2 + k.s1 * r2 + k.s2 * r4;
     yd = y * cdist * icdist2 + k.p1 * a3 + k.p2 * a1 + k.s3 * r2 + k.s4 * r4;
+}
+
+// d(xd, yd) / d(x, y) of distort_forward, row-major {dxd/dx, dxd/dy, dyd/dx, dyd/dy}: the chain rule through r2 on the
+// same polynomial (q = cdist * icdist2; dq/dr2 = (cdist' - q * den') * icdist2)
+__device__ __forceinline__ void distort_forward_jacobian(const Lens& k, double x, double y, double j[4])
+{
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double cdist = 1 + k.k1 * r2 + k.k2 * r4 + k.k3 * r6;
+    const double icdist2 = __ddiv_rn(1., 1 + k.k4 * r2 + k.k5 * r4 + k.k6 * r6);
+    const double q = cdist * icdist2;
+    const double dq = ((k.k1 + 2 * k.k2 * r2 + 3 * k.k3 * r4) - q * (k.k4 + 2 * k.k5 * r2 + 3 * k.k6 * r4)) * icdist2;
+    const double gx = 2 * x * dq, gy = 2 * y * dq;  // dq/dx, dq/dy
+    j[0] = q + x * gx + 2 * k.p1 * y + 6 * k.p2 * x + 2 * k.s1 * x + 4 * k.s2 * r2 * x;
+    j[1] = x * gy + 2 * k.p1 * x + 2 * k.p2 * y + 2 * k.s1 * y + 4 * k.s2 * r2 * y;
+    j[2] = y * gx + 2 * k.p1 * x + 2 * k.p2 * y + 2 * k.s3 * x + 4 * k.s4 * r2 * x;
+    j[3] = q + y * gy + 6 * k.p1 * y + 2 * k.p2 * x + 2 * k.s3 * y + 4 * k.s4 * r2 * y;
+}
+
+// cv2.undistortPoints' fixed-point iteration from the normalised raw point (xs, ys): `iters` rounds, the same trip count
+// for every lane -- a lane that met icdist < 0 keeps its start value through selects
+__device__ __forceinline__ void undistort_iterate(const Lens& k, double xs, double ys, int iters, double& x, double& y)
+{
+    x = xs, y = ys;
+    bool done = false;
+    for (int j = 0; j < iters; j++) {
+        const double r2 = x * x + y * y;
+        const double icdist = __ddiv_rn(1 + ((k.k6 * r2 + k.k5) * r2 + k.k4) * r2, 1 + ((k.k3 * r2 + k.k2) * r2 + k.k1) * r2);
+        const double dX = 2 * k.p1 * x * y + k.p2 * (r2 + 2 * x * x) + k.s1 * r2 + k.s2 * r2 * r2;
+        const double dY = k.p1 * (r2 + 2 * y * y) + 2 * k.p2 * x * y + k.s3 * r2 + k.s4 * r2 * r2;
+        const bool neg = icdist < 0;
+        const double xn = neg ? xs : (xs - dX) * icdist, yn = neg ? ys : (ys - dY) * icdist;
+        x = done ? x : xn;
+        y = done ? y : yn;
+        done = done || neg;
+    }
 }
 
 // cv2.initUndistortRectifyMap on a normalised point

@@ -1,0 +1,511 @@
+// pnp.hip -- the pose of a target in every frame of a recording from its detected points (batched PnP).
+//
+// Replaces (file:line in the reference's calibrating/):
+//   camera.py:266-273   cv2.solvePnPGeneric(object_points, image_points[:, None], K, D) -> rvecs[0], tvecs[0], RMS
+// One wavefront per frame, four frames per 256-thread workgroup and NO workgroup barrier anywhere: the waves of a group
+// belong to different frames and run different numbers of iterations.  The lanes of a wave stride over the frame's
+// points and keep partial sums; an xor butterfly of fixed order leaves the same bits of every sum in every lane, so all
+// that follows (a 6x6 / 9x9 / 12x12 Cholesky, the damping rule, the stopping rule) is computed by every lane, redundantly
+// and uniformly, and a frame's result depends on nothing but its own rows: alone or at any place of a batch it gets
+// the same bits.  Every loop has a trip count bounded by a constant or by the frame's point count.
+//
+// cv2's own solver is UNPINNED: this is a float64 Levenberg-Marquardt on raw, distorted
+// pixels run to float64 convergence; cv2 stops after 20 iterations at FLT_EPSILON.
+#include <climits>
+
+#include "camera_model.hpp"
+
+namespace camd {
+
+enum { PNP_OK = 0, PNP_FEW = 1, PNP_NONFINITE = 2, PNP_SINGULAR = 3 };
+constexpr int PNP_MAX_ITERATIONS = 100;
+constexpr int PNP_UNDISTORT_ITERS = 10;  // rounds of cv2.undistortPoints' iteration for the start pose (cv2 runs 5)
+constexpr double PNP_SINGULAR_PIVOT = 1e-10;  // smallest pivot of the unit-diagonal normal matrix that still counts as a pose
+
+struct PnpArgs {
+    Pinhole cam;
+    Lens k;
+    camd_pnp_points p;
+    double plane[9];  // camd_pnp_init, planar: the rotation that lays the target's plane on z = const
+    int planar, min_points;
+};
+
+// sum over the wave, the same bits in every lane: lane i adds lane i ^ m, and a + b == b + a
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_or(int v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v |= __shfl_xor(v, m, 64);
+    return v;
+}
+// a flag every lane agrees on, as a scalar: the branches on it are uniform and the wave stays whole for the butterflies
+__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+
+__device__ __forceinline__ double load_value(const void* p, int type, size_t i)
+{
+    return with_float(type, [&](auto v) { return (double)((const decltype(v)*)p)[i]; });
+}
+
+// the rows of one frame, checked: [s, s + n) of the image rows, the same of the object rows or [0, n) of a shared block
+struct Frame {
+    size_t uv0, obj0;
+    int n, status;
+};
+
+__device__ __forceinline__ Frame frame_rows(const camd_pnp_points& p, int f, int min_points)
+{
+    Frame fr = {0, 0, 0, PNP_OK};
+    const long long s = p.start[f], e = p.start[f + 1];
+    const unsigned long long obj_rows = p.object_rows;
+    if (s < 0 || e < s || (unsigned long long)e > p.image_rows || e - s > INT_MAX ||
+        (unsigned long long)(p.object_shared ? e - s : e) > obj_rows) {
+        fr.status = PNP_NONFINITE;  // a range outside the rows: nothing of it is read
+        return fr;
+    }
+    fr.n = (int)(e - s), fr.uv0 = (size_t)s, fr.obj0 = p.object_shared ? 0 : (size_t)s;
+    if (fr.n < min_points) fr.status = PNP_FEW;
+    return fr;
+}
+
+__device__ __forceinline__ void load_point(const camd_pnp_points& p, const Frame& fr, int i, double X[3], double uv[2])
+{
+    const size_t o = (fr.obj0 + i) * (size_t)p.object_stride, q = (fr.uv0 + i) * (size_t)p.image_stride;
+    X[0] = load_value(p.object, p.object_type, o), X[1] = load_value(p.object, p.object_type, o + 1);
+    X[2] = load_value(p.object, p.object_type, o + 2);
+    uv[0] = load_value(p.image, p.image_type, q), uv[1] = load_value(p.image, p.image_type, q + 1);
+}
+
+// 1 when any coordinate of the frame is NaN or infinite (every lane gets the answer)
+__device__ __forceinline__ bool frame_nonfinite(const camd_pnp_points& p, const Frame& fr, int lane)
+{
+    int bad = 0;
+    for (int i = lane; i < fr.n; i += 64) {
+        double X[3], uv[2];
+        load_point(p, fr, i, X, uv);
+        bad |= !(isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2]) && isfinite(uv[0]) && isfinite(uv[1]));
+    }
+    return uniform(wave_or(bad) != 0);
+}
+
+// ---- a symmetric positive definite system of N unknowns, lower triangle packed row by row: L[i (i + 1) / 2 + j] ----
+// every index is a constant after unrolling, so the triangle lives in registers
+template <int N>
+__device__ __forceinline__ bool cholesky(double* L, double& min_pivot)
+{
+    bool ok = true;
+    min_pivot = INFINITY;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double d = L[j * (j + 1) / 2 + j];
+#pragma unroll
+        for (int q = 0; q < j; q++) d -= L[j * (j + 1) / 2 + q] * L[j * (j + 1) / 2 + q];
+        min_pivot = d < min_pivot ? d : min_pivot;
+        ok = ok && d > 0. && isfinite(d);
+        const double r = sqrt(d), ir = __ddiv_rn(1., r);
+        L[j * (j + 1) / 2 + j] = r;
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double s = L[i * (i + 1) / 2 + j];
+#pragma unroll
+            for (int q = 0; q < j; q++) s -= L[i * (i + 1) / 2 + q] * L[j * (j + 1) / 2 + q];
+            L[i * (i + 1) / 2 + j] = s * ir;
+        }
+    }
+    return ok;
+}
+template <int N>
+__device__ __forceinline__ void cholesky_solve(const double* L, double* x)  // x: the right-hand side in, the solution out
+{
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        double s = x[i];
+#pragma unroll
+        for (int q = 0; q < i; q++) s -= L[i * (i + 1) / 2 + q] * x[q];
+        x[i] = __ddiv_rn(s, L[i * (i + 1) / 2 + i]);
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; i--) {
+        double s = x[i];
+#pragma unroll
+        for (int q = i + 1; q < N; q++) s -= L[q * (q + 1) / 2 + i] * x[q];
+        x[i] = __ddiv_rn(s, L[i * (i + 1) / 2 + i]);
+    }
+}
+
+// ---- refinement -------------------------------------------------------------------------------------------------
+struct Normal {
+    double A[21], g[6], c;  // J^T J (lower triangle packed), J^T r, r^T r
+};
+
+// residual (projected - observed, raw pixels) and its 2x6 Jacobian with respect to R <- exp([w]x) R, t <- t + d at every
+// point of the frame; their sums, reduced over the wave
+__device__ __forceinline__ void normal_equations(const PnpArgs& a, const Frame& fr, int lane, const double* R, const double* t,
+                                                 Normal& S)
+{
+#pragma unroll
+    for (int q = 0; q < 21; q++) S.A[q] = 0.;
+#pragma unroll
+    for (int q = 0; q < 6; q++) S.g[q] = 0.;
+    S.c = 0.;
+    for (int i = lane; i < fr.n; i += 64) {
+        double X[3], uv[2];
+        load_point(a.p, fr, i, X, uv);
+        const double P[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2],
+                             R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
+        const double z = P[2] + t[2];
+        const double iz = z != 0. ? __ddiv_rn(1., z) : 1.;  // (camd_project_points' rule)
+        const double x = (P[0] + t[0]) * iz, y = (P[1] + t[1]) * iz;
+        double xd, yd, d[4];
+        distort_forward(a.k, x, y, xd, yd);
+        distort_forward_jacobian(a.k, x, y, d);
+        const double r[2] = {xd * a.cam.fx + a.cam.cx - uv[0], yd * a.cam.fy + a.cam.cy - uv[1]};
+        double J[2][6];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const double f = e ? a.cam.fy : a.cam.fx, dx = d[2 * e] * f, dy = d[2 * e + 1] * f;
+            const double g[3] = {dx * iz, dy * iz, -(dx * x + dy * y) * iz};  // d pixel / d camera point
+            J[e][0] = P[1] * g[2] - P[2] * g[1];                            // (R X) x g
+            J[e][1] = P[2] * g[0] - P[0] * g[2];
+            J[e][2] = P[0] * g[1] - P[1] * g[0];
+            J[e][3] = g[0], J[e][4] = g[1], J[e][5] = g[2];
+        }
+#pragma unroll
+        for (int p = 0; p < 6; p++) {
+#pragma unroll
+            for (int q = 0; q <= p; q++) S.A[p * (p + 1) / 2 + q] += J[0][p] * J[0][q] + J[1][p] * J[1][q];
+            S.g[p] += J[0][p] * r[0] + J[1][p] * r[1];
+        }
+        S.c += r[0] * r[0] + r[1] * r[1];
+    }
+#pragma unroll
+    for (int q = 0; q < 21; q++) S.A[q] = wave_sum(S.A[q]);
+#pragma unroll
+    for (int q = 0; q < 6; q++) S.g[q] = wave_sum(S.g[q]);
+    S.c = wave_sum(S.c);
+}
+
+// R2 = exp([w]x) R: I + A [w]x + B [w]x^2 with A = sin(th) / th, B = (sin(th / 2) / (th / 2))^2 / 2, no cancellation
+__device__ __forceinline__ void rotate_left(const double w[3], const double* R, double* R2)
+{
+    const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), h = 0.5 * th;
+    const double A = th > 0. ? __ddiv_rn(sin(th), th) : 1., sh = h > 0. ? __ddiv_rn(sin(h), h) : 1., B = 0.5 * sh * sh;
+    const double E[9] = {1 - B * (w[1] * w[1] + w[2] * w[2]), B * w[0] * w[1] - A * w[2], B * w[0] * w[2] + A * w[1],
+                         B * w[0] * w[1] + A * w[2], 1 - B * (w[0] * w[0] + w[2] * w[2]), B * w[1] * w[2] - A * w[0],
+                         B * w[0] * w[2] - A * w[1], B * w[1] * w[2] + A * w[0], 1 - B * (w[0] * w[0] + w[1] * w[1])};
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) R2[3 * i + j] = E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j] + E[3 * i + 2] * R[6 + j];
+}
+
+__device__ __forceinline__ void store_frame(int lane, int f, const double* R, const double* t, double rms, int iterations,
+                                            int status, double* pose, double* rms_out, int* iterations_out, int* status_out)
+{
+    if (lane != 0) return;
+    for (int q = 0; q < 12; q++) pose[(size_t)f * 12 + q] = status == PNP_OK ? (q < 9 ? R[q] : t[q - 9]) : NAN;
+    rms_out[f] = status == PNP_OK ? rms : NAN;
+    iterations_out[f] = iterations;
+    status_out[f] = status;
+}
+
+__global__ __launch_bounds__(256) void k_pnp_refine(PnpArgs a, const double* __restrict__ pose0, int pose0_stride,
+                                                    double* __restrict__ pose, double* __restrict__ rms_out,
+                                                    int* __restrict__ iterations_out, int* __restrict__ status_out)
+{
+    const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= a.p.frames) return;  // (the whole wave; there is no barrier to miss)
+    double R[9], t[3];
+    const Frame fr = frame_rows(a.p, f, a.min_points);
+    int status = fr.status;
+    if (status == PNP_OK && frame_nonfinite(a.p, fr, lane)) status = PNP_NONFINITE;
+    if (status == PNP_OK) {
+        bool finite = true;
+        for (int q = 0; q < 12; q++) {
+            const double v = pose0[(size_t)f * pose0_stride + q];
+            finite = finite && isfinite(v);
+            if (q < 9) R[q] = v; else t[q - 9] = v;
+        }
+        if (!uniform(finite)) status = PNP_SINGULAR;  // no start pose could be made (camd_pnp_init on a degenerate frame)
+    }
+    if (status != PNP_OK) {
+        store_frame(lane, f, R, t, 0., 0, status, pose, rms_out, iterations_out, status_out);
+        return;
+    }
+    const double eps = 0x1p-52;
+    Normal S, S2;
+    normal_equations(a, fr, lane, R, t, S);
+    double lambda = 1e-3;
+    int it = 0;
+    bool stopped = false;
+    while (uniform(it < PNP_MAX_ITERATIONS && !stopped)) {
+        it++;
+        double L[21], d[6], pivot;
+#pragma unroll
+        for (int q = 0; q < 21; q++) L[q] = S.A[q];
+#pragma unroll
+        for (int q = 0; q < 6; q++) L[q * (q + 1) / 2 + q] += lambda * S.A[q * (q + 1) / 2 + q], d[q] = -S.g[q];
+        bool better = false, small = false;
+        if (uniform(cholesky<6>(L, pivot))) {
+            cholesky_solve<6>(L, d);
+            double R2[9], t2[3] = {t[0] + d[3], t[1] + d[4], t[2] + d[5]};
+            rotate_left(d, R, R2);
+            normal_equations(a, fr, lane, R2, t2, S2);
+            const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
+            const double norm = sqrt(3. + t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);  // |p|: R's Frobenius norm and t
+            small = step < eps * (norm + eps);
+            better = S2.c < S.c;
+            if (uniform(better)) {
+#pragma unroll
+                for (int q = 0; q < 9; q++) R[q] = R2[q];
+#pragma unroll
+                for (int q = 0; q < 3; q++) t[q] = t2[q];
+                S = S2;
+            }
+        }
+        lambda = uniform(better) ? lambda * 0.1 : lambda * 10.;
+        stopped = uniform(small || lambda < 1e-12 || lambda > 1e12);
+    }
+    // a pose is one only where the undamped system has full rank: J^T J scaled to a unit diagonal, then its pivots
+    {
+        double L[21], s[6], pivot;
+#pragma unroll
+        for (int q = 0; q < 6; q++) s[q] = __ddiv_rn(1., sqrt(S.A[q * (q + 1) / 2 + q]));
+#pragma unroll
+        for (int p = 0; p < 6; p++)
+#pragma unroll
+            for (int q = 0; q <= p; q++) L[p * (p + 1) / 2 + q] = S.A[p * (p + 1) / 2 + q] * s[p] * s[q];
+        const bool ok = cholesky<6>(L, pivot);
+        if (!uniform(ok && pivot >= PNP_SINGULAR_PIVOT && isfinite(S.c) && stopped)) status = PNP_SINGULAR;
+    }
+    store_frame(lane, f, R, t, sqrt(__ddiv_rn(S.c, 2. * fr.n)), it, status, pose, rms_out, iterations_out, status_out);
+}
+
+// ---- start pose -------------------------------------------------------------------------------------------------
+// The null vector of the N x N normal matrix M of a direct linear transform (lower triangle packed): inverse iteration on
+// M + mu I, a fixed number of rounds -- a start for the refinement needs no more
+template <int N>
+__device__ __forceinline__ bool null_vector(double* M, double* v)
+{
+    double trace = 0.;
+#pragma unroll
+    for (int q = 0; q < N; q++) trace += M[q * (q + 1) / 2 + q];
+    const double mu = 1e-13 * trace;
+#pragma unroll
+    for (int q = 0; q < N; q++) M[q * (q + 1) / 2 + q] += mu, v[q] = 1. + 0.25 * q;
+    double pivot;
+    bool ok = cholesky<N>(M, pivot);
+#pragma unroll 1
+    for (int round = 0; round < 6; round++) {
+        cholesky_solve<N>(M, v);
+        double s = 0.;
+#pragma unroll
+        for (int q = 0; q < N; q++) s += v[q] * v[q];
+        s = __ddiv_rn(1., sqrt(s));
+#pragma unroll
+        for (int q = 0; q < N; q++) v[q] *= s;
+    }
+#pragma unroll
+    for (int q = 0; q < N; q++) ok = ok && isfinite(v[q]);
+    return ok;
+}
+
+// C = 3: the homography of a plane (object x, y -> normalised image), C = 4: the projection matrix (x, y, z -> image).
+// Hartley-normalised on both sides; G (3 x C, row-major) comes back in the units of the caller.
+template <int C>
+__device__ __forceinline__ bool direct_linear_transform(const PnpArgs& a, const Frame& fr, int lane, double* G, double* centre)
+{
+    constexpr int N = 3 * C, D = C - 1;
+    // the object points in the plane's frame (planar) and the undistorted, normalised image points: means, then scales
+    auto point = [&](int i, double* X, double* xy) {
+        double W[3], uv[2];
+        load_point(a.p, fr, i, W, uv);
+        for (int q = 0; q < 3; q++) X[q] = a.plane[3 * q] * W[0] + a.plane[3 * q + 1] * W[1] + a.plane[3 * q + 2] * W[2];
+        undistort_iterate(a.k, (uv[0] - a.cam.cx) * a.cam.ifx, (uv[1] - a.cam.cy) * a.cam.ify, PNP_UNDISTORT_ITERS, xy[0], xy[1]);
+    };
+    double m[5] = {0., 0., 0., 0., 0.};
+    for (int i = lane; i < fr.n; i += 64) {
+        double X[3], xy[2];
+        point(i, X, xy);
+        m[0] += X[0], m[1] += X[1], m[2] += X[2], m[3] += xy[0], m[4] += xy[1];
+    }
+    const double in = __ddiv_rn(1., (double)fr.n);
+#pragma unroll
+    for (int q = 0; q < 5; q++) m[q] = wave_sum(m[q]) * in;
+    centre[0] = m[0], centre[1] = m[1], centre[2] = m[2];
+    double so = 0., si = 0.;
+    for (int i = lane; i < fr.n; i += 64) {
+        double X[3], xy[2];
+        point(i, X, xy);
+        double dd = 0.;
+        for (int q = 0; q < D; q++) dd += (X[q] - m[q]) * (X[q] - m[q]);
+        so += sqrt(dd);
+        si += sqrt((xy[0] - m[3]) * (xy[0] - m[3]) + (xy[1] - m[4]) * (xy[1] - m[4]));
+    }
+    so = __ddiv_rn(sqrt((double)D), wave_sum(so) * in), si = __ddiv_rn(sqrt(2.), wave_sum(si) * in);  // mean distance sqrt(D), sqrt(2)
+    double M[N * (N + 1) / 2];
+#pragma unroll
+    for (int q = 0; q < N * (N + 1) / 2; q++) M[q] = 0.;
+    for (int i = lane; i < fr.n; i += 64) {
+        double X[3], xy[2], h[C], r[2][N];
+        point(i, X, xy);
+#pragma unroll
+        for (int q = 0; q < D; q++) h[q] = (X[q] - m[q]) * so;
+        h[D] = 1.;
+        const double x = (xy[0] - m[3]) * si, y = (xy[1] - m[4]) * si;
+#pragma unroll
+        for (int q = 0; q < C; q++) {
+            r[0][q] = h[q], r[0][C + q] = 0., r[0][2 * C + q] = -x * h[q];
+            r[1][q] = 0., r[1][C + q] = h[q], r[1][2 * C + q] = -y * h[q];
+        }
+#pragma unroll
+        for (int p = 0; p < N; p++)
+#pragma unroll
+            for (int q = 0; q <= p; q++) M[p * (p + 1) / 2 + q] += r[0][p] * r[0][q] + r[1][p] * r[1][q];
+    }
+#pragma unroll
+    for (int q = 0; q < N * (N + 1) / 2; q++) M[q] = wave_sum(M[q]);
+    double v[N];
+    const bool ok = null_vector<N>(M, v);
+    // G = Ti^-1 Gn To: To = [so I, -so mean; 0 1], Ti^-1 = [1 / si, 0, mx; 0, 1 / si, my; 0, 0, 1]
+    const double isi = __ddiv_rn(1., si);
+#pragma unroll
+    for (int row = 0; row < 3; row++) {
+        double last = v[row * C + D];
+#pragma unroll
+        for (int q = 0; q < D; q++) last -= so * m[q] * v[row * C + q], G[row * C + q] = so * v[row * C + q];
+        G[row * C + D] = last;
+    }
+#pragma unroll
+    for (int q = 0; q < C; q++) {
+        G[q] = G[q] * isi + m[3] * G[2 * C + q];
+        G[C + q] = G[C + q] * isi + m[4] * G[2 * C + q];
+    }
+    return ok;
+}
+
+__device__ __forceinline__ void normalise3(double* v)
+{
+    const double s = __ddiv_rn(1., sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+    v[0] *= s, v[1] *= s, v[2] *= s;
+}
+
+// H or P -> R, t of the target in the camera: scale, the sign that puts the target in front, Gram-Schmidt; poses come
+// back in the caller's object frame (planar: through the plane's rotation)
+__global__ __launch_bounds__(256) void k_pnp_init(PnpArgs a, double* __restrict__ pose)
+{
+    const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= a.p.frames) return;
+    const Frame fr = frame_rows(a.p, f, a.min_points);
+    bool ok = fr.status == PNP_OK && !frame_nonfinite(a.p, fr, lane);
+    double R[9], t[3];
+    if (uniform(ok)) {
+        if (a.planar) {
+            double H[9], c[3];
+            ok = direct_linear_transform<3>(a, fr, lane, H, c);
+            const double z0 = c[2];
+            double c1[3] = {H[0], H[3], H[6]}, c2[3] = {H[1], H[4], H[7]};
+            const double n1 = sqrt(c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2]);
+            const double n2 = sqrt(c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]);
+            double s = __ddiv_rn(2., n1 + n2);
+            if (H[6] * c[0] + H[7] * c[1] + H[8] < 0.) s = -s;  // the depth of the points' centre decides the sign
+            for (int q = 0; q < 3; q++) c1[q] *= s, c2[q] *= s;
+            normalise3(c1);
+            const double dot = c1[0] * c2[0] + c1[1] * c2[1] + c1[2] * c2[2];
+            for (int q = 0; q < 3; q++) c2[q] -= dot * c1[q];
+            normalise3(c2);
+            const double c3[3] = {c1[1] * c2[2] - c1[2] * c2[1], c1[2] * c2[0] - c1[0] * c2[2], c1[0] * c2[1] - c1[1] * c2[0]};
+            // R' = [c1 c2 c3] takes the plane's frame to the camera; t' = s h3 - c3 z0; R = R' plane
+            for (int i = 0; i < 3; i++) {
+                for (int j = 0; j < 3; j++) R[3 * i + j] = c1[i] * a.plane[j] + c2[i] * a.plane[3 + j] + c3[i] * a.plane[6 + j];
+                t[i] = s * H[3 * i + 2] - c3[i] * z0;
+            }
+        } else {
+            double P[12], c[3];
+            ok = direct_linear_transform<4>(a, fr, lane, P, c);
+            double r3[3] = {P[8], P[9], P[10]}, r1[3] = {P[0], P[1], P[2]};
+            double s = __ddiv_rn(1., sqrt(r3[0] * r3[0] + r3[1] * r3[1] + r3[2] * r3[2]));
+            if (P[8] * c[0] + P[9] * c[1] + P[10] * c[2] + P[11] < 0.) s = -s;  // the depth of the points' centre decides the sign
+            for (int q = 0; q < 3; q++) r3[q] *= s, r1[q] *= s;
+            normalise3(r3);
+            const double dot = r1[0] * r3[0] + r1[1] * r3[1] + r1[2] * r3[2];
+            for (int q = 0; q < 3; q++) r1[q] -= dot * r3[q];
+            normalise3(r1);
+            const double r2[3] = {r3[1] * r1[2] - r3[2] * r1[1], r3[2] * r1[0] - r3[0] * r1[2], r3[0] * r1[1] - r3[1] * r1[0]};
+            for (int q = 0; q < 3; q++) R[q] = r1[q], R[3 + q] = r2[q], R[6 + q] = r3[q], t[q] = s * P[4 * q + 3];
+        }
+    }
+    if (lane == 0)
+        for (int q = 0; q < 12; q++) pose[(size_t)f * 12 + q] = ok ? (q < 9 ? R[q] : t[q - 9]) : NAN;
+}
+
+static int pnp_args(const char* who, const camd_pnp_points* p, const double K[9], const double* dist, int ndist, PnpArgs& a)
+{
+    const bool bad_dist = (ndist != 0 && ndist != 4 && ndist != 5 && ndist != 8 && ndist != 12 && ndist != 14) || (ndist > 0 && !dist);
+    if (!p || !K || bad_dist || p->frames < 0 || !float_type_ok(p->object_type) || !float_type_ok(p->image_type) ||
+        p->object_stride < 3 || p->image_stride < 2 ||
+        (p->frames > 0 && (!p->object || !p->image || !p->start || (uintptr_t)p->start % 8 != 0 ||
+                           (uintptr_t)p->object % (p->object_type == CAMD_VALUE_F64 ? 8 : 4) != 0 ||
+                           (uintptr_t)p->image % (p->image_type == CAMD_VALUE_F64 ? 8 : 4) != 0))) {
+        set_error("%s: bad arguments (points: object / image rows of CAMD_VALUE_F64 or _F32, aligned to an element, strides >= 3 "
+                  "/ >= 2; start: frames + 1 device int64; K is 9 host doubles; ndist is 0, 4, 5, 8, 12 or 14, got %d)", who, ndist);
+        return CAMD_ERR_BAD_ARG;
+    }
+    a.p = *p;
+    return unpack_camera(who, K, dist, ndist, &a.cam, &a.k);
+}
+
+}  // namespace camd
+
+using namespace camd;
+
+extern "C" {
+
+int camd_pnp_init(const camd_pnp_points* points, const double K[9], const double* dist, int ndist, int planar,
+                  const double plane[9], double* pose, void* queue)
+{
+    PnpArgs a = {};
+    int rc = pnp_args("camd_pnp_init", points, K, dist, ndist, a);
+    if (rc != CAMD_OK) return rc;
+    if ((planar && !plane) || (a.p.frames > 0 && (!pose || (uintptr_t)pose % 8 != 0))) {
+        set_error("camd_pnp_init: bad arguments (a planar target needs its plane's rotation, 9 host doubles; pose: frames x 12 "
+                  "device doubles)");
+        return CAMD_ERR_BAD_ARG;
+    }
+    a.planar = planar != 0, a.min_points = planar ? 4 : 6;
+    for (int q = 0; q < 9; q++) a.plane[q] = planar ? plane[q] : (q % 4 == 0 ? 1. : 0.);
+    if (a.p.frames == 0) return CAMD_OK;
+    CAMD_NEED_DEVICE();
+    hipLaunchKernelGGL(k_pnp_init, dim3(div_up(a.p.frames, 4)), dim3(256), 0, (hipStream_t)queue, a, pose);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+int camd_pnp_refine(const camd_pnp_points* points, const double K[9], const double* dist, int ndist, int min_points,
+                    const double* pose0, int pose0_stride, double* pose, double* rms, int* iterations, int* status, void* queue)
+{
+    PnpArgs a = {};
+    int rc = pnp_args("camd_pnp_refine", points, K, dist, ndist, a);
+    if (rc != CAMD_OK) return rc;
+    if (min_points < 3 || (pose0_stride != 0 && pose0_stride != 12) ||
+        (a.p.frames > 0 && (!pose0 || !pose || !rms || !iterations || !status || (uintptr_t)pose0 % 8 != 0 ||
+                            (uintptr_t)pose % 8 != 0 || (uintptr_t)rms % 8 != 0 || (uintptr_t)iterations % 4 != 0 ||
+                            (uintptr_t)status % 4 != 0))) {
+        set_error("camd_pnp_refine: bad arguments (min_points >= 3, got %d; pose0_stride is 12, or 0 for one start pose, got %d; "
+                  "pose0, pose, rms, iterations, status: device arrays)", min_points, pose0_stride);
+        return CAMD_ERR_BAD_ARG;
+    }
+    a.min_points = min_points;
+    if (a.p.frames == 0) return CAMD_OK;
+    CAMD_NEED_DEVICE();
+    hipLaunchKernelGGL(k_pnp_refine, dim3(div_up(a.p.frames, 4)), dim3(256), 0, (hipStream_t)queue, a, pose0, pose0_stride, pose,
+                       rms, iterations, status);
+    CAMD_LAUNCH_CHECK();
+    return CAMD_OK;
+}
+
+}  // extern "C"

@@ -57,21 +57,7 @@ __global__ __launch_bounds__(256) void k_undistort_points(PointsArgs a, const TI
     const Lens& k = a.k;
     const double xs = (u - a.cam.cx) * a.cam.ifx, ys = (v - a.cam.cy) * a.cam.ify;
     double x = xs, y = ys;
-    if (a.ndist) {
-        // the trip count is the same for every lane: a lane that met icdist < 0 keeps its start value through selects
-        bool done = false;
-        for (int j = 0; j < a.iters; j++) {
-            const double r2 = x * x + y * y;
-            const double icdist = __ddiv_rn(1 + ((k.k6 * r2 + k.k5) * r2 + k.k4) * r2, 1 + ((k.k3 * r2 + k.k2) * r2 + k.k1) * r2);
-            const double dX = 2 * k.p1 * x * y + k.p2 * (r2 + 2 * x * x) + k.s1 * r2 + k.s2 * r2 * r2;
-            const double dY = k.p1 * (r2 + 2 * y * y) + 2 * k.p2 * x * y + k.s3 * r2 + k.s4 * r2 * r2;
-            const bool neg = icdist < 0;
-            const double xn = neg ? xs : (xs - dX) * icdist, yn = neg ? ys : (ys - dY) * icdist;
-            x = done ? x : xn;
-            y = done ? y : yn;
-            done = done || neg;
-        }
-    }
+    if (a.ndist) undistort_iterate(k, xs, ys, a.iters, x, y);
     x = (double)(TI)x, y = (double)(TI)y;
     if (a.pixels) x = x * a.cam.fx + a.cam.cx, y = y * a.cam.fy + a.cam.cy;
     store_pair<TO>(out + i * 2, x, y);

@@ -7,6 +7,8 @@ Restates the helpers ``Stereo`` needs once per rig:
       called at stereo_camera.py:159-165 and utils.py:184-191.
 These run once per calibration; per-pair work is on the GPU.
 """
+import functools
+
 import numpy as np
 
 eps = 1e-8
@@ -151,6 +153,27 @@ def T_to_r_t(T):
     T = np.asarray(T, np.float64)
     tvec = T[:3, 3:4] if T.shape[1] > 3 else np.zeros((3, 1))
     return rodrigues(T[:3, :3]), tvec
+
+
+def mean_Ts(Ts):
+    """One pose for many (the arithmetic of the reference's utils.py:418-432), host, float64.  Every rotation is taken
+    relative to the first one; the relative rotations are multiplied up, each later one from the LEFT of the product so
+    far; the product's Rodrigues vector, divided by the number of poses, is applied to the first rotation.  The
+    translation is the plain mean.  ``R_t_to_T`` rounds the rotation through float32."""
+    poses = np.array(Ts)
+    first = poses[0, :3, :3]
+    relative = [first.T @ pose[:3, :3] for pose in poses]
+    product = functools.reduce(lambda so_far, later: later @ so_far, relative)
+    mean_rotation = first @ rodrigues(rodrigues(product) / len(poses))
+    return R_t_to_T(mean_rotation, poses.mean(axis=0)[:3, 3])
+
+
+def join_points(points):
+    """The rows of an id -> points mapping stacked in the order of the sorted ids (what the reference hands to cv2,
+    utils.py:132-136); an array passes through untouched."""
+    if not isinstance(points, dict):
+        return points
+    return np.concatenate([points[key] for key in sorted(points)], axis=0)
 
 
 # ---- rig-level pure functions (what Stereo's methods of the reference's names are thin wrappers of) -------------

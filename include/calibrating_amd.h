@@ -567,6 +567,42 @@ int camd_undistort_points(const void* uv, int uv_type, size_t n, int uv_stride, 
 int camd_project_points(const void* xyz, int xyz_type, size_t n, int xyz_stride, const double R[9], const double t[3],
                         const double K[9], const double* dist, int ndist, void* out, void* stream);
 
+/* ---- the pose of a target from its detected points, every frame of a recording in one launch (csrc/pnp.hip) ----
+ * replaces cv2.solvePnPGeneric(object_points, image_points[:, None], K, D) of Cam.perspective_n_point (camera.py:266-273):
+ * UNPINNED against cv2.  One wavefront per frame, four frames per workgroup, no workgroup
+ * barrier; a frame's outputs depend on its own rows only, so they are the same bits alone and at any place of a batch.
+ *
+ * The points: frame f owns rows start[f] .. start[f + 1] of `image` ([u, v], raw distorted pixels) and of `object`
+ * ([x, y, z]); with object_shared the object rows are one block shared by every frame (one board), frame f reading its
+ * first start[f + 1] - start[f] rows.  Rows are read in place, `*_stride` elements of `*_type` CAMD_VALUE_F64 /
+ * CAMD_VALUE_F32 apart.  start: frames + 1 int64 ON THE DEVICE; a range outside image_rows / object_rows is not read (status
+ * 2).  K, dist, ndist as in camd_project_points.  queue: the HIP stream the launch is queued on.             */
+typedef struct camd_pnp_points {
+    const void* object;
+    const void* image;
+    const long long* start;
+    unsigned long long object_rows, image_rows;
+    int object_type, image_type, object_stride, image_stride, object_shared, frames;
+} camd_pnp_points;
+/* A start pose per frame -> pose[f] = R (9, row-major), t (3): the normal matrix of the direct linear transform on
+ * Hartley-normalised points (image points undistorted by camd_undistort_points' iteration, 10 rounds), reduced over the
+ * wave; its null vector by inverse iteration; scale, sign (target in front) and Gram-Schmidt.  planar != 0: the 9 x 9
+ * matrix of the homography, on the object points turned by `plane` (9 host doubles: the rotation that lays the target's
+ * plane on z = const), >= 4 points; planar == 0: the 12 x 12 matrix of the projection matrix, >= 6 points.  A frame
+ * that cannot be started (too few points, a non-finite coordinate, no null vector) gets NaN.                        */
+int camd_pnp_init(const camd_pnp_points* points, const double K[9], const double* dist, int ndist, int planar,
+                  const double plane[9], double* pose, void* queue);
+/* Levenberg-Marquardt in float64 from pose0[f * pose0_stride] (pose0_stride 12, or 0: one start for all frames): the
+ * residual is camd_project_points' pixel minus the observed one, the step a local perturbation R <- exp([w]x) R,
+ * t <- t + d; (J^T J + lambda diag(J^T J)) delta = -J^T r by Cholesky, lambda = 1e-3 at the start, / 10 after a step
+ * that lowers the cost, * 10 after one that does not.  It stops when |delta| < eps (|p| + eps), eps = 2^-52, |p|^2 =
+ * 3 + |t|^2; when lambda leaves [1e-12, 1e12]; or after 100 evaluations.  Per frame: pose (as above), rms = sqrt(cost /
+ * 2n), iterations (evaluations after the first), status: 0 ok, 1 fewer than min_points (>= 3) points, 2 a non-finite
+ * coordinate, 3 singular (a pivot of the unit-diagonal J^T J below 1e-10, no finite start) or not stopped at the cap.
+ * status != 0: pose and rms are NaN.  pose must not overlap pose0.                                                   */
+int camd_pnp_refine(const camd_pnp_points* points, const double K[9], const double* dist, int ndist, int min_points,
+                    const double* pose0, int pose0_stride, double* pose, double* rms, int* iterations, int* status, void* queue);
+
 #ifdef __cplusplus
 }
 #endif
