@@ -42,6 +42,10 @@ VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_ar
 VALUE_U16 = 3  # a uint16 depth in millimetres: camd_vis_depth only
 NEAREST_MAX_RADIUS = 32  # CAMD_NEAREST_MAX_RADIUS
 POINTS_PIXELS = 0x100  # CAMD_POINTS_PIXELS, or-ed into camd_undistort_points' out_type
+# camd_calib_*: the sizes and the places of the state (CAMD_CALIB_*)
+CALIB_STATE_DOUBLES, CALIB_WORKSPACE_DOUBLES, CALIB_CANDIDATE_DOUBLES = 40, 136, 16
+(CALIB_DONE, CALIB_ACCEPT, CALIB_LAMBDA, CALIB_COST, CALIB_EVALUATIONS, CALIB_ITERATIONS, CALIB_STATUS, CALIB_CONVERGED, CALIB_K,
+ CALIB_DK, CALIB_MASK, CALIB_SOLVED, CALIB_PIVOT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 17, 26, 35, 36
 
 
 class SgbmParams(ctypes.Structure):
@@ -194,6 +198,11 @@ SIGNATURES = {
     "camd_pnp_init": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "camd_pnp_refine": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "camd_calib_homography": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_void_p, c_void_p]),
+    "camd_calib_linearise": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_calib_step": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_calib_finish": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_calib_read": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

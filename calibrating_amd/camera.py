@@ -3,8 +3,9 @@
 Only the record format of the reference's ``Cam`` is mirrored (``Cam.load`` / ``Cam.dump``,
 /root/reference/calibrating/camera.py:407-448): a YAML / dict record with either ``K`` (3x3) or
 ``fx, fy, cx, cy``, optional ``D`` (default five zeros), ``xy`` = (width, height) (required), and the
-free-form keys ``name``, ``T_in_main_cam``, ``retval``.  Intrinsic calibration itself
-(cv2.calibrateCamera, boards, caches) is outside the stereo-depth hot path.
+free-form keys ``name``, ``T_in_main_cam``, ``retval``.  Intrinsic calibration itself runs on the GPU from detected
+points: ``Cam.from_detections(frames, xy).calibrate()`` (camera.py:63-93: cv2.calibrateCamera; csrc/calibrate.hip).
+Detecting a board, caches and feature pictures stay with the caller.
 Two point methods of the reference's ``Cam`` run on the GPU: ``undistort_points`` and ``project_points``
 (camera.py:275-287; csrc/points.hip), the step between a matcher's raw pixels and the epipolar path.  So do its two
 alignment pictures, ``vis_depth_alignment`` and ``vis_reproject_img_alignment`` (camera.py:311-342; csrc/vis.hip), and the
@@ -68,6 +69,45 @@ class Cam(dict):
     @classmethod
     def init_by_K_D(cls, K, D=None, xy=None, name=None):
         return cls(K, D, xy, name)
+
+    @classmethod
+    def from_detections(cls, frames, xy, name=None, undistorted=False, calibrate_flags=0):
+        """A camera that holds detections and no intrinsics yet: ``frames`` maps key -> ``dict(image_points=...,
+        object_points=...)``, arrays or the reference's id -> array dicts (joined by ``geometry.join_points``).
+        ``undistorted`` and ``calibrate_flags`` are the reference's constructor arguments (camera.py:32-43); ``calibrate()``
+        makes K and D from them."""
+        cam = cls()
+        cam.xy, cam.name, cam.undistorted, cam.calibrate_flags = tuple(xy), name, bool(undistorted), int(calibrate_flags)
+        for key, frame in frames.items():
+            cam[key] = dict(frame)
+        return cam
+
+    def calibrate(self):
+        """``cv2.calibrateCamera`` over every valid frame that holds object points (camera.py:63-93), on the GPU
+        (``calibrate.calibrate_camera``): sets ``K``, ``D``, ``retval`` and, for every such key, ``self[key]["T"]`` and
+        ``["reprojection_error"]``.  ``undistorted`` selects the reference's flag set (no lens: tangential and radial
+        coefficients fixed at 0).  A frame left out of the joint problem gets no pose (and loses an earlier one).  A camera
+        that cannot be calibrated raises ``ValueError`` and keeps what it had.  Returns ``self``."""
+        from . import calibrate, geometry
+        keys = sorted(k for k in self.valid_keys if "object_points" in self[k])
+        if not keys:
+            raise ValueError("No any valid image!")
+        uvs = [np.asarray(geometry.join_points(self[k]["image_points"])).reshape(-1, 2) for k in keys]
+        xyzs = [np.asarray(geometry.join_points(self[k]["object_points"])).reshape(-1, 3) for k in keys]
+        for k, a, b in zip(keys, uvs, xyzs):
+            if len(a) != len(b):
+                raise ValueError("%r: %d image points and %d object points" % (k, len(a), len(b)))
+        flags = calibrate.UNDISTORTED_FLAGS if getattr(self, "undistorted", False) else getattr(self, "calibrate_flags", 0)
+        res = calibrate.calibrate_camera(np.concatenate(xyzs), np.concatenate(uvs), self.xy, counts=[len(a) for a in uvs], flags=flags)
+        self.retval, self.K, self.D = res["retval"], res["K"], res["D"]
+        for i, k in enumerate(keys):
+            d = self[k]
+            if res["status"][i] == 0:
+                d["T"], d["reprojection_error"] = res["T"][i], float(res["reprojection_error"][i])
+            else:
+                d.pop("T", None)
+                d.pop("reprojection_error", None)
+        return self
 
     def load(self, path_or_str_or_dict=None):
         """``Cam.load(record)`` (called on the class: builds a new Cam) or ``cam.load(record)`` (in place)."""

@@ -11,131 +11,9 @@
 //
 // cv2's own solver is UNPINNED: this is a float64 Levenberg-Marquardt on raw, distorted
 // pixels run to float64 convergence; cv2 stops after 20 iterations at FLT_EPSILON.
-#include <climits>
-
-#include "camera_model.hpp"
+#include "pnp_common.hpp"
 
 namespace camd {
-
-enum { PNP_OK = 0, PNP_FEW = 1, PNP_NONFINITE = 2, PNP_SINGULAR = 3 };
-constexpr int PNP_MAX_ITERATIONS = 100;
-constexpr int PNP_UNDISTORT_ITERS = 10;  // rounds of cv2.undistortPoints' iteration for the start pose (cv2 runs 5)
-constexpr double PNP_SINGULAR_PIVOT = 1e-10;  // smallest pivot of the unit-diagonal normal matrix that still counts as a pose
-
-struct PnpArgs {
-    Pinhole cam;
-    Lens k;
-    camd_pnp_points p;
-    double plane[9];  // camd_pnp_init, planar: the rotation that lays the target's plane on z = const
-    int planar, min_points;
-};
-
-// sum over the wave, the same bits in every lane: lane i adds lane i ^ m, and a + b == b + a
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_or(int v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v |= __shfl_xor(v, m, 64);
-    return v;
-}
-// a flag every lane agrees on, as a scalar: the branches on it are uniform and the wave stays whole for the butterflies
-__device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
-
-__device__ __forceinline__ double load_value(const void* p, int type, size_t i)
-{
-    return with_float(type, [&](auto v) { return (double)((const decltype(v)*)p)[i]; });
-}
-
-// the rows of one frame, checked: [s, s + n) of the image rows, the same of the object rows or [0, n) of a shared block
-struct Frame {
-    size_t uv0, obj0;
-    int n, status;
-};
-
-__device__ __forceinline__ Frame frame_rows(const camd_pnp_points& p, int f, int min_points)
-{
-    Frame fr = {0, 0, 0, PNP_OK};
-    const long long s = p.start[f], e = p.start[f + 1];
-    const unsigned long long obj_rows = p.object_rows;
-    if (s < 0 || e < s || (unsigned long long)e > p.image_rows || e - s > INT_MAX ||
-        (unsigned long long)(p.object_shared ? e - s : e) > obj_rows) {
-        fr.status = PNP_NONFINITE;  // a range outside the rows: nothing of it is read
-        return fr;
-    }
-    fr.n = (int)(e - s), fr.uv0 = (size_t)s, fr.obj0 = p.object_shared ? 0 : (size_t)s;
-    if (fr.n < min_points) fr.status = PNP_FEW;
-    return fr;
-}
-
-__device__ __forceinline__ void load_point(const camd_pnp_points& p, const Frame& fr, int i, double X[3], double uv[2])
-{
-    const size_t o = (fr.obj0 + i) * (size_t)p.object_stride, q = (fr.uv0 + i) * (size_t)p.image_stride;
-    X[0] = load_value(p.object, p.object_type, o), X[1] = load_value(p.object, p.object_type, o + 1);
-    X[2] = load_value(p.object, p.object_type, o + 2);
-    uv[0] = load_value(p.image, p.image_type, q), uv[1] = load_value(p.image, p.image_type, q + 1);
-}
-
-// 1 when any coordinate of the frame is NaN or infinite (every lane gets the answer)
-__device__ __forceinline__ bool frame_nonfinite(const camd_pnp_points& p, const Frame& fr, int lane)
-{
-    int bad = 0;
-    for (int i = lane; i < fr.n; i += 64) {
-        double X[3], uv[2];
-        load_point(p, fr, i, X, uv);
-        bad |= !(isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2]) && isfinite(uv[0]) && isfinite(uv[1]));
-    }
-    return uniform(wave_or(bad) != 0);
-}
-
-// ---- a symmetric positive definite system of N unknowns, lower triangle packed row by row: L[i (i + 1) / 2 + j] ----
-// every index is a constant after unrolling, so the triangle lives in registers
-template <int N>
-__device__ __forceinline__ bool cholesky(double* L, double& min_pivot)
-{
-    bool ok = true;
-    min_pivot = INFINITY;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double d = L[j * (j + 1) / 2 + j];
-#pragma unroll
-        for (int q = 0; q < j; q++) d -= L[j * (j + 1) / 2 + q] * L[j * (j + 1) / 2 + q];
-        min_pivot = d < min_pivot ? d : min_pivot;
-        ok = ok && d > 0. && isfinite(d);
-        const double r = sqrt(d), ir = __ddiv_rn(1., r);
-        L[j * (j + 1) / 2 + j] = r;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double s = L[i * (i + 1) / 2 + j];
-#pragma unroll
-            for (int q = 0; q < j; q++) s -= L[i * (i + 1) / 2 + q] * L[j * (j + 1) / 2 + q];
-            L[i * (i + 1) / 2 + j] = s * ir;
-        }
-    }
-    return ok;
-}
-template <int N>
-__device__ __forceinline__ void cholesky_solve(const double* L, double* x)  // x: the right-hand side in, the solution out
-{
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        double s = x[i];
-#pragma unroll
-        for (int q = 0; q < i; q++) s -= L[i * (i + 1) / 2 + q] * x[q];
-        x[i] = __ddiv_rn(s, L[i * (i + 1) / 2 + i]);
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; i--) {
-        double s = x[i];
-#pragma unroll
-        for (int q = i + 1; q < N; q++) s -= L[q * (q + 1) / 2 + i] * x[q];
-        x[i] = __ddiv_rn(s, L[i * (i + 1) / 2 + i]);
-    }
-}
 
 // ---- refinement -------------------------------------------------------------------------------------------------
 struct Normal {
@@ -187,20 +65,6 @@ __device__ __forceinline__ void normal_equations(const PnpArgs& a, const Frame& 
 #pragma unroll
     for (int q = 0; q < 6; q++) S.g[q] = wave_sum(S.g[q]);
     S.c = wave_sum(S.c);
-}
-
-// R2 = exp([w]x) R: I + A [w]x + B [w]x^2 with A = sin(th) / th, B = (sin(th / 2) / (th / 2))^2 / 2, no cancellation
-__device__ __forceinline__ void rotate_left(const double w[3], const double* R, double* R2)
-{
-    const double th = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]), h = 0.5 * th;
-    const double A = th > 0. ? __ddiv_rn(sin(th), th) : 1., sh = h > 0. ? __ddiv_rn(sin(h), h) : 1., B = 0.5 * sh * sh;
-    const double E[9] = {1 - B * (w[1] * w[1] + w[2] * w[2]), B * w[0] * w[1] - A * w[2], B * w[0] * w[2] + A * w[1],
-                         B * w[0] * w[1] + A * w[2], 1 - B * (w[0] * w[0] + w[2] * w[2]), B * w[1] * w[2] - A * w[0],
-                         B * w[0] * w[2] - A * w[1], B * w[1] * w[2] + A * w[0], 1 - B * (w[0] * w[0] + w[1] * w[1])};
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) R2[3 * i + j] = E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j] + E[3 * i + 2] * R[6 + j];
 }
 
 __device__ __forceinline__ void store_frame(int lane, int f, const double* R, const double* t, double rms, int iterations,
@@ -286,108 +150,6 @@ __global__ __launch_bounds__(256) void k_pnp_refine(PnpArgs a, const double* __r
 }
 
 // ---- start pose -------------------------------------------------------------------------------------------------
-// The null vector of the N x N normal matrix M of a direct linear transform (lower triangle packed): inverse iteration on
-// M + mu I, a fixed number of rounds -- a start for the refinement needs no more
-template <int N>
-__device__ __forceinline__ bool null_vector(double* M, double* v)
-{
-    double trace = 0.;
-#pragma unroll
-    for (int q = 0; q < N; q++) trace += M[q * (q + 1) / 2 + q];
-    const double mu = 1e-13 * trace;
-#pragma unroll
-    for (int q = 0; q < N; q++) M[q * (q + 1) / 2 + q] += mu, v[q] = 1. + 0.25 * q;
-    double pivot;
-    bool ok = cholesky<N>(M, pivot);
-#pragma unroll 1
-    for (int round = 0; round < 6; round++) {
-        cholesky_solve<N>(M, v);
-        double s = 0.;
-#pragma unroll
-        for (int q = 0; q < N; q++) s += v[q] * v[q];
-        s = __ddiv_rn(1., sqrt(s));
-#pragma unroll
-        for (int q = 0; q < N; q++) v[q] *= s;
-    }
-#pragma unroll
-    for (int q = 0; q < N; q++) ok = ok && isfinite(v[q]);
-    return ok;
-}
-
-// C = 3: the homography of a plane (object x, y -> normalised image), C = 4: the projection matrix (x, y, z -> image).
-// Hartley-normalised on both sides; G (3 x C, row-major) comes back in the units of the caller.
-template <int C>
-__device__ __forceinline__ bool direct_linear_transform(const PnpArgs& a, const Frame& fr, int lane, double* G, double* centre)
-{
-    constexpr int N = 3 * C, D = C - 1;
-    // the object points in the plane's frame (planar) and the undistorted, normalised image points: means, then scales
-    auto point = [&](int i, double* X, double* xy) {
-        double W[3], uv[2];
-        load_point(a.p, fr, i, W, uv);
-        for (int q = 0; q < 3; q++) X[q] = a.plane[3 * q] * W[0] + a.plane[3 * q + 1] * W[1] + a.plane[3 * q + 2] * W[2];
-        undistort_iterate(a.k, (uv[0] - a.cam.cx) * a.cam.ifx, (uv[1] - a.cam.cy) * a.cam.ify, PNP_UNDISTORT_ITERS, xy[0], xy[1]);
-    };
-    double m[5] = {0., 0., 0., 0., 0.};
-    for (int i = lane; i < fr.n; i += 64) {
-        double X[3], xy[2];
-        point(i, X, xy);
-        m[0] += X[0], m[1] += X[1], m[2] += X[2], m[3] += xy[0], m[4] += xy[1];
-    }
-    const double in = __ddiv_rn(1., (double)fr.n);
-#pragma unroll
-    for (int q = 0; q < 5; q++) m[q] = wave_sum(m[q]) * in;
-    centre[0] = m[0], centre[1] = m[1], centre[2] = m[2];
-    double so = 0., si = 0.;
-    for (int i = lane; i < fr.n; i += 64) {
-        double X[3], xy[2];
-        point(i, X, xy);
-        double dd = 0.;
-        for (int q = 0; q < D; q++) dd += (X[q] - m[q]) * (X[q] - m[q]);
-        so += sqrt(dd);
-        si += sqrt((xy[0] - m[3]) * (xy[0] - m[3]) + (xy[1] - m[4]) * (xy[1] - m[4]));
-    }
-    so = __ddiv_rn(sqrt((double)D), wave_sum(so) * in), si = __ddiv_rn(sqrt(2.), wave_sum(si) * in);  // mean distance sqrt(D), sqrt(2)
-    double M[N * (N + 1) / 2];
-#pragma unroll
-    for (int q = 0; q < N * (N + 1) / 2; q++) M[q] = 0.;
-    for (int i = lane; i < fr.n; i += 64) {
-        double X[3], xy[2], h[C], r[2][N];
-        point(i, X, xy);
-#pragma unroll
-        for (int q = 0; q < D; q++) h[q] = (X[q] - m[q]) * so;
-        h[D] = 1.;
-        const double x = (xy[0] - m[3]) * si, y = (xy[1] - m[4]) * si;
-#pragma unroll
-        for (int q = 0; q < C; q++) {
-            r[0][q] = h[q], r[0][C + q] = 0., r[0][2 * C + q] = -x * h[q];
-            r[1][q] = 0., r[1][C + q] = h[q], r[1][2 * C + q] = -y * h[q];
-        }
-#pragma unroll
-        for (int p = 0; p < N; p++)
-#pragma unroll
-            for (int q = 0; q <= p; q++) M[p * (p + 1) / 2 + q] += r[0][p] * r[0][q] + r[1][p] * r[1][q];
-    }
-#pragma unroll
-    for (int q = 0; q < N * (N + 1) / 2; q++) M[q] = wave_sum(M[q]);
-    double v[N];
-    const bool ok = null_vector<N>(M, v);
-    // G = Ti^-1 Gn To: To = [so I, -so mean; 0 1], Ti^-1 = [1 / si, 0, mx; 0, 1 / si, my; 0, 0, 1]
-    const double isi = __ddiv_rn(1., si);
-#pragma unroll
-    for (int row = 0; row < 3; row++) {
-        double last = v[row * C + D];
-#pragma unroll
-        for (int q = 0; q < D; q++) last -= so * m[q] * v[row * C + q], G[row * C + q] = so * v[row * C + q];
-        G[row * C + D] = last;
-    }
-#pragma unroll
-    for (int q = 0; q < C; q++) {
-        G[q] = G[q] * isi + m[3] * G[2 * C + q];
-        G[C + q] = G[C + q] * isi + m[4] * G[2 * C + q];
-    }
-    return ok;
-}
-
 __device__ __forceinline__ void normalise3(double* v)
 {
     const double s = __ddiv_rn(1., sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));

@@ -42,6 +42,33 @@ def plane_of(object_points):
     return bool(s[2] < PLANAR_RATIO * s[1]), np.ascontiguousarray(Vt)
 
 
+def batch_layout(object_points, image_points, counts):
+    """(frames, lengths (frames,) int64, shared) of the three ways a batch is given: (f, n, .) with per-frame or one shared
+    block of object points, or ragged rows with ``counts``.  Refuses everything else; nothing touches the device."""
+    shared = False
+    if counts is None:
+        if image_points.ndim != 3:
+            raise ValueError("image_points must be (f, n, 2) unless counts is given, got %s" % (tuple(image_points.shape),))
+        frames, n = int(image_points.shape[0]), int(image_points.shape[1])
+        shared = object_points.ndim == 2
+        if tuple(object_points.shape) != ((n, 3) if shared else (frames, n, 3)):
+            raise ValueError("object_points must be (%d, %d, 3) or a shared (%d, 3), got %s" % (frames, n, n, tuple(object_points.shape)))
+        lengths = np.full(frames, n, np.int64)
+    else:
+        lengths = np.asarray(counts)
+        if image_points.ndim != 2 or object_points.ndim != 2:
+            raise ValueError("with counts, the points are ragged rows (N, 2) and (N, 3)")
+        if lengths.ndim != 1 or lengths.dtype.kind not in "iu" or (lengths < 0).any():
+            raise ValueError("counts must be a 1-d array of non-negative integers")
+        lengths = lengths.astype(np.int64)
+        frames = len(lengths)
+        if int(lengths.sum()) != image_points.shape[0] or object_points.shape[0] != image_points.shape[0]:
+            raise ValueError("counts sum to %d rows, the points have %d and %d" % (lengths.sum(), image_points.shape[0], object_points.shape[0]))
+    if frames == 0:
+        raise ValueError("no frames")
+    return frames, lengths, shared
+
+
 def _start_poses(T0, frames):
     T0 = np.asarray(T0, np.float64)
     if T0.shape not in ((4, 4), (frames, 4, 4)):
@@ -78,27 +105,7 @@ def solve_pnp_batch(object_points, image_points, K, D=None, counts=None, T0=None
     if nd == 14 and (Dv[12] != 0 or Dv[13] != 0):
         raise ValueError("tilted-sensor distortion (tauX, tauY) not implemented")
     Kf = K9(K)
-    shared = False
-    if counts is None:
-        if image_points.ndim != 3:
-            raise ValueError("image_points must be (f, n, 2) unless counts is given, got %s" % (tuple(image_points.shape),))
-        frames, n = int(image_points.shape[0]), int(image_points.shape[1])
-        shared = object_points.ndim == 2
-        if tuple(object_points.shape) != ((n, 3) if shared else (frames, n, 3)):
-            raise ValueError("object_points must be (%d, %d, 3) or a shared (%d, 3), got %s" % (frames, n, n, tuple(object_points.shape)))
-        lengths = np.full(frames, n, np.int64)
-    else:
-        lengths = np.asarray(counts)
-        if image_points.ndim != 2 or object_points.ndim != 2:
-            raise ValueError("with counts, the points are ragged rows (N, 2) and (N, 3)")
-        if lengths.ndim != 1 or lengths.dtype.kind not in "iu" or (lengths < 0).any():
-            raise ValueError("counts must be a 1-d array of non-negative integers")
-        lengths = lengths.astype(np.int64)
-        frames = len(lengths)
-        if int(lengths.sum()) != image_points.shape[0] or object_points.shape[0] != image_points.shape[0]:
-            raise ValueError("counts sum to %d rows, the points have %d and %d" % (lengths.sum(), image_points.shape[0], object_points.shape[0]))
-    if frames == 0:
-        raise ValueError("no frames")
+    frames, lengths, shared = batch_layout(object_points, image_points, counts)
     pose0 = None if T0 is None else _start_poses(T0, frames)
     if lengths.max() < 4:
         raise ValueError("every frame has fewer than 4 points")

@@ -603,6 +603,49 @@ int camd_pnp_init(const camd_pnp_points* points, const double K[9], const double
 int camd_pnp_refine(const camd_pnp_points* points, const double K[9], const double* dist, int ndist, int min_points,
                     const double* pose0, int pose0_stride, double* pose, double* rms, int* iterations, int* status, void* queue);
 
+/* ---- a camera's intrinsics and every frame's pose from detected points (csrc/calibrate.hip) ----
+ * replaces cv2.calibrateCamera of Cam.calibrate (camera.py:63-93) for fx fy cx cy | k1 k2 p1 p2 k3: UNPINNED against cv2
+ * (DESIGN.md section 2, U29).  A float64 Levenberg-Marquardt on raw pixels over the nine shared unknowns and six per
+ * frame (camd_pnp_refine's local pose update), solved through the Schur complement on the shared block; damping and
+ * stopping as in camd_pnp_refine, on the joint step; a candidate is accepted when its cost is lower, or higher by at most 64
+ * ulp of the cost (the rounding of the sums).  The points are a camd_pnp_points.  The frames of the joint problem
+ * are `used`: used_n int32 frame indices ON THE DEVICE, rising; per-frame arrays of these calls have one row per USED
+ * frame.  All sums over frames have a fixed order (a stride of 64 over the used frames, then a butterfly): the same
+ * input gives the same bits on every run.
+ *
+ * state: CAMD_CALIB_STATE_DOUBLES device doubles, written by the caller before the first call:
+ *   [CAMD_CALIB_LAMBDA] = 1e-3, [CAMD_CALIB_K .. + 9) = fx fy cx cy k1 k2 p1 p2 k3 of the start,
+ *   [CAMD_CALIB_MASK .. + 9) = 1 for a free entry of the block and 0 for a fixed one, everything else 0.
+ * After camd_calib_step: [CAMD_CALIB_DONE] != 0 when the iteration has ended (stopped by the rule, or 100 evaluations),
+ * [CAMD_CALIB_ACCEPT] != 0 when the step was taken (then the next step needs camd_calib_linearise first).
+ * After camd_calib_finish: [CAMD_CALIB_STATUS] 0 ok / 3 singular (a pivot of the unit-diagonal reduced matrix below 1e-10)
+ * or not converged at the cap, [CAMD_CALIB_COST] the sum of squared residuals, [CAMD_CALIB_K .. + 9) the result.     */
+#define CAMD_CALIB_STATE_DOUBLES 40
+#define CAMD_CALIB_WORKSPACE_DOUBLES 136 /* per used frame: A 21, B 54, C 45, gp 6, gk 9, c 1 */
+#define CAMD_CALIB_CANDIDATE_DOUBLES 16  /* per used frame: R 9, t 3, cost, |step|^2, |pose|^2, unused */
+enum {
+    CAMD_CALIB_DONE = 0, CAMD_CALIB_ACCEPT = 1, CAMD_CALIB_LAMBDA = 2, CAMD_CALIB_COST = 3, CAMD_CALIB_EVALUATIONS = 4,
+    CAMD_CALIB_ITERATIONS = 5, CAMD_CALIB_STATUS = 6, CAMD_CALIB_CONVERGED = 7, CAMD_CALIB_K = 8, CAMD_CALIB_DK = 17,
+    CAMD_CALIB_MASK = 26, CAMD_CALIB_SOLVED = 35, CAMD_CALIB_PIVOT = 36
+};
+/* The start: H[f] = the homography (9, row-major) from the target's plane -- the object points turned by `plane`, 9 host
+ * doubles, their x and y -- to raw pixels, by camd_pnp_init's Hartley-normalised direct linear transform with an identity
+ * camera and no lens; NaN for a frame of fewer than 4 points, with a non-finite coordinate or without a null vector.
+ * H: frames x 9 device doubles.                                                                                    */
+int camd_calib_homography(const camd_pnp_points* points, const double plane[9], double* H, void* queue);
+/* The sums of every used frame at state's K and `poses` (used_n x 12: R, t) -> workspace (used_n x 136).          */
+int camd_calib_linearise(const camd_pnp_points* points, const int* used, int used_n, double* state, double* poses,
+                         double* workspace, void* queue);
+/* One evaluation at state's lambda: the reduced system and the block's step; every frame's step, candidate pose and
+ * cost (candidate: used_n x 16); accept (poses and state's K take the candidate) or reject; lambda; the stop flags.  */
+int camd_calib_step(const camd_pnp_points* points, const int* used, int used_n, double* state, double* poses,
+                    double* candidate, double* workspace, void* queue);
+/* After the last linearisation: the status, the cost, and frame_error[u] = sqrt(sum |r|^2 / n) of every used frame.   */
+int camd_calib_finish(const camd_pnp_points* points, const int* used, int used_n, double* state, double* workspace,
+                      double* frame_error, void* queue);
+/* The first `count` doubles of state -> out (host), after everything queued before; returns when they have arrived.  */
+int camd_calib_read(const double* state, int count, double* out, void* queue);
+
 #ifdef __cplusplus
 }
 #endif
