@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _native, pnp
-from ._arrays import FLOAT_TYPES, dtype_name, is_np, to_caller, to_device
+from ._arrays import to_caller
 
 # cv2's values
 CALIB_USE_INTRINSIC_GUESS = 0x00001
@@ -118,11 +118,7 @@ def calibrate_camera(object_points, image_points, xy, counts=None, flags=0, K=No
     whose reduced matrix is singular, or whose iteration has not stopped at the cap of evaluations, raises ``ValueError``
     with status 3."""
     import torch
-    pnp._rows(object_points, 3, "object_points")
-    pnp._rows(image_points, 2, "image_points")
-    if is_np(object_points) != is_np(image_points):
-        raise TypeError("object_points and image_points must both be NumPy arrays or both be CUDA tensors")
-    was_np = is_np(image_points)
+    was_np = pnp.check_points(object_points, image_points)
     flags = int(flags)
     if flags & ~(HONOURED | WITHOUT_EFFECT):
         raise ValueError("calibrate_camera: flags 0x%x are not implemented (honoured: %s)" % (flags & ~(HONOURED | WITHOUT_EFFECT),
@@ -159,13 +155,7 @@ def calibrate_camera(object_points, image_points, xy, counts=None, flags=0, K=No
     if 2 * int(lengths[enough].sum()) < unknowns(int(enough.sum())):
         raise ValueError("singular: %d equations for %d free unknowns" % (2 * int(lengths[enough].sum()), unknowns(int(enough.sum()))))
 
-    img = to_device(image_points)
-    obj = to_device(object_points, device=img.device)
-    img2, obj2 = img.reshape(-1, 2), obj.reshape(-1, 3)
-    dev = img.device
-    start = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
-    pts = _native.PnpPoints(obj2.data_ptr(), img2.data_ptr(), start.data_ptr(), obj2.shape[0], img2.shape[0],
-                            FLOAT_TYPES[dtype_name(obj2)], FLOAT_TYPES[dtype_name(img2)], 3, 2, int(shared), frames)
+    pts, dev, alive = pnp.pack_points(object_points, image_points, lengths, shared)
     f64 = dict(dtype=torch.float64, device=dev)
     what = "calibrate_camera"
     if not guess:
@@ -215,11 +205,7 @@ def calibrate_camera(object_points, image_points, xy, counts=None, flags=0, K=No
         raise ValueError("calibrate_camera: status %d (%s) after %d evaluations, smallest pivot %.3g"
                          % (s[_native.CALIB_STATUS], STATUS_TEXT[3], s[_native.CALIB_EVALUATIONS], s[_native.CALIB_PIVOT]))
     k = s[_native.CALIB_K:_native.CALIB_K + 9]
-    T = torch.full((frames, 4, 4), float("nan"), **f64)
-    T[:, 3, :3] = 0
-    T[:, 3, 3] = 1
-    T[used.long(), :3, :3] = cur[:, :9].view(n_used, 3, 3)
-    T[used.long(), :3, 3] = cur[:, 9:]
+    T = pnp.poses_to_T(cur, fill=(frames, used.long()))
     error = torch.full((frames,), float("nan"), **f64)
     error[used.long()] = err
     T, error, status = to_caller((T, error, status), was_np)

@@ -7,7 +7,8 @@
 // frames.  Per frame i the sums over its points are A_i (6 x 6), B_i (6 x 9), C_i (9 x 9), gp_i, gk_i, c_i: 136 doubles in
 // the workspace.  The block is solved from the reduced system
 //   sum_i (C_i - B_i^T (A_i + l diag A_i)^-1 B_i) + l diag sum_i C_i,
-// and every frame's step follows by back-substitution.  Damping and stopping are pnp.hip's.
+// and every frame's step follows by back-substitution.  Damping and stopping are pnp_common.hpp's one rule (LM_*), which
+// pnp.hip follows too; the acceptance of a step is this file's own (CALIB_COST_RESOLUTION).
 //
 // Kernels.  k_calib_linearise and k_calib_evaluate sum over a frame's points: one wavefront per frame, four frames per
 // workgroup, no workgroup barrier, the butterfly of pnp_common.hpp.  136 accumulators do not fit beside the Jacobian, so
@@ -22,7 +23,6 @@
 namespace camd {
 
 constexpr int CALIB_MAX_EVALUATIONS = 100;      // every case of tests/calibrate_cases.py ends below half of it
-constexpr double CALIB_SINGULAR_PIVOT = 1e-10;  // smallest pivot of the unit-diagonal reduced matrix that still counts
 // A candidate is accepted when its cost is lower, or higher by no more than the rounding of the sums can explain (64 ulp
 // of the cost).  Near the minimum the cost is flat to rounding while the step is still accurate (it comes from the
 // gradient); rejecting such steps by the noise of `c2 < c` would leave the parameters about sqrt(eps c / h) from the
@@ -67,34 +67,16 @@ __device__ __forceinline__ Frame used_frame(const CalibArgs& a, int u)
     return fr;
 }
 
-// one point under R, t, cam, lens: the residual r (projected - observed, raw pixels), its 2 x 6 Jacobian Jp with respect
-// to the pose (pnp.hip's) and its 2 x 9 Jacobian Jk with respect to fx fy cx cy k1 k2 p1 p2 k3
+// one point under R, t, cam, lens: pose_terms' residual r and 2 x 6 Jacobian Jp with respect to the pose, and the 2 x 9
+// Jacobian Jk with respect to fx fy cx cy k1 k2 p1 p2 k3
 struct PointTerms {
     double r[2], Jp[2][6], Jk[2][9];
 };
 __device__ __forceinline__ void point_terms(const camd_pnp_points& p, const Frame& fr, int i, const Pinhole& cam, const Lens& k,
                                             const double* R, const double* t, PointTerms& o)
 {
-    double X[3], uv[2];
-    load_point(p, fr, i, X, uv);
-    const double P[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2],
-                         R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
-    const double z = P[2] + t[2];
-    const double iz = z != 0. ? __ddiv_rn(1., z) : 1.;  // (camd_project_points' rule)
-    const double x = (P[0] + t[0]) * iz, y = (P[1] + t[1]) * iz;
-    double xd, yd, d[4];
-    distort_forward(k, x, y, xd, yd);
-    distort_forward_jacobian(k, x, y, d);
-    o.r[0] = xd * cam.fx + cam.cx - uv[0], o.r[1] = yd * cam.fy + cam.cy - uv[1];
-#pragma unroll
-    for (int e = 0; e < 2; e++) {
-        const double f = e ? cam.fy : cam.fx, dx = d[2 * e] * f, dy = d[2 * e + 1] * f;
-        const double g[3] = {dx * iz, dy * iz, -(dx * x + dy * y) * iz};  // d pixel / d camera point
-        o.Jp[e][0] = P[1] * g[2] - P[2] * g[1];                         // (R X) x g
-        o.Jp[e][1] = P[2] * g[0] - P[0] * g[2];
-        o.Jp[e][2] = P[0] * g[1] - P[1] * g[0];
-        o.Jp[e][3] = g[0], o.Jp[e][4] = g[1], o.Jp[e][5] = g[2];
-    }
+    const Projected n = pose_terms(p, fr, i, cam, k, R, t, o.r, o.Jp);
+    const double x = n.x, y = n.y, xd = n.xd, yd = n.yd;
     const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
     const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
     o.Jk[0][0] = xd, o.Jk[0][1] = 0., o.Jk[0][2] = 1., o.Jk[0][3] = 0.;
@@ -115,32 +97,19 @@ __global__ __launch_bounds__(256) void k_calib_linearise(CalibArgs a)
     Lens k;
     load_intrinsics(a.state + CS_K, cam, k);
     double R[9], t[3];
-    for (int q = 0; q < 12; q++) {
-        const double v = a.poses[(size_t)u * 12 + q];
-        if (q < 9) R[q] = v; else t[q - 9] = v;
-    }
+    load_pose(a.poses + (size_t)u * 12, R, t);
     double* w = a.ws + (size_t)u * CALIB_WS;
     {  // pass 1: A, gp, c
-        double A[21], g[6], c = 0.;
-#pragma unroll
-        for (int q = 0; q < 21; q++) A[q] = 0.;
-#pragma unroll
-        for (int q = 0; q < 6; q++) g[q] = 0.;
+        double A[21] = {}, g[6] = {}, c = 0.;
         for (int i = lane; i < fr.n; i += 64) {
             PointTerms o;
             point_terms(a.p, fr, i, cam, k, R, t, o);
-#pragma unroll
-            for (int p = 0; p < 6; p++) {
-#pragma unroll
-                for (int q = 0; q <= p; q++) A[p * (p + 1) / 2 + q] += o.Jp[0][p] * o.Jp[0][q] + o.Jp[1][p] * o.Jp[1][q];
-                g[p] += o.Jp[0][p] * o.r[0] + o.Jp[1][p] * o.r[1];
-            }
+            add_outer<6>(A, o.Jp[0], o.Jp[1]);
+            add_gradient<6>(g, o.Jp[0], o.Jp[1], o.r);
             c += o.r[0] * o.r[0] + o.r[1] * o.r[1];
         }
-#pragma unroll
-        for (int q = 0; q < 21; q++) A[q] = wave_sum(A[q]);
-#pragma unroll
-        for (int q = 0; q < 6; q++) g[q] = wave_sum(g[q]);
+        wave_sum_all<21>(A);
+        wave_sum_all<6>(g);
         c = wave_sum(c);
         if (lane == 0) {
 #pragma unroll
@@ -151,9 +120,7 @@ __global__ __launch_bounds__(256) void k_calib_linearise(CalibArgs a)
         }
     }
     {  // pass 2: B
-        double B[54];
-#pragma unroll
-        for (int q = 0; q < 54; q++) B[q] = 0.;
+        double B[54] = {};
         for (int i = lane; i < fr.n; i += 64) {
             PointTerms o;
             point_terms(a.p, fr, i, cam, k, R, t, o);
@@ -162,33 +129,22 @@ __global__ __launch_bounds__(256) void k_calib_linearise(CalibArgs a)
 #pragma unroll
                 for (int q = 0; q < 9; q++) B[p * 9 + q] += o.Jp[0][p] * o.Jk[0][q] + o.Jp[1][p] * o.Jk[1][q];
         }
-#pragma unroll
-        for (int q = 0; q < 54; q++) B[q] = wave_sum(B[q]);
+        wave_sum_all<54>(B);
         if (lane == 0) {
 #pragma unroll
             for (int q = 0; q < 54; q++) w[WS_B + q] = B[q];
         }
     }
     {  // pass 3: C, gk
-        double C[45], g[9];
-#pragma unroll
-        for (int q = 0; q < 45; q++) C[q] = 0.;
-#pragma unroll
-        for (int q = 0; q < 9; q++) g[q] = 0.;
+        double C[45] = {}, g[9] = {};
         for (int i = lane; i < fr.n; i += 64) {
             PointTerms o;
             point_terms(a.p, fr, i, cam, k, R, t, o);
-#pragma unroll
-            for (int p = 0; p < 9; p++) {
-#pragma unroll
-                for (int q = 0; q <= p; q++) C[p * (p + 1) / 2 + q] += o.Jk[0][p] * o.Jk[0][q] + o.Jk[1][p] * o.Jk[1][q];
-                g[p] += o.Jk[0][p] * o.r[0] + o.Jk[1][p] * o.r[1];
-            }
+            add_outer<9>(C, o.Jk[0], o.Jk[1]);
+            add_gradient<9>(g, o.Jk[0], o.Jk[1], o.r);
         }
-#pragma unroll
-        for (int q = 0; q < 45; q++) C[q] = wave_sum(C[q]);
-#pragma unroll
-        for (int q = 0; q < 9; q++) g[q] = wave_sum(g[q]);
+        wave_sum_all<45>(C);
+        wave_sum_all<9>(g);
         if (lane == 0) {
 #pragma unroll
             for (int q = 0; q < 45; q++) w[WS_C + q] = C[q];
@@ -196,17 +152,6 @@ __global__ __launch_bounds__(256) void k_calib_linearise(CalibArgs a)
             for (int q = 0; q < 9; q++) w[WS_GK + q] = g[q];
         }
     }
-}
-
-// A_i + lambda diag A_i, factored (every index constant: the triangle stays in registers)
-__device__ __forceinline__ bool damped_factor(const double* w, double lambda, double* L)
-{
-#pragma unroll
-    for (int q = 0; q < 21; q++) L[q] = w[WS_A + q];
-#pragma unroll
-    for (int q = 0; q < 6; q++) L[q * (q + 1) / 2 + q] += lambda * w[WS_A + q * (q + 1) / 2 + q];
-    double pivot;
-    return cholesky<6>(L, pivot);
 }
 
 // the candidate of one frame: its step by back-substitution from the block's step, its pose, and the cost there
@@ -217,8 +162,9 @@ __global__ __launch_bounds__(256) void k_calib_evaluate(CalibArgs a)
     if (!uniform(a.state[CS_SOLVED] != 0.)) return;  // no step: k_calib_update rejects
     const Frame fr = used_frame(a, u);
     const double* w = a.ws + (size_t)u * CALIB_WS;
-    double L[21], d[6], k2[9], R[9], t[3];
-    damped_factor(w, a.state[CS_LAMBDA], L);  // (k_calib_solve factored it: it did not fail)
+    double L[21], d[6], k2[9], R[9], t[3], pivot;
+    damped<6>(w + WS_A, a.state[CS_LAMBDA], L);
+    cholesky<6>(L, pivot);  // (k_calib_solve factored it: it did not fail)
 #pragma unroll
     for (int p = 0; p < 6; p++) {
         double s = w[WS_GP + p];
@@ -227,10 +173,7 @@ __global__ __launch_bounds__(256) void k_calib_evaluate(CalibArgs a)
         d[p] = -s;
     }
     cholesky_solve<6>(L, d);
-    for (int q = 0; q < 12; q++) {
-        const double v = a.poses[(size_t)u * 12 + q];
-        if (q < 9) R[q] = v; else t[q - 9] = v;
-    }
+    load_pose(a.poses + (size_t)u * 12, R, t);
     double R2[9], t2[3] = {t[0] + d[3], t[1] + d[4], t[2] + d[5]};
     rotate_left(d, R, R2);
 #pragma unroll
@@ -247,13 +190,10 @@ __global__ __launch_bounds__(256) void k_calib_evaluate(CalibArgs a)
     c = wave_sum(c);
     if (lane == 0) {
         double* o = a.cand + (size_t)u * CALIB_CAND;
-#pragma unroll
-        for (int q = 0; q < 9; q++) o[q] = R2[q];
-#pragma unroll
-        for (int q = 0; q < 3; q++) o[9 + q] = t2[q];
+        store_pose(o, R2, t2);
         o[12] = c;
         o[13] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-        o[14] = 3. + t[0] * t[0] + t[1] * t[1] + t[2] * t[2];  // |p_i|^2: R's Frobenius norm and t
+        o[14] = pose_norm2(t);
     }
 }
 
@@ -266,16 +206,13 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
 {
     const int lane = threadIdx.x;
     const double lambda = FINAL ? 0. : a.state[CS_LAMBDA];
-    double S[45], g[9], dC[9], cost = 0.;
+    double S[45] = {}, g[9] = {}, dC[9] = {}, cost = 0.;
     int bad = 0;
-#pragma unroll
-    for (int q = 0; q < 45; q++) S[q] = 0.;
-#pragma unroll
-    for (int q = 0; q < 9; q++) g[q] = 0., dC[q] = 0.;
     for (int u = lane; u < a.used_n; u += 64) {
         const double* w = a.ws + (size_t)u * CALIB_WS;
-        double L[21], y[6];
-        bad |= !damped_factor(w, lambda, L);
+        double L[21], y[6], frame_pivot;
+        damped<6>(w + WS_A, lambda, L);
+        bad |= !cholesky<6>(L, frame_pivot);
 #pragma unroll
         for (int p = 0; p < 6; p++) y[p] = w[WS_GP + p];
         cholesky_solve<6>(L, y);
@@ -306,10 +243,9 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
             a.error[u] = sqrt(__ddiv_rn(w[WS_COST], (double)(fr.n > 0 ? fr.n : 1)));
         }
     }
-#pragma unroll
-    for (int q = 0; q < 45; q++) S[q] = wave_sum(S[q]);
-#pragma unroll
-    for (int q = 0; q < 9; q++) g[q] = wave_sum(g[q]), dC[q] = wave_sum(dC[q]);
+    wave_sum_all<45>(S);
+    wave_sum_all<9>(g);
+    wave_sum_all<9>(dC);
     bool ok = wave_or(bad) == 0;
     double scale[9], pivot;
 #pragma unroll
@@ -317,7 +253,8 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
         if (FINAL) scale[q] = __ddiv_rn(1., sqrt(S[q * (q + 1) / 2 + q]));
         else S[q * (q + 1) / 2 + q] += lambda * dC[q];
     }
-    // a fixed entry: a unit row and column, a zero right-hand side
+    // a fixed entry: a unit row and column, a zero right-hand side.  (FINAL is pnp_common.hpp's rank test written out, not
+    // unit_diagonal_pivot: the scale comes from the unmasked diagonal and the mask goes over the scaled entries, in this order)
 #pragma unroll
     for (int p = 0; p < 9; p++) {
         const bool fp = a.state[CS_MASK + p] == 0.;
@@ -334,7 +271,7 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
     if (FINAL) {
         cost = wave_sum(cost);
         if (lane == 0) {
-            const bool good = ok && pivot >= CALIB_SINGULAR_PIVOT && isfinite(cost) && a.state[CS_CONVERGED] != 0.;
+            const bool good = ok && pivot >= SINGULAR_PIVOT && isfinite(cost) && a.state[CS_CONVERGED] != 0.;
             a.state[CS_STATUS] = good ? 0. : 3.;
             a.state[CS_PIVOT] = pivot;
             a.state[CS_COST] = cost;
@@ -351,7 +288,7 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
     }
 }
 
-// accept or reject the candidate, move lambda, decide whether to stop (pnp.hip's rules on the joint step and parameters)
+// accept or reject the candidate, move lambda, decide whether to stop (the LM rule on the joint step and parameters)
 __global__ __launch_bounds__(64) void k_calib_update(CalibArgs a, int max_evaluations)
 {
     const int lane = threadIdx.x;
@@ -371,17 +308,14 @@ __global__ __launch_bounds__(64) void k_calib_update(CalibArgs a, int max_evalua
         k[q] = a.state[CS_K + q], dk[q] = a.state[CS_DK + q];
         step += dk[q] * dk[q], norm += k[q] * k[q];
     }
-    const double eps = 0x1p-52;
-    const bool small = solved && sqrt(step) < eps * (sqrt(norm) + eps);
+    const bool small = solved && lm_small(step, norm);
     const bool better = uniform(solved && (c2 < c || c2 - c <= CALIB_COST_RESOLUTION * c));
     if (better)
         for (int u = lane; u < a.used_n; u += 64)
             for (int q = 0; q < 12; q++) a.poses[(size_t)u * 12 + q] = a.cand[(size_t)u * CALIB_CAND + q];
     if (lane == 0) {
-        double lambda = a.state[CS_LAMBDA];
-        lambda = better ? lambda * 0.1 : lambda * 10.;
-        const double evals = a.state[CS_EVALS] + 1.;
-        const bool stopped = small || lambda < 1e-12 || lambda > 1e12;
+        const double lambda = lm_next(a.state[CS_LAMBDA], better), evals = a.state[CS_EVALS] + 1.;
+        const bool stopped = lm_stopped(small, lambda);
         if (better) {
 #pragma unroll
             for (int q = 0; q < 9; q++) a.state[CS_K + q] = k[q] + dk[q];
@@ -407,16 +341,6 @@ __global__ __launch_bounds__(256) void k_calib_homography(PnpArgs a, double* __r
     if (lane == 0)
         for (int q = 0; q < 9; q++) H[(size_t)f * 9 + q] = ok ? G[q] : NAN;
 }
-
-static bool points_ok(const camd_pnp_points* p)
-{
-    return p && p->frames >= 0 && float_type_ok(p->object_type) && float_type_ok(p->image_type) && p->object_stride >= 3 &&
-           p->image_stride >= 2 &&
-           (p->frames == 0 || (p->object && p->image && p->start && (uintptr_t)p->start % 8 == 0 &&
-                               (uintptr_t)p->object % (p->object_type == CAMD_VALUE_F64 ? 8 : 4) == 0 &&
-                               (uintptr_t)p->image % (p->image_type == CAMD_VALUE_F64 ? 8 : 4) == 0));
-}
-static bool doubles_ok(const void* p) { return p && (uintptr_t)p % 8 == 0; }
 
 // the arguments every part of an evaluation shares
 static int calib_args(const char* who, const camd_pnp_points* p, const int* used, int used_n, double* state, CalibArgs& a)

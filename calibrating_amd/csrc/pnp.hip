@@ -20,8 +20,7 @@ struct Normal {
     double A[21], g[6], c;  // J^T J (lower triangle packed), J^T r, r^T r
 };
 
-// residual (projected - observed, raw pixels) and its 2x6 Jacobian with respect to R <- exp([w]x) R, t <- t + d at every
-// point of the frame; their sums, reduced over the wave
+// pose_terms at every point of the frame; their sums, reduced over the wave
 __device__ __forceinline__ void normal_equations(const PnpArgs& a, const Frame& fr, int lane, const double* R, const double* t,
                                                  Normal& S)
 {
@@ -31,39 +30,14 @@ __device__ __forceinline__ void normal_equations(const PnpArgs& a, const Frame& 
     for (int q = 0; q < 6; q++) S.g[q] = 0.;
     S.c = 0.;
     for (int i = lane; i < fr.n; i += 64) {
-        double X[3], uv[2];
-        load_point(a.p, fr, i, X, uv);
-        const double P[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2],
-                             R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
-        const double z = P[2] + t[2];
-        const double iz = z != 0. ? __ddiv_rn(1., z) : 1.;  // (camd_project_points' rule)
-        const double x = (P[0] + t[0]) * iz, y = (P[1] + t[1]) * iz;
-        double xd, yd, d[4];
-        distort_forward(a.k, x, y, xd, yd);
-        distort_forward_jacobian(a.k, x, y, d);
-        const double r[2] = {xd * a.cam.fx + a.cam.cx - uv[0], yd * a.cam.fy + a.cam.cy - uv[1]};
-        double J[2][6];
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-            const double f = e ? a.cam.fy : a.cam.fx, dx = d[2 * e] * f, dy = d[2 * e + 1] * f;
-            const double g[3] = {dx * iz, dy * iz, -(dx * x + dy * y) * iz};  // d pixel / d camera point
-            J[e][0] = P[1] * g[2] - P[2] * g[1];                            // (R X) x g
-            J[e][1] = P[2] * g[0] - P[0] * g[2];
-            J[e][2] = P[0] * g[1] - P[1] * g[0];
-            J[e][3] = g[0], J[e][4] = g[1], J[e][5] = g[2];
-        }
-#pragma unroll
-        for (int p = 0; p < 6; p++) {
-#pragma unroll
-            for (int q = 0; q <= p; q++) S.A[p * (p + 1) / 2 + q] += J[0][p] * J[0][q] + J[1][p] * J[1][q];
-            S.g[p] += J[0][p] * r[0] + J[1][p] * r[1];
-        }
+        double r[2], J[2][6];
+        pose_terms(a.p, fr, i, a.cam, a.k, R, t, r, J);
+        add_outer<6>(S.A, J[0], J[1]);
+        add_gradient<6>(S.g, J[0], J[1], r);
         S.c += r[0] * r[0] + r[1] * r[1];
     }
-#pragma unroll
-    for (int q = 0; q < 21; q++) S.A[q] = wave_sum(S.A[q]);
-#pragma unroll
-    for (int q = 0; q < 6; q++) S.g[q] = wave_sum(S.g[q]);
+    wave_sum_all<21>(S.A);
+    wave_sum_all<6>(S.g);
     S.c = wave_sum(S.c);
 }
 
@@ -71,7 +45,7 @@ __device__ __forceinline__ void store_frame(int lane, int f, const double* R, co
                                             int status, double* pose, double* rms_out, int* iterations_out, int* status_out)
 {
     if (lane != 0) return;
-    for (int q = 0; q < 12; q++) pose[(size_t)f * 12 + q] = status == PNP_OK ? (q < 9 ? R[q] : t[q - 9]) : NAN;
+    store_pose(pose + (size_t)f * 12, R, t, status == PNP_OK);
     rms_out[f] = status == PNP_OK ? rms : NAN;
     iterations_out[f] = iterations;
     status_out[f] = status;
@@ -87,42 +61,31 @@ __global__ __launch_bounds__(256) void k_pnp_refine(PnpArgs a, const double* __r
     const Frame fr = frame_rows(a.p, f, a.min_points);
     int status = fr.status;
     if (status == PNP_OK && frame_nonfinite(a.p, fr, lane)) status = PNP_NONFINITE;
-    if (status == PNP_OK) {
-        bool finite = true;
-        for (int q = 0; q < 12; q++) {
-            const double v = pose0[(size_t)f * pose0_stride + q];
-            finite = finite && isfinite(v);
-            if (q < 9) R[q] = v; else t[q - 9] = v;
-        }
-        if (!uniform(finite)) status = PNP_SINGULAR;  // no start pose could be made (camd_pnp_init on a degenerate frame)
-    }
+    // a start pose that is not finite: none could be made (camd_pnp_init on a degenerate frame)
+    if (status == PNP_OK && !uniform(load_pose(pose0 + (size_t)f * pose0_stride, R, t))) status = PNP_SINGULAR;
     if (status != PNP_OK) {
         store_frame(lane, f, R, t, 0., 0, status, pose, rms_out, iterations_out, status_out);
         return;
     }
-    const double eps = 0x1p-52;
     Normal S, S2;
     normal_equations(a, fr, lane, R, t, S);
-    double lambda = 1e-3;
+    double lambda = LM_LAMBDA_START;
     int it = 0;
     bool stopped = false;
     while (uniform(it < PNP_MAX_ITERATIONS && !stopped)) {
         it++;
         double L[21], d[6], pivot;
+        damped<6>(S.A, lambda, L);
 #pragma unroll
-        for (int q = 0; q < 21; q++) L[q] = S.A[q];
-#pragma unroll
-        for (int q = 0; q < 6; q++) L[q * (q + 1) / 2 + q] += lambda * S.A[q * (q + 1) / 2 + q], d[q] = -S.g[q];
+        for (int q = 0; q < 6; q++) d[q] = -S.g[q];
         bool better = false, small = false;
         if (uniform(cholesky<6>(L, pivot))) {
             cholesky_solve<6>(L, d);
             double R2[9], t2[3] = {t[0] + d[3], t[1] + d[4], t[2] + d[5]};
             rotate_left(d, R, R2);
             normal_equations(a, fr, lane, R2, t2, S2);
-            const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-            const double norm = sqrt(3. + t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);  // |p|: R's Frobenius norm and t
-            small = step < eps * (norm + eps);
-            better = S2.c < S.c;
+            small = lm_small(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5], pose_norm2(t));
+            better = S2.c < S.c;  // (the bare comparison; calibrate.hip's rule also takes a cost within its rounding)
             if (uniform(better)) {
 #pragma unroll
                 for (int q = 0; q < 9; q++) R[q] = R2[q];
@@ -131,21 +94,13 @@ __global__ __launch_bounds__(256) void k_pnp_refine(PnpArgs a, const double* __r
                 S = S2;
             }
         }
-        lambda = uniform(better) ? lambda * 0.1 : lambda * 10.;
-        stopped = uniform(small || lambda < 1e-12 || lambda > 1e12);
+        lambda = lm_next(lambda, uniform(better));
+        stopped = uniform(lm_stopped(small, lambda));
     }
-    // a pose is one only where the undamped system has full rank: J^T J scaled to a unit diagonal, then its pivots
-    {
-        double L[21], s[6], pivot;
-#pragma unroll
-        for (int q = 0; q < 6; q++) s[q] = __ddiv_rn(1., sqrt(S.A[q * (q + 1) / 2 + q]));
-#pragma unroll
-        for (int p = 0; p < 6; p++)
-#pragma unroll
-            for (int q = 0; q <= p; q++) L[p * (p + 1) / 2 + q] = S.A[p * (p + 1) / 2 + q] * s[p] * s[q];
-        const bool ok = cholesky<6>(L, pivot);
-        if (!uniform(ok && pivot >= PNP_SINGULAR_PIVOT && isfinite(S.c) && stopped)) status = PNP_SINGULAR;
-    }
+    // a pose is one only where the undamped system has full rank
+    double pivot;
+    const bool ok = unit_diagonal_pivot<6>(S.A, pivot);
+    if (!uniform(ok && pivot >= SINGULAR_PIVOT && isfinite(S.c) && stopped)) status = PNP_SINGULAR;
     store_frame(lane, f, R, t, sqrt(__ddiv_rn(S.c, 2. * fr.n)), it, status, pose, rms_out, iterations_out, status_out);
 }
 
@@ -201,18 +156,13 @@ __global__ __launch_bounds__(256) void k_pnp_init(PnpArgs a, double* __restrict_
             for (int q = 0; q < 3; q++) R[q] = r1[q], R[3 + q] = r2[q], R[6 + q] = r3[q], t[q] = s * P[4 * q + 3];
         }
     }
-    if (lane == 0)
-        for (int q = 0; q < 12; q++) pose[(size_t)f * 12 + q] = ok ? (q < 9 ? R[q] : t[q - 9]) : NAN;
+    if (lane == 0) store_pose(pose + (size_t)f * 12, R, t, ok);
 }
 
 static int pnp_args(const char* who, const camd_pnp_points* p, const double K[9], const double* dist, int ndist, PnpArgs& a)
 {
     const bool bad_dist = (ndist != 0 && ndist != 4 && ndist != 5 && ndist != 8 && ndist != 12 && ndist != 14) || (ndist > 0 && !dist);
-    if (!p || !K || bad_dist || p->frames < 0 || !float_type_ok(p->object_type) || !float_type_ok(p->image_type) ||
-        p->object_stride < 3 || p->image_stride < 2 ||
-        (p->frames > 0 && (!p->object || !p->image || !p->start || (uintptr_t)p->start % 8 != 0 ||
-                           (uintptr_t)p->object % (p->object_type == CAMD_VALUE_F64 ? 8 : 4) != 0 ||
-                           (uintptr_t)p->image % (p->image_type == CAMD_VALUE_F64 ? 8 : 4) != 0))) {
+    if (!points_ok(p) || !K || bad_dist) {
         set_error("%s: bad arguments (points: object / image rows of CAMD_VALUE_F64 or _F32, aligned to an element, strides >= 3 "
                   "/ >= 2; start: frames + 1 device int64; K is 9 host doubles; ndist is 0, 4, 5, 8, 12 or 14, got %d)", who, ndist);
         return CAMD_ERR_BAD_ARG;
@@ -233,7 +183,7 @@ int camd_pnp_init(const camd_pnp_points* points, const double K[9], const double
     PnpArgs a = {};
     int rc = pnp_args("camd_pnp_init", points, K, dist, ndist, a);
     if (rc != CAMD_OK) return rc;
-    if ((planar && !plane) || (a.p.frames > 0 && (!pose || (uintptr_t)pose % 8 != 0))) {
+    if ((planar && !plane) || (a.p.frames > 0 && !doubles_ok(pose))) {
         set_error("camd_pnp_init: bad arguments (a planar target needs its plane's rotation, 9 host doubles; pose: frames x 12 "
                   "device doubles)");
         return CAMD_ERR_BAD_ARG;
@@ -254,9 +204,8 @@ int camd_pnp_refine(const camd_pnp_points* points, const double K[9], const doub
     int rc = pnp_args("camd_pnp_refine", points, K, dist, ndist, a);
     if (rc != CAMD_OK) return rc;
     if (min_points < 3 || (pose0_stride != 0 && pose0_stride != 12) ||
-        (a.p.frames > 0 && (!pose0 || !pose || !rms || !iterations || !status || (uintptr_t)pose0 % 8 != 0 ||
-                            (uintptr_t)pose % 8 != 0 || (uintptr_t)rms % 8 != 0 || (uintptr_t)iterations % 4 != 0 ||
-                            (uintptr_t)status % 4 != 0))) {
+        (a.p.frames > 0 && (!doubles_ok(pose0) || !doubles_ok(pose) || !doubles_ok(rms) || !iterations || !status ||
+                            (uintptr_t)iterations % 4 != 0 || (uintptr_t)status % 4 != 0))) {
         set_error("camd_pnp_refine: bad arguments (min_points >= 3, got %d; pose0_stride is 12, or 0 for one start pose, got %d; "
                   "pose0, pose, rms, iterations, status: device arrays)", min_points, pose0_stride);
         return CAMD_ERR_BAD_ARG;

@@ -1,6 +1,14 @@
 // pnp_common.hpp -- what the per-frame solvers share: pnp.hip (a pose per frame) and calibrate.hip (the intrinsics and a
-// pose per frame).  One wavefront per frame: the fixed-order butterfly sums, a frame's checked rows, the register Cholesky,
-// the local rotation update and the Hartley-normalised direct linear transform.
+// pose per frame).  One wavefront per frame.  It offers:
+//   points_ok, doubles_ok; frame_rows, load_point, frame_nonfinite   the host's check of the points; a frame's checked rows
+//   wave_sum, wave_sum_all, wave_or, uniform   the fixed-order butterfly: the same bits of a sum in every lane
+//   load_pose, store_pose, pose_terms          R, t as 12 doubles; a point's residual (raw pixels) and 2 x 6 pose Jacobian
+//   add_outer, add_gradient                    J^T J (packed lower triangle) and J^T r, two rows of J at a time
+//   damped, cholesky, cholesky_solve           (A + lambda diag A) x = b in registers
+//   unit_diagonal_pivot, SINGULAR_PIVOT        the rank test: the smallest pivot of A scaled to a unit diagonal
+//   LM_*, lm_small, lm_next, lm_stopped        the one Levenberg-Marquardt rule (damping, stopping); pose_norm2: its |p|^2
+//   rotate_left; null_vector, direct_linear_transform   R <- exp([w]x) R; the Hartley-normalised start (H or P)
+// Acceptance of a step is NOT here: pnp.hip takes a lower cost, calibrate.hip also one within the rounding of its sums.
 #pragma once
 
 #include <climits>
@@ -12,7 +20,16 @@ namespace camd {
 enum { PNP_OK = 0, PNP_FEW = 1, PNP_NONFINITE = 2, PNP_SINGULAR = 3 };
 constexpr int PNP_MAX_ITERATIONS = 100;
 constexpr int PNP_UNDISTORT_ITERS = 10;  // rounds of cv2.undistortPoints' iteration for the start pose (cv2 runs 5)
-constexpr double PNP_SINGULAR_PIVOT = 1e-10;  // smallest pivot of the unit-diagonal normal matrix that still counts as a pose
+constexpr double SINGULAR_PIVOT = 1e-10;  // smallest pivot of the unit-diagonal (reduced) normal matrix that still counts
+
+// ---- the Levenberg-Marquardt rule of every solver here: Marquardt's lambda diag(J^T J); calibrate.py writes the start ----
+constexpr double LM_LAMBDA_START = 1e-3, LM_LAMBDA_DOWN = 0.1, LM_LAMBDA_UP = 10.;  // after a step that is taken / is not
+constexpr double LM_LAMBDA_MIN = 1e-12, LM_LAMBDA_MAX = 1e12, LM_EPS = 0x1p-52;  // small: |step| < eps (|p| + eps), given squared
+__device__ __forceinline__ bool lm_small(double step2, double norm2) { return sqrt(step2) < LM_EPS * (sqrt(norm2) + LM_EPS); }
+__device__ __forceinline__ double lm_next(double lambda, bool better) { return better ? lambda * LM_LAMBDA_DOWN : lambda * LM_LAMBDA_UP; }
+__device__ __forceinline__ bool lm_stopped(bool small, double lambda) { return small || lambda < LM_LAMBDA_MIN || lambda > LM_LAMBDA_MAX; }
+// |p|^2 of one pose: R's Frobenius norm and t
+__device__ __forceinline__ double pose_norm2(const double* t) { return 3. + t[0] * t[0] + t[1] * t[1] + t[2] * t[2]; }
 
 struct PnpArgs {
     Pinhole cam;
@@ -22,12 +39,29 @@ struct PnpArgs {
     int planar, min_points;
 };
 
+// the host's checks: rows of a float type, aligned to an element, with their strides; an aligned device array of doubles
+static inline bool points_ok(const camd_pnp_points* p)
+{
+    return p && p->frames >= 0 && float_type_ok(p->object_type) && float_type_ok(p->image_type) && p->object_stride >= 3 &&
+           p->image_stride >= 2 &&
+           (p->frames == 0 || (p->object && p->image && p->start && (uintptr_t)p->start % 8 == 0 &&
+                               (uintptr_t)p->object % (p->object_type == CAMD_VALUE_F64 ? 8 : 4) == 0 &&
+                               (uintptr_t)p->image % (p->image_type == CAMD_VALUE_F64 ? 8 : 4) == 0));
+}
+static inline bool doubles_ok(const void* p) { return p && (uintptr_t)p % 8 == 0; }
+
 // sum over the wave, the same bits in every lane: lane i adds lane i ^ m, and a + b == b + a
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
     return v;
+}
+template <int N>
+__device__ __forceinline__ void wave_sum_all(double* x)
+{
+#pragma unroll
+    for (int q = 0; q < N; q++) x[q] = wave_sum(x[q]);
 }
 __device__ __forceinline__ int wave_or(int v)
 {
@@ -84,8 +118,77 @@ __device__ __forceinline__ bool frame_nonfinite(const camd_pnp_points& p, const 
     return uniform(wave_or(bad) != 0);
 }
 
+// R, t as 12 doubles; false where one of them is NaN or infinite
+__device__ __forceinline__ bool load_pose(const double* src, double* R, double* t)
+{
+    bool finite = true;
+    for (int q = 0; q < 12; q++) {
+        const double v = src[q];
+        finite = finite && isfinite(v);
+        if (q < 9) R[q] = v; else t[q - 9] = v;
+    }
+    return finite;
+}
+__device__ __forceinline__ void store_pose(double* dst, const double* R, const double* t, bool ok = true)  // NaN where not ok
+{
+    for (int q = 0; q < 12; q++) dst[q] = ok ? (q < 9 ? R[q] : t[q - 9]) : NAN;
+}
+
+// One point under R, t, cam, lens: the residual r (projected - observed, raw pixels) and its 2 x 6 Jacobian J with respect
+// to R <- exp([w]x) R, t <- t + d.  Returned: the normalised image point before the lens (x, y) and behind it (xd, yd).
+struct Projected { double x, y, xd, yd; };
+__device__ __forceinline__ Projected pose_terms(const camd_pnp_points& p, const Frame& fr, int i, const Pinhole& cam, const Lens& k,
+                                                const double* R, const double* t, double r[2], double J[2][6])
+{
+    double X[3], uv[2];
+    load_point(p, fr, i, X, uv);
+    const double P[3] = {R[0] * X[0] + R[1] * X[1] + R[2] * X[2], R[3] * X[0] + R[4] * X[1] + R[5] * X[2],
+                         R[6] * X[0] + R[7] * X[1] + R[8] * X[2]};
+    const double z = P[2] + t[2];
+    const double iz = z != 0. ? __ddiv_rn(1., z) : 1.;  // (camd_project_points' rule)
+    const double x = (P[0] + t[0]) * iz, y = (P[1] + t[1]) * iz;
+    double xd, yd, d[4];
+    distort_forward(k, x, y, xd, yd);
+    distort_forward_jacobian(k, x, y, d);
+    r[0] = xd * cam.fx + cam.cx - uv[0], r[1] = yd * cam.fy + cam.cy - uv[1];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const double f = e ? cam.fy : cam.fx, dx = d[2 * e] * f, dy = d[2 * e + 1] * f;
+        const double g[3] = {dx * iz, dy * iz, -(dx * x + dy * y) * iz};  // d pixel / d camera point
+        J[e][0] = P[1] * g[2] - P[2] * g[1];                            // (R X) x g
+        J[e][1] = P[2] * g[0] - P[0] * g[2];
+        J[e][2] = P[0] * g[1] - P[1] * g[0];
+        J[e][3] = g[0], J[e][4] = g[1], J[e][5] = g[2];
+    }
+    return {x, y, xd, yd};
+}
+
 // ---- a symmetric positive definite system of N unknowns, lower triangle packed row by row: L[i (i + 1) / 2 + j] ----
 // every index is a constant after unrolling, so the triangle lives in registers
+// A += a0 a0^T + a1 a1^T and g += a0 r[0] + a1 r[1]: the two rows of one point's Jacobian
+template <int N>
+__device__ __forceinline__ void add_outer(double* A, const double* a0, const double* a1)
+{
+#pragma unroll
+    for (int p = 0; p < N; p++)
+#pragma unroll
+        for (int q = 0; q <= p; q++) A[p * (p + 1) / 2 + q] += a0[p] * a0[q] + a1[p] * a1[q];
+}
+template <int N>
+__device__ __forceinline__ void add_gradient(double* g, const double* a0, const double* a1, const double* r)
+{
+#pragma unroll
+    for (int p = 0; p < N; p++) g[p] += a0[p] * r[0] + a1[p] * r[1];
+}
+// L = A + lambda diag A, for the caller to factor
+template <int N>
+__device__ __forceinline__ void damped(const double* A, double lambda, double* L)
+{
+#pragma unroll
+    for (int q = 0; q < N * (N + 1) / 2; q++) L[q] = A[q];
+#pragma unroll
+    for (int q = 0; q < N; q++) L[q * (q + 1) / 2 + q] += lambda * A[q * (q + 1) / 2 + q];
+}
 template <int N>
 __device__ __forceinline__ bool cholesky(double* L, double& min_pivot)
 {
@@ -127,6 +230,20 @@ __device__ __forceinline__ void cholesky_solve(const double* L, double* x)  // x
         for (int q = i + 1; q < N; q++) s -= L[q * (q + 1) / 2 + i] * x[q];
         x[i] = __ddiv_rn(s, L[i * (i + 1) / 2 + i]);
     }
+}
+
+// the rank test: A scaled to a unit diagonal, factored; its smallest pivot is compared with SINGULAR_PIVOT by the caller
+template <int N>
+__device__ __forceinline__ bool unit_diagonal_pivot(const double* A, double& pivot)
+{
+    double L[N * (N + 1) / 2], s[N];
+#pragma unroll
+    for (int q = 0; q < N; q++) s[q] = __ddiv_rn(1., sqrt(A[q * (q + 1) / 2 + q]));
+#pragma unroll
+    for (int p = 0; p < N; p++)
+#pragma unroll
+        for (int q = 0; q <= p; q++) L[p * (p + 1) / 2 + q] = A[p * (p + 1) / 2 + q] * s[p] * s[q];
+    return cholesky<N>(L, pivot);
 }
 
 // R2 = exp([w]x) R: I + A [w]x + B [w]x^2 with A = sin(th) / th, B = (sin(th / 2) / (th / 2))^2 / 2, no cancellation
@@ -219,13 +336,9 @@ __device__ __forceinline__ bool direct_linear_transform(const PnpArgs& a, const 
             r[0][q] = h[q], r[0][C + q] = 0., r[0][2 * C + q] = -x * h[q];
             r[1][q] = 0., r[1][C + q] = h[q], r[1][2 * C + q] = -y * h[q];
         }
-#pragma unroll
-        for (int p = 0; p < N; p++)
-#pragma unroll
-            for (int q = 0; q <= p; q++) M[p * (p + 1) / 2 + q] += r[0][p] * r[0][q] + r[1][p] * r[1][q];
+        add_outer<N>(M, r[0], r[1]);
     }
-#pragma unroll
-    for (int q = 0; q < N * (N + 1) / 2; q++) M[q] = wave_sum(M[q]);
+    wave_sum_all<N * (N + 1) / 2>(M);
     double v[N];
     const bool ok = null_vector<N>(M, v);
     // G = Ti^-1 Gn To: To = [so I, -so mean; 0 1], Ti^-1 = [1 / si, 0, mx; 0, 1 / si, my; 0, 0, 1]

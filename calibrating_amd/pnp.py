@@ -18,12 +18,40 @@ STATUS_TEXT = {0: "ok", 1: "too few points", 2: "non-finite input", 3: "singular
 PLANAR_RATIO = 1e-3  # planar: the smallest singular value of the centred object points below this part of the middle one
 
 
-def _rows(a, width, what):
-    check_array(a, what)
-    if dtype_name(a) not in FLOAT_TYPES:
-        raise ValueError("%s must be float32 or float64, got %s" % (what, a.dtype))
-    if a.ndim not in (2, 3) or a.shape[-1] != width:
-        raise ValueError("%s must be (n, %d) or (f, n, %d), got %s" % (what, width, width, tuple(a.shape)))
+def check_points(object_points, image_points):
+    """The refusals every entry point begins with -> whether the points are NumPy arrays (CUDA tensors otherwise)."""
+    for a, width, what in ((object_points, 3, "object_points"), (image_points, 2, "image_points")):
+        check_array(a, what)
+        if dtype_name(a) not in FLOAT_TYPES:
+            raise ValueError("%s must be float32 or float64, got %s" % (what, a.dtype))
+        if a.ndim not in (2, 3) or a.shape[-1] != width:
+            raise ValueError("%s must be (n, %d) or (f, n, %d), got %s" % (what, width, width, tuple(a.shape)))
+    if is_np(object_points) != is_np(image_points):
+        raise TypeError("object_points and image_points must both be NumPy arrays or both be CUDA tensors")
+    return is_np(image_points)
+
+
+def pack_points(object_points, image_points, lengths, shared):
+    """The hand-over -> (``camd_pnp_points``, device, the tensors it points into: keep them alive while it is used)."""
+    import torch
+    img2 = to_device(image_points).reshape(-1, 2)
+    obj2 = to_device(object_points, device=img2.device).reshape(-1, 3)
+    start = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(img2.device)
+    pts = _native.PnpPoints(obj2.data_ptr(), img2.data_ptr(), start.data_ptr(), obj2.shape[0], img2.shape[0],
+                            FLOAT_TYPES[dtype_name(obj2)], FLOAT_TYPES[dtype_name(img2)], 3, 2, int(shared), len(lengths))
+    return pts, img2.device, (obj2, img2, start)
+
+
+def poses_to_T(pose, fill=None):
+    """(f, 12) R, t -> (f, 4, 4); ``fill = (frames, at)``: they are the frames ``at`` of ``frames``, the others get NaN."""
+    frames, at = (len(pose), slice(None)) if fill is None else fill
+    T = pose.new_zeros((frames, 4, 4))
+    if fill is not None:
+        T[:, :3] = float("nan")
+    T[at, :3, :3] = pose[:, :9].view(-1, 3, 3)
+    T[at, :3, 3] = pose[:, 9:]
+    T[:, 3, 3] = 1
+    return T
 
 
 def plane_of(object_points):
@@ -94,11 +122,7 @@ def solve_pnp_batch(object_points, image_points, K, D=None, counts=None, T0=None
     before anything is launched: a batch of a target with depth, without ``T0``, that has no frame of 6 points (CUDA
     object points are read back once for the planarity test; with ``T0`` nothing is)."""
     import torch
-    _rows(object_points, 3, "object_points")
-    _rows(image_points, 2, "image_points")
-    if is_np(object_points) != is_np(image_points):
-        raise TypeError("object_points and image_points must both be NumPy arrays or both be CUDA tensors")
-    was_np = is_np(image_points)
+    was_np = check_points(object_points, image_points)
     Dv, dptr, nd = dist(D)
     if nd not in (0, 4, 5, 8, 12, 14):
         raise ValueError("D must hold 0, 4, 5, 8, 12 or 14 coefficients, got %d" % nd)
@@ -119,13 +143,7 @@ def solve_pnp_batch(object_points, image_points, K, D=None, counts=None, T0=None
         if lengths.max() < min_points:
             raise ValueError("every frame has fewer than 6 points (non-planar target)")
 
-    img = to_device(image_points)
-    obj = to_device(object_points, device=img.device)
-    img2, obj2 = img.reshape(-1, 2), obj.reshape(-1, 3)
-    dev = img.device
-    start = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
-    pts = _native.PnpPoints(obj2.data_ptr(), img2.data_ptr(), start.data_ptr(), obj2.shape[0], img2.shape[0],
-                            FLOAT_TYPES[dtype_name(obj2)], FLOAT_TYPES[dtype_name(img2)], 3, 2, int(shared), frames)
+    pts, dev, alive = pack_points(object_points, image_points, lengths, shared)
     pose = torch.empty((frames, 12), dtype=torch.float64, device=dev)
     rms = torch.empty(frames, dtype=torch.float64, device=dev)
     iterations = torch.empty(frames, dtype=torch.int32, device=dev)
@@ -138,9 +156,5 @@ def solve_pnp_batch(object_points, image_points, K, D=None, counts=None, T0=None
         start_pose, stride = torch.from_numpy(pose0).to(dev), (12 if len(pose0) > 1 or frames == 1 else 0)
     _native.call("camd_pnp_refine", dev, ctypes.byref(pts), Kf.ctypes.data, dptr, nd, min_points, start_pose.data_ptr(), stride,
                  pose.data_ptr(), rms.data_ptr(), iterations.data_ptr(), status.data_ptr(), what="solve_pnp_batch")
-    T = torch.zeros((frames, 4, 4), dtype=torch.float64, device=dev)
-    T[:, :3, :3] = pose[:, :9].view(frames, 3, 3)
-    T[:, :3, 3] = pose[:, 9:]
-    T[:, 3, 3] = 1
-    T, rms, iterations, status = to_caller((T, rms, iterations, status), was_np)
+    T, rms, iterations, status = to_caller((poses_to_T(pose), rms, iterations, status), was_np)
     return dict(T=T, reprojection_error=rms, iterations=iterations, status=status)

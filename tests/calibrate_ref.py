@@ -35,18 +35,7 @@ def free_mask(flags):
 
 def homography(obj, uv, plane):
     """plane coordinates (the object points turned by ``plane``, x and y) -> raw pixels, as the kernel forms it"""
-    X = (obj @ plane.T)[:, :2]
-    m, mi = X.mean(0), uv.mean(0)
-    so = np.sqrt(2.0) / np.sqrt(((X - m) ** 2).sum(1)).mean()
-    si = np.sqrt(2.0) / np.sqrt(((uv - mi) ** 2).sum(1)).mean()
-    h = np.concatenate([(X - m) * so, np.ones((len(X), 1))], 1)
-    x, y = ((uv - mi) * si).T
-    z = np.zeros_like(h)
-    rows = np.concatenate([np.concatenate([h, z, -x[:, None] * h], 1), np.concatenate([z, h, -y[:, None] * h], 1)])
-    Gn = np.linalg.eigh(rows.T @ rows)[1][:, 0].reshape(3, 3)
-    To = np.array([[so, 0, -so * m[0]], [0, so, -so * m[1]], [0, 0, 1]])
-    Ti_inv = np.array([[1 / si, 0, mi[0]], [0, 1 / si, mi[1]], [0, 0, 1]])
-    return Ti_inv @ Gn @ To
+    return pnp_ref.normalised_dlt((obj @ plane.T)[:, :2], uv)
 
 
 def initial_camera_matrix(Hs, xy):
@@ -74,16 +63,8 @@ def camera_of(k):
 def frame_terms(R, t, obj, uv, k):
     """residuals (2n,), pose Jacobian (2n, 6), intrinsic Jacobian (2n, 9) of one frame at R, t and k = fx fy cx cy k1 k2 p1 p2 k3"""
     K, D = camera_of(k)
-    P = obj @ R.T
-    Xc = P + t
+    r, Jp, x, y, _ = pnp_ref.pose_jacobian(R, t, obj, uv, K, D)
     with np.errstate(all="ignore"):
-        iz = np.where(Xc[:, 2] != 0, 1.0 / Xc[:, 2], 1.0)
-        x, y = Xc[:, 0] * iz, Xc[:, 1] * iz
-        r = points_ref.project_points(obj, R, t, K, D) - uv
-        d = pnp_ref.distort_jacobian(D, x, y) * np.array([K[0, 0], K[1, 1]])[None, :, None]
-        g = np.stack([d[:, :, 0] * iz[:, None], d[:, :, 1] * iz[:, None],
-                      -(d[:, :, 0] * x[:, None] + d[:, :, 1] * y[:, None]) * iz[:, None]], 2)
-        Jp = np.concatenate([np.cross(P[:, None, :], g), g], 2).reshape(-1, 6)
         k1, k2, p1, p2, k3 = _coefficients(D)[:5]
         r2 = x * x + y * y
         r4 = r2 * r2

@@ -41,8 +41,9 @@ def residuals(R, t, obj, uv, K, D):
     return points_ref.project_points(obj, R, t, K, D) - uv
 
 
-def normal_equations(R, t, obj, uv, K, D):
-    """(J^T J (6, 6), J^T r (6,), r^T r) at the pose R, t."""
+def pose_jacobian(R, t, obj, uv, K, D):
+    """(r (n, 2) residuals, J (2n, 6) their Jacobian in R <- exp([w]x) R, t <- t + d, and x, y, iz of the projection) at
+    the pose R, t.  (``uv`` is among the arguments because the residual needs it.)"""
     K = np.asarray(K, np.float64)
     P = obj @ R.T
     Xc = P + t
@@ -54,6 +55,13 @@ def normal_equations(R, t, obj, uv, K, D):
         g = np.stack([d[:, :, 0] * iz[:, None], d[:, :, 1] * iz[:, None],
                       -(d[:, :, 0] * x[:, None] + d[:, :, 1] * y[:, None]) * iz[:, None]], 2)  # (n, 2, 3): d pixel / d camera point
         J = np.concatenate([np.cross(P[:, None, :], g), g], 2).reshape(-1, 6)
+    return r, J, x, y, iz
+
+
+def normal_equations(R, t, obj, uv, K, D):
+    """(J^T J (6, 6), J^T r (6,), r^T r) at the pose R, t."""
+    r, J = pose_jacobian(R, t, obj, uv, K, D)[:2]
+    with np.errstate(all="ignore"):
         rr = r.reshape(-1)
         A = (J[:, :, None] * J[:, None, :]).sum(0)
         return A, (J * rr[:, None]).sum(0), (rr * rr).sum()
@@ -137,17 +145,15 @@ def null_vector_by_inverse_iteration(M):
     return v
 
 
-def init_pose(obj, uv, K, D, planar, plane, null="eigh"):
-    """The start pose of the direct linear transform on Hartley-normalised points, as the kernel forms it; ``null``: the
-    null vector from ``numpy.linalg.eigh`` or, "kernel", from the kernel's inverse iteration."""
-    obj, uv = np.asarray(obj, np.float64), np.asarray(uv, np.float64)
-    xy = points_ref.undistort_trace(uv, K, D, iters=10)[0]
-    X = obj @ plane.T if planar else obj
-    Dn = 2 if planar else 3
+def normalised_dlt(X, xy, null="eigh"):
+    """G (3, d + 1) with xy ~ G [X 1] from (n, d) object and (n, 2) image coordinates: the direct linear transform on
+    Hartley-normalised points, as the kernel forms it; ``null``: the null vector from ``numpy.linalg.eigh`` or, "kernel",
+    from the kernel's inverse iteration."""
+    Dn = X.shape[1]
     m, mi = X.mean(0), xy.mean(0)
-    so = np.sqrt(Dn) / np.sqrt(((X[:, :Dn] - m[:Dn]) ** 2).sum(1)).mean()
+    so = np.sqrt(Dn) / np.sqrt(((X - m) ** 2).sum(1)).mean()
     si = np.sqrt(2.0) / np.sqrt(((xy - mi) ** 2).sum(1)).mean()
-    h = np.concatenate([(X[:, :Dn] - m[:Dn]) * so, np.ones((len(X), 1))], 1)
+    h = np.concatenate([(X - m) * so, np.ones((len(X), 1))], 1)
     x, y = ((xy - mi) * si).T
     z = np.zeros_like(h)
     rows = np.concatenate([np.concatenate([h, z, -x[:, None] * h], 1), np.concatenate([z, h, -y[:, None] * h], 1)])
@@ -156,9 +162,19 @@ def init_pose(obj, uv, K, D, planar, plane, null="eigh"):
     Gn = v.reshape(3, Dn + 1)
     To = np.eye(Dn + 1)
     To[:Dn, :Dn] *= so
-    To[:Dn, Dn] = -so * m[:Dn]
+    To[:Dn, Dn] = -so * m
     Ti_inv = np.array([[1 / si, 0, mi[0]], [0, 1 / si, mi[1]], [0, 0, 1]])
-    G = Ti_inv @ Gn @ To
+    return Ti_inv @ Gn @ To
+
+
+def init_pose(obj, uv, K, D, planar, plane, null="eigh"):
+    """The start pose from ``normalised_dlt`` of the object points (a plane's: turned by ``plane``, x and y) and the
+    undistorted image points, as the kernel forms it."""
+    obj, uv = np.asarray(obj, np.float64), np.asarray(uv, np.float64)
+    xy = points_ref.undistort_trace(uv, K, D, iters=10)[0]
+    X = obj @ plane.T if planar else obj
+    m = X.mean(0)
+    G = normalised_dlt(X[:, :2 if planar else 3], xy, null)
     unit = lambda a: a / np.linalg.norm(a)  # noqa: E731
     T = np.eye(4)
     if planar:
