@@ -20,6 +20,7 @@ from .geometry import mean_Ts
 from .pnp import solve_pnp_batch
 from .calibrate import (CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3, CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6,
                         CALIB_FIX_PRINCIPAL_POINT, CALIB_USE_INTRINSIC_GUESS, CALIB_ZERO_TANGENT_DIST, calibrate_camera)
+from .stereo_calibrate import CALIB_FIX_INTRINSIC, CALIB_USE_EXTRINSIC_GUESS, stereo_calibrate
 from .vis import resolve_max_l1, vis_align, vis_depth, vis_depth_l1, vis_stereo
 
 __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "StereoSGBM",
@@ -29,4 +30,5 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "matching_uvs_in_one_img_batch", "ReconstructionExtrinsics", "warp_flow", "vis_depth", "vis_depth_l1",
            "resolve_max_l1", "vis_stereo", "vis_align", "solve_pnp_batch", "mean_Ts",
            "calibrate_camera", "CALIB_USE_INTRINSIC_GUESS", "CALIB_FIX_PRINCIPAL_POINT", "CALIB_FIX_FOCAL_LENGTH",
-           "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6"]
+           "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
+           "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS"]

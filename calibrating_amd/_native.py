@@ -46,6 +46,10 @@ POINTS_PIXELS = 0x100  # CAMD_POINTS_PIXELS, or-ed into camd_undistort_points' o
 CALIB_STATE_DOUBLES, CALIB_WORKSPACE_DOUBLES, CALIB_CANDIDATE_DOUBLES = 40, 136, 16
 (CALIB_DONE, CALIB_ACCEPT, CALIB_LAMBDA, CALIB_COST, CALIB_EVALUATIONS, CALIB_ITERATIONS, CALIB_STATUS, CALIB_CONVERGED, CALIB_K,
  CALIB_DK, CALIB_MASK, CALIB_SOLVED, CALIB_PIVOT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 17, 26, 35, 36
+# camd_stereo_*: the same (CAMD_STEREO_*)
+STEREO_STATE_DOUBLES, STEREO_WORKSPACE_DOUBLES, STEREO_CANDIDATE_DOUBLES, STEREO_PARTIAL_DOUBLES = 40, 91, 16, 36
+(STEREO_DONE, STEREO_ACCEPT, STEREO_LAMBDA, STEREO_COST, STEREO_EVALUATIONS, STEREO_ITERATIONS, STEREO_STATUS, STEREO_CONVERGED,
+ STEREO_RIG, STEREO_STEP, STEREO_CANDIDATE, STEREO_SOLVED, STEREO_PIVOT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 20, 26, 38, 39
 
 
 class SgbmParams(ctypes.Structure):
@@ -68,6 +72,13 @@ class PnpPoints(ctypes.Structure):  # camd_pnp_points
     _fields_ = [("object", c_void_p), ("image", c_void_p), ("start", c_void_p), ("object_rows", ctypes.c_ulonglong),
                 ("image_rows", ctypes.c_ulonglong), ("object_type", c_int), ("image_type", c_int), ("object_stride", c_int),
                 ("image_stride", c_int), ("object_shared", c_int), ("frames", c_int)]
+
+
+class StereoRig(ctypes.Structure):  # camd_stereo_rig
+    _fields_ = [("points1", PnpPoints), ("points2", PnpPoints), ("K1", c_void_p), ("dist1", c_void_p), ("K2", c_void_p),
+                ("dist2", c_void_p), ("used", c_void_p), ("state", c_void_p), ("poses", c_void_p), ("candidate", c_void_p),
+                ("workspace", c_void_p), ("partials", c_void_p), ("frame_error", c_void_p), ("ndist1", c_int), ("ndist2", c_int),
+                ("used_n", c_int), ("reserved", c_int)]
 
 
 # name -> (restype, argtypes); every symbol include/calibrating_amd.h declares
@@ -203,6 +214,9 @@ SIGNATURES = {
     "camd_calib_step": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_calib_finish": (c_int, [ctypes.POINTER(PnpPoints), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_calib_read": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "camd_stereo_linearise": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
+    "camd_stereo_step": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
+    "camd_stereo_finish": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

@@ -8,7 +8,7 @@
 // the workspace.  The block is solved from the reduced system
 //   sum_i (C_i - B_i^T (A_i + l diag A_i)^-1 B_i) + l diag sum_i C_i,
 // and every frame's step follows by back-substitution.  Damping and stopping are pnp_common.hpp's one rule (LM_*), which
-// pnp.hip follows too; the acceptance of a step is this file's own (CALIB_COST_RESOLUTION).
+// pnp.hip follows too; the acceptance of a step is lm_better, shared with stereo_calibrate.hip.
 //
 // Kernels.  k_calib_linearise and k_calib_evaluate sum over a frame's points: one wavefront per frame, four frames per
 // workgroup, no workgroup barrier, the butterfly of pnp_common.hpp.  136 accumulators do not fit beside the Jacobian, so
@@ -23,11 +23,6 @@
 namespace camd {
 
 constexpr int CALIB_MAX_EVALUATIONS = 100;      // every case of tests/calibrate_cases.py ends below half of it
-// A candidate is accepted when its cost is lower, or higher by no more than the rounding of the sums can explain (64 ulp
-// of the cost).  Near the minimum the cost is flat to rounding while the step is still accurate (it comes from the
-// gradient); rejecting such steps by the noise of `c2 < c` would leave the parameters about sqrt(eps c / h) from the
-// minimum along the flattest direction h, 1e-7 .. 1e-6 px in K, and dependent on the order of the sums.
-constexpr double CALIB_COST_RESOLUTION = 64 * 0x1p-52;
 constexpr int CALIB_WS = CAMD_CALIB_WORKSPACE_DOUBLES, CALIB_CAND = CAMD_CALIB_CANDIDATE_DOUBLES;
 // the workspace of one frame
 enum { WS_A = 0, WS_B = 21, WS_C = 75, WS_GP = 120, WS_GK = 126, WS_COST = 135 };
@@ -309,7 +304,7 @@ __global__ __launch_bounds__(64) void k_calib_update(CalibArgs a, int max_evalua
         step += dk[q] * dk[q], norm += k[q] * k[q];
     }
     const bool small = solved && lm_small(step, norm);
-    const bool better = uniform(solved && (c2 < c || c2 - c <= CALIB_COST_RESOLUTION * c));
+    const bool better = uniform(solved && lm_better(c2, c));
     if (better)
         for (int u = lane; u < a.used_n; u += 64)
             for (int q = 0; q < 12; q++) a.poses[(size_t)u * 12 + q] = a.cand[(size_t)u * CALIB_CAND + q];

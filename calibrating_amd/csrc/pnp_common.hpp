@@ -7,8 +7,9 @@
 //   damped, cholesky, cholesky_solve           (A + lambda diag A) x = b in registers
 //   unit_diagonal_pivot, SINGULAR_PIVOT        the rank test: the smallest pivot of A scaled to a unit diagonal
 //   LM_*, lm_small, lm_next, lm_stopped        the one Levenberg-Marquardt rule (damping, stopping); pose_norm2: its |p|^2
+//   lm_better                                  the joint solvers' acceptance: a lower cost, or one within the rounding of the sums
 //   rotate_left; null_vector, direct_linear_transform   R <- exp([w]x) R; the Hartley-normalised start (H or P)
-// Acceptance of a step is NOT here: pnp.hip takes a lower cost, calibrate.hip also one within the rounding of its sums.
+// pnp.hip accepts a step by the bare comparison of the costs; calibrate.hip and stereo_calibrate.hip by lm_better.
 #pragma once
 
 #include <climits>
@@ -28,6 +29,13 @@ constexpr double LM_LAMBDA_MIN = 1e-12, LM_LAMBDA_MAX = 1e12, LM_EPS = 0x1p-52; 
 __device__ __forceinline__ bool lm_small(double step2, double norm2) { return sqrt(step2) < LM_EPS * (sqrt(norm2) + LM_EPS); }
 __device__ __forceinline__ double lm_next(double lambda, bool better) { return better ? lambda * LM_LAMBDA_DOWN : lambda * LM_LAMBDA_UP; }
 __device__ __forceinline__ bool lm_stopped(bool small, double lambda) { return small || lambda < LM_LAMBDA_MIN || lambda > LM_LAMBDA_MAX; }
+// The acceptance of a step of the JOINT solvers (calibrate.hip, stereo_calibrate.hip): a candidate is taken when its cost
+// is lower, or higher by no more than the rounding of the sums can explain (64 ulp of the cost).  Near the minimum the
+// cost is flat to rounding while the step is still accurate (it comes from the gradient); rejecting such steps by the
+// noise of `c2 < c` would leave the parameters about sqrt(eps c / h) from the minimum along the flattest direction h,
+// 1e-7 .. 1e-6 px in K, and dependent on the order of the sums.  (pnp.hip takes the bare comparison.)
+constexpr double LM_COST_RESOLUTION = 64 * 0x1p-52;
+__device__ __forceinline__ bool lm_better(double c2, double c) { return c2 < c || c2 - c <= LM_COST_RESOLUTION * c; }
 // |p|^2 of one pose: R's Frobenius norm and t
 __device__ __forceinline__ double pose_norm2(const double* t) { return 3. + t[0] * t[0] + t[1] * t[1] + t[2] * t[2]; }
 

@@ -14,8 +14,10 @@ the bodies are this package's own: rig geometry lives in ``geometry.py`` as pure
   unrectify_depth                     :415-428   -> imgproc.unrectify_depth
   undistort_img                       :430-431   -> imgproc.remap_fixed_bilinear
   distort_depth                       :433-464   -> imgproc.distort_index_map (once per rig) + imgproc.distort_depth
-Extrinsic calibration (cv2.stereoCalibrate, :95-123) is outside the hot path: construct the rig from
-known {K, D, R, t} via ``Stereo.load`` or the R/t keywords.
+  get_conjoint_points                 :55-93     (host)
+  get_R_t_by_stereo_calibrate         :95-123    -> stereo_calibrate.stereo_calibrate
+``Stereo(cam1, cam2)`` calibrates the rig from the cameras' detections; a rig with known {K, D, R, t} comes from
+``Stereo.load`` or the R/t keywords.
 
 NumPy in -> NumPy out (one H2D copy of the pair, one D2H copy per result entry); torch CUDA tensors
 in -> torch tensors out, zero-copy.
@@ -61,17 +63,62 @@ class Stereo:
         self.K_target = K_target
         if cam1 is None:
             return
-        if R is None or t is None:
-            raise NotImplementedError(
-                "extrinsic calibration from board detections (cv2.stereoCalibrate) is outside the MI355X "
-                "stereo-depth path; pass R= and t=, or use Stereo.load(dict(R=..., t=..., cam1=..., cam2=...))")
         self.cam1, self.cam2 = cam1, cam2
-        self._set_pose(R, t)
+        if R is None or t is None:
+            # (the reference raises AssertionError where no frame is shared; this package keeps its own NotImplementedError,
+            # raised before anything touches the device or the shared library)
+            if not self.get_conjoint_points()[0]:
+                raise NotImplementedError(
+                    "extrinsic calibration from board detections (cv2.stereoCalibrate) needs frames in which both cameras "
+                    "detected the board: pass R= and t=, use Stereo.load(dict(R=..., t=..., cam1=..., cam2=...)), or pass "
+                    "cameras that carry detections (Cam.from_detections) with a common key")
+            self.get_R_t_by_stereo_calibrate()
+        else:
+            self._set_pose(R, t)
         self._get_undistort_rectify_map()
 
     def _set_pose(self, R, t):
         self.R = np.float64(R)
         self.t = np.float64(t).reshape(3, 1)
+
+    # ---- the rig from board detections (stereo_camera.py:55-123; csrc/stereo_calibrate.hip) ----------
+    def get_conjoint_points(self):
+        """``(image_points1, image_points2, object_points)``: one array per frame both cameras detected the board in (the
+        reference's method, on the host).  Detections stored as arrays: the keys of ``cam1.valid_keys_intersection(cam2)``.
+        Detections stored as id -> points dicts (markers): per key of camera 1, the ids both cameras saw there,
+        concatenated in camera 1's order; a key without a common id is left out.  A key must also hold ``object_points`` in
+        camera 1.  Without any detection in camera 1 the lists are empty (the reference asserts)."""
+        cam1, cam2 = self.cam1, self.cam2
+        first = next((d["image_points"] for d in cam1.values() if isinstance(d, dict) and "image_points" in d), None)
+        uvs1, uvs2, xyzs = [], [], []
+        if isinstance(first, np.ndarray):
+            keys = [k for k in cam1.valid_keys_intersection(cam2) if "object_points" in cam1[k]]
+            uvs1, uvs2 = [cam1[k]["image_points"] for k in keys], [cam2[k]["image_points"] for k in keys]
+            xyzs = [cam1[k]["object_points"] for k in keys]
+        elif isinstance(first, dict):
+            for key in cam1:
+                a, b, c = [], [], []
+                seen2 = cam2[key].get("image_points", {}) if key in cam2 else {}
+                for i in cam1[key].get("image_points", {}) if "object_points" in cam1[key] else ():
+                    if i in seen2:
+                        a.append(cam1[key]["image_points"][i]), b.append(seen2[i]), c.append(cam1[key]["object_points"][i])
+                if a:
+                    uvs1.append(np.concatenate(a, 0)), uvs2.append(np.concatenate(b, 0)), xyzs.append(np.concatenate(c, 0))
+        return uvs1, uvs2, xyzs
+
+    def get_R_t_by_stereo_calibrate(self):
+        """``cv2.stereoCalibrate(..., flags=CALIB_FIX_INTRINSIC)`` over ``get_conjoint_points()`` with the two cameras' K and
+        D, on the GPU (``stereo_calibrate.stereo_calibrate``): sets ``R``, ``t`` (3, 1) and ``retval``.  A rig that cannot be
+        solved raises ``ValueError`` and sets nothing."""
+        from .stereo_calibrate import CALIB_FIX_INTRINSIC, stereo_calibrate  # (the package's attribute of that name is the function)
+        uvs1, uvs2, xyzs = self.get_conjoint_points()
+        flat = lambda arrays, width: np.concatenate([np.asarray(a, np.float64).reshape(-1, width) for a in arrays])  # noqa: E731
+        counts = [len(np.asarray(a).reshape(-1, 2)) for a in uvs1]
+        res = stereo_calibrate(flat(xyzs, 3), flat(uvs1, 2), flat(uvs2, 2), self.cam1.K, self.cam1.D, self.cam2.K, self.cam2.D,
+                               counts=counts, flags=CALIB_FIX_INTRINSIC)
+        self._set_pose(res["R"], res["t"])
+        self.retval = res["retval"]
+        return self
 
     # ---- init-time geometry (host, 3x3 algebra only) -----------------------------------------------
     def stereo_recitfy(self):

@@ -646,6 +646,63 @@ int camd_calib_finish(const camd_pnp_points* points, const int* used, int used_n
 /* The first `count` doubles of state -> out (host), after everything queued before; returns when they have arrived.  */
 int camd_calib_read(const double* state, int count, double* out, void* queue);
 
+/* ---- a rig's R, t and the board's pose in every frame from the points both cameras detected (csrc/stereo_calibrate.hip) ----
+ * replaces cv2.stereoCalibrate(..., flags=CALIB_FIX_INTRINSIC) of Stereo.get_R_t_by_stereo_calibrate
+ * (stereo_camera.py:95-123): UNPINNED against cv2.  Both cameras' K and D stay fixed.  A float64
+ * Levenberg-Marquardt on raw pixels over the six unknowns of the rig (x2 = R x1 + t; R <- exp([w]x) R, t <- t + d) and
+ * six per frame (the board in camera 1, camd_pnp_refine's local pose update), solved through the Schur complement on the
+ * rig's block; damping, stopping and acceptance as in camd_calib_step.  The frames of the joint problem are `used`, as
+ * in camd_calib_*.  The sums over frames have two levels of fixed order -- a lane per frame and a butterfly over the 64
+ * frames of a workgroup, then one wavefront over the workgroups' partials in rising order --, without atomics: the same
+ * input gives the same bits on every run.
+ *
+ * points1 / points2: the same object rows, start and frames; `image` (with its type and stride) is camera 1's / camera
+ * 2's.  K, dist, ndist of each camera as in camd_project_points (host).  Device arrays: used (used_n int32, rising),
+ * state (CAMD_STEREO_STATE_DOUBLES), poses (used_n x 12: R_i, t_i), candidate (used_n x CAMD_STEREO_CANDIDATE_DOUBLES),
+ * workspace (used_n x CAMD_STEREO_WORKSPACE_DOUBLES), partials (ceil(used_n / 64) x CAMD_STEREO_PARTIAL_DOUBLES),
+ * frame_error (used_n).
+ *
+ * state, written by the caller before the first call: [CAMD_STEREO_LAMBDA] = 1e-3, [CAMD_STEREO_RIG .. + 12) = R (9,
+ * row-major), t (3) of the start, everything else 0.  Its first two places are camd_calib's and camd_calib_read reads it:
+ * after camd_stereo_step [CAMD_STEREO_DONE] != 0 when the iteration has ended (stopped by the rule, or 100 evaluations),
+ * [CAMD_STEREO_ACCEPT] != 0 when the step was taken (then the next step needs camd_stereo_linearise first, which also
+ * moves every frame's candidate into `poses`).  After camd_stereo_finish: [CAMD_STEREO_STATUS] 0 ok / 3 singular (a pivot
+ * of the unit-diagonal reduced matrix below 1e-10) or not converged at the cap, [CAMD_STEREO_COST] the sum of squared
+ * residuals of both cameras, [CAMD_STEREO_RIG .. + 12) the result.                                                   */
+#define CAMD_STEREO_STATE_DOUBLES 40
+#define CAMD_STEREO_WORKSPACE_DOUBLES 91 /* per used frame: A 21, B 36, C 21, gp 6, gr 6, c 1 */
+#define CAMD_STEREO_CANDIDATE_DOUBLES 16 /* per used frame: R 9, t 3, cost, |step|^2, |pose|^2, unused */
+#define CAMD_STEREO_PARTIAL_DOUBLES 36   /* per 64 used frames: S 21, g 6, diag C 6, cost; frames that did not factor; unused */
+enum {
+    CAMD_STEREO_DONE = 0, CAMD_STEREO_ACCEPT = 1, CAMD_STEREO_LAMBDA = 2, CAMD_STEREO_COST = 3, CAMD_STEREO_EVALUATIONS = 4,
+    CAMD_STEREO_ITERATIONS = 5, CAMD_STEREO_STATUS = 6, CAMD_STEREO_CONVERGED = 7, CAMD_STEREO_RIG = 8, CAMD_STEREO_STEP = 20,
+    CAMD_STEREO_CANDIDATE = 26, CAMD_STEREO_SOLVED = 38, CAMD_STEREO_PIVOT = 39
+};
+typedef struct camd_stereo_rig {
+    camd_pnp_points points1, points2;
+    const double* K1;     /* 9 host doubles */
+    const double* dist1;  /* ndist1 host doubles */
+    const double* K2;
+    const double* dist2;
+    const int* used;
+    double* state;
+    double* poses;
+    double* candidate;
+    double* workspace;
+    double* partials;
+    double* frame_error;
+    int ndist1, ndist2, used_n, reserved;
+} camd_stereo_rig;
+/* The sums of every used frame at state's rig and `poses` -> workspace; needs poses and candidate.                 */
+int camd_stereo_linearise(const camd_stereo_rig* rig, void* queue);
+/* One evaluation at state's lambda: every frame's reduced contribution and the partials; the rig's step and candidate;
+ * every frame's step, candidate pose and cost in both cameras; accept (state's rig takes the candidate) or reject;
+ * lambda; the stop flags.  Needs poses, candidate and partials.                                                     */
+int camd_stereo_step(const camd_stereo_rig* rig, void* queue);
+/* After the last linearisation: the status, the cost, and frame_error[u] = sqrt(sum (|r1|^2 + |r2|^2) / 2n) of every
+ * used frame.  Needs partials and frame_error.                                                                     */
+int camd_stereo_finish(const camd_stereo_rig* rig, void* queue);
+
 #ifdef __cplusplus
 }
 #endif
