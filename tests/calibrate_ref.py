@@ -80,14 +80,15 @@ def frame_terms(R, t, obj, uv, k):
     return r.reshape(-1), Jp, Jk
 
 
+def blocks(r, Jp, Jk):
+    """(A, B, C, gp, gk, c): the sums over one frame's residuals and Jacobians"""
+    outer = lambda a, b: (a[:, :, None] * b[:, None, :]).sum(0)  # noqa: E731
+    return (outer(Jp, Jp), outer(Jp, Jk), outer(Jk, Jk), (Jp * r[:, None]).sum(0), (Jk * r[:, None]).sum(0), (r * r).sum())
+
+
 def linearise(poses, objs, uvs, k):
     """per frame (A, B, C, gp, gk, c)"""
-    out = []
-    for (R, t), obj, uv in zip(poses, objs, uvs):
-        r, Jp, Jk = frame_terms(R, t, obj, uv, k)
-        outer = lambda a, b: (a[:, :, None] * b[:, None, :]).sum(0)  # noqa: E731
-        out.append((outer(Jp, Jp), outer(Jp, Jk), outer(Jk, Jk), (Jp * r[:, None]).sum(0), (Jk * r[:, None]).sum(0), (r * r).sum()))
-    return out
+    return [blocks(*frame_terms(R, t, obj, uv, k)) for (R, t), obj, uv in zip(poses, objs, uvs)]
 
 
 def cost_of(poses, objs, uvs, k):
@@ -125,6 +126,46 @@ def mask_system(S, g, free):
     S[fixed, fixed] = 1
     g[fixed] = 0
     return S, g
+
+
+def shared_step(lin, lam, free):
+    """(dk, the per-frame factors) of one evaluation at lambda, as ``joint`` solves it; None where nothing can be solved"""
+    red = reduced(lin, lam, free)
+    if red is None:
+        return None
+    S, g, dC, Ls = red
+    S, g = mask_system(S + lam * np.diag(dC), g, free)
+    L = _chol(S)
+    if L is None:
+        return None
+    dk = _solve(L, -g)
+    return (dk, Ls) if np.isfinite(dk).all() else None
+
+
+def candidates(lin, Ls, poses, objs, uvs, k, dk):
+    """One evaluation's intermediate values after the block's step, as ``joint`` forms them -> dict(k2, poses2, cost2,
+    step2, norm2: per frame, cost, accept)."""
+    poses2, step2, norm2 = [], [], []
+    for (A, B, C, gp, gk, c), Lf, (R, t) in zip(lin, Ls, poses):
+        d = _solve(Lf, -(gp + B @ dk))
+        poses2.append((pnp_ref.rotate_left(d[:3], R), t + d[3:]))
+        step2.append((d * d).sum())
+        norm2.append(3.0 + (t * t).sum())
+    k2 = k + dk
+    cost2 = cost_of(poses2, objs, uvs, k2)
+    c2, c = sum(cost2), sum(l[5] for l in lin)
+    return dict(k2=k2, poses2=poses2, cost2=cost2, step2=step2, norm2=norm2, cost=c,
+                accept=bool(c2 < c or c2 - c <= COST_RESOLUTION * c))
+
+
+def final_stage(lin, free):
+    """(the smallest pivot of the undamped reduced matrix scaled to a unit diagonal, NaN where it does not factor; the cost),
+    as ``joint`` ends"""
+    S = reduced(lin, 0.0, free)[0]
+    with np.errstate(all="ignore"):
+        s = 1.0 / np.sqrt(np.diag(S))
+        L = _chol(mask_system(S * s[:, None] * s[None, :], np.zeros(9), free)[0])
+    return (np.nan if L is None else float((np.diag(L) ** 2).min())), sum(l[5] for l in lin)
 
 
 def joint(objs, uvs, k0, poses0, flags):

@@ -56,15 +56,16 @@ def finite_difference_blocks(Ri, ti, R, t, obj, uv1, uv2, cams, h=FD_STEP):
     return J[:, :6], J[:, 6:]
 
 
+def blocks(r1, J1, r2, Jf, Jr):
+    """(A, B, C, gp, gr, c): the sums over one frame's residuals and Jacobians"""
+    outer = lambda a, b: (a[:, :, None] * b[:, None, :]).sum(0)  # noqa: E731
+    return (outer(J1, J1) + outer(Jf, Jf), outer(Jf, Jr), outer(Jr, Jr), (J1 * r1[:, None]).sum(0) + (Jf * r2[:, None]).sum(0),
+            (Jr * r2[:, None]).sum(0), (r1 * r1).sum() + (r2 * r2).sum())
+
+
 def linearise(poses, R, t, objs, uv1s, uv2s, cams):
     """per frame (A, B, C, gp, gr, c)"""
-    out = []
-    outer = lambda a, b: (a[:, :, None] * b[:, None, :]).sum(0)  # noqa: E731
-    for (Ri, ti), obj, u1, u2 in zip(poses, objs, uv1s, uv2s):
-        r1, J1, r2, Jf, Jr = frame_terms(Ri, ti, R, t, obj, u1, u2, cams)
-        out.append((outer(J1, J1) + outer(Jf, Jf), outer(Jf, Jr), outer(Jr, Jr), (J1 * r1[:, None]).sum(0) + (Jf * r2[:, None]).sum(0),
-                    (Jr * r2[:, None]).sum(0), (r1 * r1).sum() + (r2 * r2).sum()))
-    return out
+    return [blocks(*frame_terms(Ri, ti, R, t, obj, u1, u2, cams)) for (Ri, ti), obj, u1, u2 in zip(poses, objs, uv1s, uv2s)]
 
 
 def _solve(L, b):
@@ -83,6 +84,47 @@ def reduced(lin, lam):
         g = g + (gr - B.T @ _solve(L, gp))
         dC = dC + np.diag(C)
     return S, g, dC, Ls
+
+
+def shared_step(lin, lam):
+    """(the rig's step, the per-frame factors) of one evaluation at lambda, as ``joint`` solves it; None where nothing can
+    be solved"""
+    red = reduced(lin, lam)
+    if red is None:
+        return None
+    S, g, dC, Ls = red
+    L = pnp_ref._cholesky(S + lam * np.diag(dC))
+    if L is None:
+        return None
+    dr = _solve(L, -g)
+    return (dr, Ls) if np.isfinite(dr).all() else None
+
+
+def candidates(lin, Ls, poses, R, t, objs, uv1s, uv2s, cams, dr):
+    """One evaluation's intermediate values after the rig's step, as ``joint`` forms them -> dict(R2, t2, poses2, cost2,
+    step2, norm2: per frame, cost, accept)."""
+    R2, t2 = pnp_ref.rotate_left(dr[:3], R), t + dr[3:]
+    poses2, step2, norm2, cost2 = [], [], [], []
+    for (A, B, C, gp, gr, c), Lf, (Ri, ti), obj, u1, u2 in zip(lin, Ls, poses, objs, uv1s, uv2s):
+        d = _solve(Lf, -(gp + B @ dr))
+        poses2.append((pnp_ref.rotate_left(d[:3], Ri), ti + d[3:]))
+        step2.append((d * d).sum())
+        norm2.append(3.0 + (ti * ti).sum())
+        rr = residuals(poses2[-1][0], poses2[-1][1], R2, t2, obj, u1, u2, cams)
+        cost2.append((rr * rr).sum())
+    c2, c = sum(cost2), sum(l[5] for l in lin)
+    return dict(R2=R2, t2=t2, poses2=poses2, cost2=cost2, step2=step2, norm2=norm2, cost=c,
+                accept=bool(c2 < c or c2 - c <= COST_RESOLUTION * c))
+
+
+def final_stage(lin):
+    """(the smallest pivot of the undamped reduced matrix scaled to a unit diagonal, NaN where it does not factor; the cost),
+    as ``joint`` ends"""
+    S = reduced(lin, 0.0)[0]
+    with np.errstate(all="ignore"):
+        s = 1.0 / np.sqrt(np.diag(S))
+        L = pnp_ref._cholesky(S * s[:, None] * s[None, :])
+    return (np.nan if L is None else float((np.diag(L) ** 2).min())), sum(l[5] for l in lin)
 
 
 def joint(objs, uv1s, uv2s, cams, poses0, R0, t0):
