@@ -217,6 +217,10 @@ SIGNATURES = {
     "camd_stereo_linearise": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
     "camd_stereo_step": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
     "camd_stereo_finish": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
+    "camd_corner_sub_pix": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int,
+                                    c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_bgr_to_gray_u8": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_int,
+                                    c_int, c_int, c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

@@ -320,3 +320,198 @@ def distort_depth(depth, src_index):
         call("camd_distort_depth", z.device, z.data_ptr(), z.element_size(), w, h, idx.data_ptr(), out.data_ptr(),
              z.numel() // (h * w), what="distort_depth")
     return to_caller(out, was_np)
+
+
+# ---- gray images and corners refined to sub-pixel (boards.py:156-172; csrc/subpix.hip) ----
+# cv2's fixed-point weights of B, G, R and their shift, by the bits of the fixed point (recalled,
+# unpinned).  OpenCV 4.x: 15 bits, older releases: 14.  GRAY_BITS is the switch.
+GRAY_WEIGHTS = {15: (3735, 19235, 9798), 14: (1868, 9617, 4899)}
+GRAY_BITS = 15
+SUBPIX_SINGULAR, SUBPIX_LEFT_IMAGE, SUBPIX_REVERTED, SUBPIX_BAD_START = 1, 2, 4, 8  # bits of corner_sub_pix's status
+SUBPIX_MAX_ITERATIONS = 100
+TERM_CRITERIA_COUNT, TERM_CRITERIA_EPS = 1, 2  # cv2.TERM_CRITERIA_MAX_ITER, cv2.TERM_CRITERIA_EPS
+
+
+def _image_rows(t, channels):
+    """(batch, h, w, pitch, stride) in bytes of a uint8 CUDA tensor (h, w[, 3]) or (f, h, w[, 3]) whose pixels are
+    contiguous; rows and images may be apart by more than their bytes (a crop, a slice of a wider batch)."""
+    lead = t.dim() - (3 if channels == 3 else 2)
+    h, w = int(t.shape[lead]), int(t.shape[lead + 1])
+    f = int(t.shape[0]) if lead else 1
+    st = t.stride()
+    tight = (st[-1] == 1 and st[-2] == 3) if channels == 3 else st[-1] == 1
+    pitch = int(st[lead]) if h > 1 else w * channels
+    stride = int(st[0]) if lead and f > 1 else h * pitch
+    if not tight or pitch < w * channels or stride < (h - 1) * pitch + w * channels:
+        t = t.contiguous()
+        pitch, stride = w * channels, h * w * channels
+    return t, f, h, w, pitch, stride
+
+
+def _check_image(img, what):
+    check_array(img, what)
+    if dtype_name(img) != "uint8":
+        raise ValueError("%s must be uint8, got %s" % (what, img.dtype))
+
+
+def _to_image(img):
+    """The CUDA tensor of an image: an ndarray is uploaded, a tensor is taken as it is (pitched views are read in place)."""
+    import torch
+    if is_np(img):
+        _native.require_device()
+        return torch.from_numpy(np.ascontiguousarray(img)).cuda()
+    return img
+
+
+def cvt_gray(img, code="bgr"):
+    """cv2.cvtColor(img, cv2.COLOR_BGR2GRAY) (``code="bgr"``) or COLOR_RGB2GRAY (``"rgb"``) on uint8, on the GPU:
+    (h, w, 3) or (f, h, w, 3) -> (h, w) or (f, h, w).  The first channel gets blue's weight with "bgr" and red's with
+    "rgb"; the reference hands an RGB image to COLOR_BGR2GRAY (boards.py:159), which ``Chessboard`` repeats.  Weights:
+    ``GRAY_WEIGHTS[GRAY_BITS]`` (U32).  A tensor whose rows or images are apart (a crop) is read in place."""
+    import torch
+    _check_image(img, "img")
+    if code not in ("bgr", "rgb"):
+        raise ValueError("code must be 'bgr' or 'rgb', got %r" % (code,))
+    if img.ndim not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError("img must be (h, w, 3) or (f, h, w, 3), got %s" % (tuple(img.shape),))
+    if 0 in tuple(img.shape):
+        raise ValueError("img is empty: %s" % (tuple(img.shape),))
+    was_np = is_np(img)
+    t, f, h, w, pitch, stride = _image_rows(_to_image(img), 3)
+    by, gy, ry = GRAY_WEIGHTS[GRAY_BITS]
+    k = (by, gy, ry) if code == "bgr" else (ry, gy, by)
+    dst = torch.empty((f, h, w), dtype=torch.uint8, device=t.device)
+    call("camd_bgr_to_gray_u8", t.device, t.data_ptr(), w, h, pitch, stride, dst.data_ptr(), w, h * w, f, k[0], k[1], k[2],
+         GRAY_BITS, what="cvt_gray")
+    return to_caller(dst if img.ndim == 4 else dst[0], was_np)
+
+
+def sub_pix_mask(win, zero_zone=(-1, -1)):
+    """cornerSubPix's window weights, (2 win_h + 1, 2 win_w + 1) float32, made on the host: row i, column j holds
+    (float)(vy * exp(-x^2)) with y = (float)(i - win_h) / win_h, vy = exp(-y^2) and x alike, all float32 (each exp is
+    the float64 one rounded to float32: a correctly rounded expf); zero over the zero zone when ``zero_zone >= 0`` and
+    ``2 zero_zone + 1 < 2 win + 1`` on both axes."""
+    ww, wh = int(win[0]), int(win[1])
+    if ww <= 0 or wh <= 0:
+        raise ValueError("win must be a pair of positive half-sizes, got %r" % (win,))
+
+    def axis(n):
+        v = (np.arange(2 * n + 1) - n).astype(np.float32) / np.float32(n)
+        return np.exp(-(v * v).astype(np.float64)).astype(np.float32)
+    mask = (axis(wh)[:, None] * axis(ww)[None, :]).astype(np.float32)
+    zx, zy = int(zero_zone[0]), int(zero_zone[1])
+    if zx >= 0 and zy >= 0 and 2 * zx + 1 < 2 * ww + 1 and 2 * zy + 1 < 2 * wh + 1:
+        mask[wh - zy:wh + zy + 1, ww - zx:ww + zx + 1] = 0
+    return mask
+
+
+_MASKS = {}  # (win, zero_zone, device) -> the mask on that device: a tracking loop uploads it once, not once per frame
+
+
+def _device_mask(win, zero_zone, device):
+    import torch
+    key = (win, zero_zone, str(device))
+    if key not in _MASKS:
+        if len(_MASKS) >= 64:  # (a caller that sweeps windows: start again rather than grow)
+            _MASKS.clear()
+        _MASKS[key] = torch.from_numpy(sub_pix_mask(win, zero_zone)).to(device)
+    return _MASKS[key]
+
+
+def sub_pix_criteria(criteria):
+    """(max_iters, squared eps) of cornerSubPix's termination criteria: ``(count, eps)`` -- either may be None -- or cv2's
+    ``(type, count, eps)``.  max_iters = clamp(count, 1, 100) when a count is carried, else 100; eps = max(eps, 0)^2 when
+    an epsilon is carried, else 0."""
+    c = tuple(criteria)
+    if len(c) == 3:
+        kind = int(c[0])
+        if kind & ~(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS) or not kind:
+            raise ValueError("criteria type must be TERM_CRITERIA_COUNT (1), TERM_CRITERIA_EPS (2) or both, got %r" % (c[0],))
+        count = c[1] if kind & TERM_CRITERIA_COUNT else None
+        eps = c[2] if kind & TERM_CRITERIA_EPS else None
+    elif len(c) == 2:
+        count, eps = c
+    else:
+        raise ValueError("criteria must be (count, eps) or cv2's (type, count, eps), got %r" % (criteria,))
+    max_iters = SUBPIX_MAX_ITERATIONS if count is None else min(max(int(count), 1), SUBPIX_MAX_ITERATIONS)
+    eps = 0.0 if eps is None else max(float(eps), 0.0)
+    if eps != eps:
+        raise ValueError("criteria: eps is NaN")
+    return max_iters, eps * eps
+
+
+def _corner_layout(corners, counts, frames):
+    """(rows (N, 2) view, lengths or None for a dense batch, the shape the result takes)."""
+    shape = tuple(corners.shape)
+    if counts is not None:
+        lengths = np.asarray(counts)
+        if corners.ndim != 2 or shape[1] != 2:
+            raise ValueError("with counts, corners are ragged rows (N, 2), got %s" % (shape,))
+        if lengths.ndim != 1 or lengths.dtype.kind not in "iu" or (lengths < 0).any() or len(lengths) != frames:
+            raise ValueError("counts must be %d non-negative integers, one per image" % frames)
+        if int(lengths.sum()) != shape[0]:
+            raise ValueError("counts sum to %d rows, corners have %d" % (lengths.sum(), shape[0]))
+        return lengths.astype(np.int64)
+    if corners.ndim == 3 and shape[2] == 2 and shape[0] == frames and (frames > 1 or shape[1] != 1):
+        pass  # (f, n, 2); with one image, (n, 1, 2) is cv2's layout of n corners
+    elif corners.ndim == 2 and shape[1] == 2 or corners.ndim == 3 and shape[1:] == (1, 2):
+        if frames != 1:
+            raise ValueError("corners %s are one frame's; %d images need (f, n, 2) or counts" % (shape, frames))
+    elif corners.ndim == 3 and shape[2] == 2:
+        raise ValueError("corners %s do not match %d image(s)" % (shape, frames))
+    else:
+        raise ValueError("corners must be (n, 2), (n, 1, 2), (f, n, 2) or ragged (N, 2) with counts, got %s" % (shape,))
+    return None
+
+
+def corner_sub_pix(images, corners, win=(4, 4), zero_zone=(-1, -1), criteria=(30, 0.01), counts=None, return_info=False):
+    """cv2.cornerSubPix(gray, corners, win, zero_zone, criteria) for every corner of every frame in one launch
+    (boards.py:163-169; UNPINNED against cv2) -> the refined corners, in the shape and type
+    they came in; they are not changed in place.
+
+    ``images``: uint8 gray (h, w) / (f, h, w), or colour (h, w, 3) / (f, h, w, 3), which goes through
+    ``cvt_gray(code="bgr")`` first.  ``corners``: float32 or float64, (n, 2) or cv2's (n, 1, 2) for one image,
+    (f, n, 2) for f, or ragged rows (N, 2) with ``counts`` (f lengths; a frame may have none).  NumPy in -> NumPy out; CUDA
+    tensors stay on their device and the current stream.  ``criteria``: ``(count, eps)`` or cv2's ``(type, count, eps)``
+    (``sub_pix_criteria``).  ``return_info``: ``(corners, iterations, status)``, int32 per corner in the corners' leading
+    shape; status bits: 1 singular window, 2 the iterate left the image, 4 it drifted further than the window and the
+    start is returned, 8 the start is not finite or not inside the image and is returned as it came (cv2 asserts)."""
+    import torch
+    _check_image(images, "images")
+    check_array(corners, "corners")
+    if is_np(images) != is_np(corners):
+        raise TypeError("images and corners must both be NumPy arrays or both be CUDA tensors")
+    if dtype_name(corners) not in FLOAT_TYPES:
+        raise ValueError("corners must be float32 or float64, got %s" % corners.dtype)
+    colour = images.ndim in (3, 4) and images.shape[-1] == 3  # (no gray image is 3 wide: the smallest window needs 7)
+    if images.ndim not in (2, 3, 4) or (images.ndim == 4 and not colour):
+        raise ValueError("images must be (h, w), (f, h, w), (h, w, 3) or (f, h, w, 3), got %s" % (tuple(images.shape),))
+    frames = int(images.shape[0]) if images.ndim - (1 if colour else 0) == 3 else 1
+    lengths = _corner_layout(corners, counts, frames)
+    ww, wh = int(win[0]), int(win[1])
+    zone = (int(zero_zone[0]), int(zero_zone[1]))
+    if ww <= 0 or wh <= 0:
+        raise ValueError("win must be a pair of positive half-sizes, got %r" % (win,))
+    max_iters, eps = sub_pix_criteria(criteria)
+    was_np = is_np(images)
+    gray = cvt_gray(_to_image(images), "bgr") if colour else _to_image(images)
+    gray, f, h, w, pitch, stride = _image_rows(gray, 1)
+    if w < 2 * ww + 5 or h < 2 * wh + 5:
+        raise ValueError("a %d x %d image is smaller than the %d x %d a window of %r needs" % (w, h, 2 * ww + 5, 2 * wh + 5, (ww, wh)))
+    rows = to_device(corners, device=gray.device).reshape(-1, 2)
+    n = int(rows.shape[0])
+    out = torch.empty_like(rows)
+    iterations = torch.empty(n, dtype=torch.int32, device=gray.device)
+    status = torch.empty(n, dtype=torch.int32, device=gray.device)
+    start = None
+    if lengths is not None:
+        start = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(gray.device)
+    mask_t = _device_mask((ww, wh), zone, gray.device)
+    call("camd_corner_sub_pix", gray.device, gray.data_ptr(), w, h, pitch, stride, f, rows.data_ptr(), FLOAT_TYPES[dtype_name(rows)],
+         n, None if start is None else start.data_ptr(), ww, wh, mask_t.data_ptr(), max_iters, ctypes.c_double(eps),
+         out.data_ptr(), iterations.data_ptr(), status.data_ptr(), what="corner_sub_pix")
+    lead = tuple(corners.shape[:-1])
+    out = out.reshape(tuple(corners.shape))
+    if not return_info:
+        return to_caller(out, was_np)
+    return to_caller((out, iterations.reshape(lead), status.reshape(lead)), was_np)

@@ -703,6 +703,50 @@ int camd_stereo_step(const camd_stereo_rig* rig, void* queue);
  * used frame.  Needs partials and frame_error.                                                                     */
 int camd_stereo_finish(const camd_stereo_rig* rig, void* queue);
 
+/* ---- detected corners refined to sub-pixel, every corner of every frame in one launch (csrc/subpix.hip) ----
+ * replaces cv2.cornerSubPix(gray, corners, win, zero_zone, criteria) of Chessboard.find_image_points (boards.py:163-169):
+ * UNPINNED against cv2.  One wavefront per corner, four corners per workgroup, no workgroup
+ * barrier; a corner's outputs depend on its own start and its frame only, so they are the same bits alone and anywhere in
+ * a batch.
+ *
+ * gray: `frames` u8 images of w x h with the pitch / stride conventions of camd_remap_u8 (cn = 1).  corners: `rows` rows
+ * [x, y] of corner_type CAMD_VALUE_F64 / CAMD_VALUE_F32, contiguous.  start == NULL: dense, frame f owns rows
+ * f * (rows / frames) ... ; otherwise frames + 1 int64 ON THE DEVICE, rising, as camd_pnp_points.start: frame f owns rows
+ * start[f] .. start[f + 1] and may own none.  The start rows live on the device and are not checked by the host: a row
+ * that no frame owns (rows beyond start[frames], rows that do not rise) gets status bit 8, and rows that rise but are not
+ * the caller's split give a corner to another frame -- the frame index always stays below `frames`, so no memory beyond
+ * the images is read either way.  mask: (2 win_h + 1) * (2 win_w + 1) float32 weights ON THE DEVICE, made by
+ * the caller (row i, column j: exp(-y^2) exp(-x^2) with y = (i - win_h) / win_h, x alike, in float32, zero over the zero
+ * zone), so the kernel calls no exp.  max_iters 1 .. 100; eps >= 0 is the SQUARED step below which the iteration ends.
+ *
+ * Per corner, with cT = the start rounded to float32 and cI = cT:
+ *   patch  (2 win_w + 3) x (2 win_h + 3) float32 samples around cI: cx = cI.x - (pw - 1) * 0.5f, ix = floor(cx), a = cx - ix,
+ *          y alike with b; ((a11 p00 + a12 p01) + a21 p10) + a22 p11 with a11 = (1 - a)(1 - b), a12 = a (1 - b),
+ *          a21 = (1 - a) b, a22 = a b in float32; source coordinates clamped to the image
+ *   sums   in float64 over the window, pixel k = i * (2 win_w + 1) + j: tgx = right - left, tgy = lower - upper sample,
+ *          m = mask[k]; gxx = tgx tgx m, gxy = tgx tgy m, gyy = tgy tgy m; px = j - win_w, py = i - win_h;
+ *          a += gxx, b += gxy, c += gyy, bb1 += gxx px + gxy py, bb2 += gxy px + gyy py.  Pixel k belongs to lane
+ *          k % 64, a lane adds its pixels in rising k, the lanes' sums meet in a butterfly (xor 1, 2, ... 32)
+ *   solve  det = a c - b b; |det| <= DBL_EPSILON^2: stop (status bit 1).  scale = 1 / det;
+ *          cI2.x = (float)(cI.x + c scale bb1 - b scale bb2), cI2.y = (float)(cI.y - b scale bb1 + a scale bb2);
+ *          err = the squared float32 step, in float64; cI = cI2; outside [0, w) x [0, h): stop (bit 2)
+ *   loop   while (++iter < max_iters && err > eps)
+ *   revert |cI.x - cT.x| > win_w or |cI.y - cT.y| > win_h: the result is cT (bit 4)
+ * A start that is not finite, lies outside [0, w) x [0, h) or belongs to no frame: status bit 8, the corner comes back as
+ * it came and no pixel is read (cv2 asserts).  out: rows x 2 of corner_type (a float64 holds the float32 result exactly);
+ * iterations: the patches sampled; status: the bits above, 0 = converged or stopped at max_iters.
+ * CAMD_ERR_BAD_ARG: win <= 0, an image smaller than 2 win + 5 on a side (cv2's assertion); CAMD_ERR_UNSUPPORTED: a patch
+ * beyond 4096 floats (half-sizes up to (30, 30) fit).  queue: the HIP stream the launch is queued on.                  */
+int camd_corner_sub_pix(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, const void* corners,
+                        int corner_type, size_t rows, const long long* start, int win_w, int win_h, const float* mask,
+                        int max_iters, double eps, void* out, int* iterations, int* status, void* queue);
+/* replaces cv2.cvtColor(img, cv2.COLOR_BGR2GRAY) on u8 (boards.py:159): UNPINNED against cv2.
+ * dst = (c0 * k0 + c1 * k1 + c2 * k2 + (1 << (shift - 1))) >> shift per pixel of a three-channel image, c0 the first byte
+ * of the pixel; the weights are >= 0 and add up to 1 << shift (cv2 4.x, recalled: 3735, 19235, 9798 and 15 for B, G, R).
+ * Batched; pitch / stride conventions of camd_remap_u8 (src cn = 3, dst cn = 1).                                      */
+int camd_bgr_to_gray_u8(const uint8_t* src, int w, int h, size_t src_pitch, size_t src_stride, uint8_t* dst, size_t dst_pitch,
+                        size_t dst_stride, int batch, int k0, int k1, int k2, int shift, void* queue);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,37 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 
+def export_subpix(cv2, folder):
+    """cv2.cvtColor(COLOR_BGR2GRAY) and cv2.cornerSubPix on the rendered boards of tests/subpix_cases.py -> tests/golden/
+    cv2_subpix.npz (inputs and what cv2 returned), with a report against the NumPy restatement tests/subpix_ref.py and its
+    switches."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import subpix_cases as sc
+    import subpix_ref as ref
+    out = {"cv2_version": np.array(cv2.__version__)}
+    crit = (cv2.TERM_CRITERIA_EPS + cv2.TERM_CRITERIA_MAX_ITER, 30, 0.01)
+    for i in range(len(sc.POSES)):
+        f = sc.frame(i)
+        rgb = sc.colour(f["img"])
+        out["frame%d/rgb" % i], out["frame%d/seeds" % i] = rgb, f["seeds"]
+        out["frame%d/gray" % i] = cv2.cvtColor(rgb, cv2.COLOR_BGR2GRAY)
+        for bits in (15, 14):
+            d = np.abs(ref.gray(rgb, "bgr", bits).astype(int) - out["frame%d/gray" % i]).max()
+            print("  U32 frame %d: max |restatement(bits=%d) - cv2| = %d" % (i, bits, d))
+        for win in ((4, 4), (5, 3), (11, 11)):
+            for zone in ((-1, -1), (1, 1)):
+                c = f["seeds"].reshape(-1, 1, 2).copy()
+                cv2.cornerSubPix(np.ascontiguousarray(f["img"]), c, win, zone, crit)
+                out["frame%d/win%dx%d_zone%d" % (i, win[0], win[1], zone[0])] = c
+                for bilinear in ("four_tap", "running"):
+                    r = ref.corner_sub_pix(f["img"], f["seeds"], win, zone, crit, bilinear=bilinear)[0]
+                    print("  U31 frame %d win %s zone %s: max |restatement(%s) - cv2| = %g px" % (
+                        i, win, zone, bilinear, np.abs(r - c[:, 0]).max()))
+    path = os.path.join(folder, "cv2_subpix.npz")
+    np.savez_compressed(path, **out)
+    return path
+
+
 def main():
     try:
         import cv2
@@ -34,6 +65,8 @@ def main():
     for p in cases.write("cv2"):
         written.append(os.path.relpath(p, ROOT))
         print("wrote %s (%d KB)" % (written[-1], os.path.getsize(p) // 1024))
+    if hasattr(cv2, "cornerSubPix") and hasattr(cv2, "cvtColor"):  # (a stand-in module of the plumbing test has neither)
+        written.append(os.path.relpath(export_subpix(cv2, cases.HERE), ROOT))
     # report: the repo's oracle against what was just written
     try:
         worst = {}
