@@ -221,6 +221,10 @@ SIGNATURES = {
                                     c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_bgr_to_gray_u8": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p]),
+    "camd_chess_response": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_chess_peaks_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "camd_chess_peaks": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_chess_lattice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

@@ -5,7 +5,9 @@ reference runs ``cv2.cvtColor -> cv2.findChessboardCorners -> cv2.cornerSubPix``
 sub-pixel refinement run on the GPU (``imgproc.cvt_gray``, ``imgproc.corner_sub_pix``; csrc/subpix.hip) and the coarse
 guess comes from ``d["corners"]`` / ``d["coarse_corners"]``: any detector's corners, or the previous frame's pose projected
 with ``cam.project_points(board.object_points, T_prev)``.  ``findChessboardCorners`` itself, a heuristic quad search, is
-not provided.  The marker boards of the reference (ArUco, ChArUco) live in cv2.aruco and are not here.
+not provided; ``Chessboard(..., detector="chess")`` finds the guess with this package's own detector
+instead (``imgproc.find_chessboard_corners``; csrc/chessboard.hip), whose contract is not cv2's.
+The marker boards of the reference (ArUco, ChArUco) live in cv2.aruco and are not here.
 
 What a board computes on the host -- its object points, its printable image, the pixels of a region of interest -- is
 written from the behaviour the reference shows, which tests/golden/reference_boards.npz records bit for bit.
@@ -16,6 +18,7 @@ SUBPIX_WIN, SUBPIX_ZERO_ZONE = (4, 4), (-1, -1)  # boards.py:166-167
 SUBPIX_CRITERIA = (2 + 1, 30, 0.01)  # boards.py:161: cv2.TERM_CRITERIA_EPS + cv2.TERM_CRITERIA_MAX_ITER, 30, 0.01
 POINT_KEYS = ("image_points", "corners", "marker_corners")  # what a region of interest moves back into the whole image
 GUESS_KEYS = ("corners", "coarse_corners")
+DETECTORS = (None, "chess")
 
 NO_QUAD_SEARCH = ("Chessboard.find_image_points: no coarse corners -- the quad search of cv2.findChessboardCorners is not "
                   "provided.  Supply a start as d['corners'] or d['coarse_corners'], (n, 2) or (n, 1, 2): the corners of any "
@@ -102,11 +105,17 @@ class BaseBoard:
 
 
 class Chessboard(BaseBoard):
-    def __init__(self, checkboard=(11, 8), size_mm=25):
+    def __init__(self, checkboard=(11, 8), size_mm=25, detector=None):
         """``checkboard``: inner corners (across, down); ``size_mm``: a square's side.  ``object_points``: (n, 3) float32
-        metres in the board's plane, across fastest, the centre of the corners at the origin."""
+        metres in the board's plane, across fastest, the centre of the corners at the origin.  ``detector``: what
+        ``find_image_points`` does with a record that carries no coarse corners -- None refuses it, "chess" runs
+        ``imgproc.find_chessboard_corners``."""
+        if detector not in DETECTORS:
+            raise ValueError("detector must be one of %r, got %r" % (DETECTORS, detector))
         self.init_kwargs = dict(checkboard=checkboard, size_mm=size_mm)
-        self.checkboard, self.size_mm = checkboard, size_mm
+        if detector is not None:
+            self.init_kwargs["detector"] = detector
+        self.checkboard, self.size_mm, self.detector = checkboard, size_mm, detector
         across, down = checkboard
         col, row = np.meshgrid(np.arange(across), np.arange(down))  # (down, across): across runs fastest when flattened
         grid = np.zeros((across * down, 3), np.float32)
@@ -132,13 +141,19 @@ class Chessboard(BaseBoard):
         """boards.py:156-172 with the coarse guess taken from ``d["corners"]`` or ``d["coarse_corners"]``, (n, 2) or
         (n, 1, 2): gray conversion as the reference does it (its RGB image through COLOR_BGR2GRAY) and
         ``cornerSubPix(gray, corners, (4, 4), (-1, -1), (EPS + MAX_ITER, 30, 0.01))`` on the GPU.  Sets ``d["corners"]``
-        (n, 1, 2) float32, ``d["image_points"]`` (n, 2) and ``d["object_points"]``.  Without a guess: NotImplementedError."""
+        (n, 1, 2) float32, ``d["image_points"]`` (n, 2) and ``d["object_points"]``.  Without a guess: NotImplementedError,
+        or with ``detector="chess"`` the guess is detected first, and a record whose board is not found is left without
+        ``image_points`` (the reference's ``if ok``, boards.py:162)."""
         from . import imgproc
         coarse = d.get("corners")
         if coarse is None:
             coarse = d.get("coarse_corners")
         if coarse is None:
-            raise NotImplementedError(NO_QUAD_SEARCH)
+            if self.detector is None:
+                raise NotImplementedError(NO_QUAD_SEARCH)
+            coarse = self.detect_corners(d["img"])
+            if coarse is None:
+                return
         coarse = self._coarse(coarse)
         if not isinstance(coarse, np.ndarray):
             coarse = coarse.detach().cpu().numpy()
@@ -153,11 +168,32 @@ class Chessboard(BaseBoard):
         d["image_points"] = d["corners"][:, 0]
         d["object_points"] = self.object_points
 
-    def find_image_points_batch(self, images, coarse, return_info=False):
+    def detect_corners(self, img):
+        """The board's corners in one image, from the image alone (``imgproc.find_chessboard_corners`` with its default
+        thresholds): (n, 2) float32 whole pixels on the host, in the order of ``object_points``, or None where the board
+        is not found."""
+        from . import imgproc
+        found, corners = imgproc.find_chessboard_corners(img, self.checkboard)
+        if not bool(found):
+            return None
+        return corners if isinstance(corners, np.ndarray) else corners.cpu().numpy()
+
+    def find_image_points_batch(self, images, coarse=None, return_info=False):
         """A whole recording in one launch: ``images`` (f, h, w) gray or (f, h, w, 3) as the reference's loader gives
         them, ``coarse`` (f, n, 2) -> the refined corners (f, n, 2), NumPy or CUDA like the inputs, ready for
-        ``perspective_n_point_batch`` with ``object_points``.  ``return_info`` adds iterations and status."""
+        ``perspective_n_point_batch`` with ``object_points``.  ``return_info`` adds iterations and status.
+
+        ``coarse=None``: detect, then refine -> ``(found, corners)``: (f,) bool and (f, n, 2) float32, NaN in the
+        frames whose board is not found (their rows go through the refinement as starts that are no pixel and come back
+        as they are); ``return_info`` adds the refinement's iterations and status and the detector's status and
+        candidate counts."""
         from . import imgproc
+        if coarse is None:
+            det = imgproc.find_chessboard_corners(images, self.checkboard, return_info=return_info)
+            if det[1].ndim != 3:
+                raise ValueError("images must be a batch (f, h, w) or (f, h, w, 3), got %s" % (tuple(images.shape),))
+            refined = imgproc.corner_sub_pix(images, det[1], SUBPIX_WIN, SUBPIX_ZERO_ZONE, SUBPIX_CRITERIA, return_info=return_info)
+            return (det[0], refined) if not return_info else (det[0],) + tuple(refined) + tuple(det[2:])
         coarse = self._coarse(coarse, int(images.shape[0]))
         return imgproc.corner_sub_pix(images, coarse, SUBPIX_WIN, SUBPIX_ZERO_ZONE, SUBPIX_CRITERIA, return_info=return_info)
 

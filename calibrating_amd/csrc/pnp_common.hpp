@@ -2,6 +2,7 @@
 // pose per frame).  One wavefront per frame.  It offers:
 //   points_ok, doubles_ok; frame_rows, load_point, frame_nonfinite   the host's check of the points; a frame's checked rows
 //   wave_sum, wave_sum_all, wave_or, uniform   the fixed-order butterfly: the same bits of a sum in every lane
+//   wave_lds_fence                             orders a wave's writes to its own LDS slice against its other lanes' reads
 //   load_pose, store_pose, pose_terms          R, t as 12 doubles; a point's residual (raw pixels) and 2 x 6 pose Jacobian
 //   add_outer, add_gradient                    J^T J (packed lower triangle) and J^T r, two rows of J at a time
 //   damped, cholesky, cholesky_solve           (A + lambda diag A) x = b in registers
@@ -79,6 +80,13 @@ __device__ __forceinline__ int wave_or(int v)
 }
 // a flag every lane agrees on, as a scalar: the branches on it are uniform and the wave stays whole for the butterflies
 __device__ __forceinline__ bool uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+// what a wave wrote to its own slice of LDS is read by its other lanes (and the other way round): LDS serves a wave's
+// instructions in order, so only the compiler has to be held to that order (subpix.hip, chessboard.hip)
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 __device__ __forceinline__ double load_value(const void* p, int type, size_t i)
 {

@@ -55,14 +55,6 @@ __device__ __forceinline__ int frame_of(const SubpixArgs& a, unsigned c)
 
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-// what the wave wrote to its slice is read by its other lanes (and the other way round): LDS serves a wave's
-// instructions in order, so only the compiler has to be held to that order
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <typename T>
 __device__ __forceinline__ void store_corner(const SubpixArgs& a, unsigned c, T x, T y, int iterations, int status)
 {

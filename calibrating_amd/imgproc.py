@@ -515,3 +515,131 @@ def corner_sub_pix(images, corners, win=(4, 4), zero_zone=(-1, -1), criteria=(30
     if not return_info:
         return to_caller(out, was_np)
     return to_caller((out, iterations.reshape(lead), status.reshape(lead)), was_np)
+
+
+# ---- chessboard corners from the image alone (csrc/chessboard.hip; a contract of our own) ----
+CHESS_CAPACITY, CHESS_MAX_CORNERS, CHESS_MAX_RELATIVE, CHESS_MAX_NMS_RADIUS, CHESS_MAX_SIDE = 1024, 512, 64, 8, 16384
+CHESS_FEW, CHESS_OVERFLOW, CHESS_INCOMPLETE = 1, 2, 4  # find_chessboard_corners' status; 0 = found
+
+
+def _chess_arguments(pattern, relative, nms_radius):
+    """(across, down, relative, nms_radius) as integers within the detector's limits, or ValueError"""
+    try:
+        across, down = pattern
+    except (TypeError, ValueError):
+        raise ValueError("pattern must be the inner corners (across, down), got %r" % (pattern,))
+    for name, v in (("across", across), ("down", down), ("relative", relative), ("nms_radius", nms_radius)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    across, down, relative, nms_radius = int(across), int(down), int(relative), int(nms_radius)
+    if across < 2 or down < 2 or across * down > CHESS_MAX_CORNERS:
+        raise ValueError("a pattern of %d x %d corners; the detector takes across, down >= 2 with at most %d corners"
+                         % (across, down, CHESS_MAX_CORNERS))
+    if not 1 <= relative <= CHESS_MAX_RELATIVE:
+        raise ValueError("relative must be 1 .. %d, got %d" % (CHESS_MAX_RELATIVE, relative))
+    if not 1 <= nms_radius <= CHESS_MAX_NMS_RADIUS:
+        raise ValueError("nms_radius must be 1 .. %d, got %d" % (CHESS_MAX_NMS_RADIUS, nms_radius))
+    return across, down, relative, nms_radius
+
+
+def _chess_gray(images, what):
+    """(gray CUDA tensor, frames, h, w, pitch, stride, batched, was_numpy) of uint8 images (h, w[, 3]) or (f, h, w[, 3]);
+    colour goes through ``cvt_gray(code="bgr")``.  Every refusal comes before the device is touched."""
+    _check_image(images, what)
+    colour = images.ndim in (3, 4) and images.shape[-1] == 3  # (a gray image 3 wide has no pixel 5 from its borders)
+    if images.ndim not in (2, 3, 4) or (images.ndim == 4 and not colour):
+        raise ValueError("%s must be (h, w), (f, h, w), (h, w, 3) or (f, h, w, 3), got %s" % (what, tuple(images.shape)))
+    if 0 in tuple(images.shape):
+        raise ValueError("%s is empty: %s" % (what, tuple(images.shape)))
+    batched = images.ndim - (1 if colour else 0) == 3
+    gray = cvt_gray(_to_image(images), "bgr") if colour else _to_image(images)
+    gray, f, h, w, pitch, stride = _image_rows(gray, 1)
+    if f * h >= 2 ** 31:
+        raise ValueError("%s: %d rows in all, the kernels take fewer than 2^31" % (what, f * h))
+    return gray, f, h, w, pitch, stride, batched, is_np(images)
+
+
+def _chess_response(gray, f, h, w, pitch, stride):
+    import torch
+    r = torch.empty((f, h, w), dtype=torch.int16, device=gray.device)
+    rmax = torch.empty(f, dtype=torch.int32, device=gray.device)
+    call("camd_chess_response", gray.device, gray.data_ptr(), w, h, pitch, stride, f, r.data_ptr(), rmax.data_ptr(),
+         what="chess_response")
+    return r, rmax
+
+
+def chess_response(images):
+    """Stage 1 of the chessboard detector: the ChESS corner response (Bennett & Lasenby) times 5 of every pixel, in
+    integers -- ``include/calibrating_amd.h`` states the formula -- -> ``(response, response_max)``: int16 in the shape of
+    the gray image(s), 0 within 5 px of a border, and its maximum per frame, int32 (f,) (0-d for one image).  ``images``:
+    uint8 gray (h, w) / (f, h, w) or colour (h, w, 3) / (f, h, w, 3) (through ``cvt_gray``), NumPy or CUDA; pitched views
+    are read in place."""
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    r, rmax = _chess_response(gray, f, h, w, pitch, stride)
+    return to_caller((r, rmax) if batched else (r[0], rmax[0]), was_np)
+
+
+def _chess_peaks(r, rmax, relative, nms_radius):
+    import torch
+    f, h, w = (int(v) for v in r.shape)
+    peaks = torch.full((f, CHESS_CAPACITY, 2), -1, dtype=torch.int32, device=r.device)
+    counts = torch.empty(f, dtype=torch.int32, device=r.device)
+    ws = torch.empty(_native.lib().camd_chess_peaks_workspace_bytes(h, f), dtype=torch.uint8, device=r.device)
+    call("camd_chess_peaks", r.device, r.data_ptr(), rmax.data_ptr(), w, h, f, relative, nms_radius, ws.data_ptr(),
+         peaks.data_ptr(), counts.data_ptr(), what="chess_peaks")
+    return peaks, counts
+
+
+def chess_peaks(response, response_max, relative=8, nms_radius=3):
+    """Stage 2: the candidates of response planes (f, h, w) int16 with their maxima (f,) int32 -- positive, at least
+    1 / ``relative`` of the frame's maximum, and the peak of their (2 nms_radius + 1)^2 window (of equal responses the
+    first in pixel order) -> ``(peaks, counts)``: int32 (f, 1024, 2) of (x, y) in pixel order, -1 beyond a frame's
+    candidates, and every frame's count in full, int32 (f,)."""
+    _, _, relative, nms_radius = _chess_arguments((2, 2), relative, nms_radius)
+    check_array(response, "response")
+    check_array(response_max, "response_max")
+    if is_np(response) != is_np(response_max):
+        raise TypeError("response and response_max must both be NumPy arrays or both be CUDA tensors")
+    if dtype_name(response) != "int16" or dtype_name(response_max) != "int32":
+        raise ValueError("response must be int16 and response_max int32, got %s and %s" % (response.dtype, response_max.dtype))
+    if response.ndim != 3 or 0 in tuple(response.shape) or tuple(response_max.shape) != (response.shape[0],):
+        raise ValueError("response must be (f, h, w) and response_max (f,), got %s and %s"
+                         % (tuple(response.shape), tuple(response_max.shape)))
+    if response.shape[0] * response.shape[1] >= 2 ** 31:
+        raise ValueError("response: %d rows in all, the kernels take fewer than 2^31" % (response.shape[0] * response.shape[1]))
+    r = to_device(response)
+    return to_caller(_chess_peaks(r, to_device(response_max, device=r.device), relative, nms_radius), is_np(response))
+
+
+def find_chessboard_corners(images, pattern, relative=8, nms_radius=3, return_info=False):
+    """The inner corners of a chessboard of ``pattern`` = (across, down) corners from the image alone, on the GPU, for
+    every frame at once -> ``(found, corners)``: bool and float32 (n, 2) for one image, (f,) and (f, n, 2) for a batch,
+    NumPy or CUDA like ``images``; corners are whole pixels in the board's order (across fastest), NaN where the board
+    was not found -- seeds for ``corner_sub_pix``.  The detector is this package's own, NOT
+    cv2.findChessboardCorners: ChESS response -> peaks of at least 1 / ``relative`` of the frame's strongest, alone in
+    their (2 ``nms_radius`` + 1)^2 window -> a lattice grown from the peak nearest the centroid.  Squares below about
+    12 px and corners within 5 px of a border are out of its range; of the two (a square pattern: four) ways to number
+    a board it returns the one whose first corner comes first in pixel order.
+
+    ``images``: uint8 gray or colour (through ``cvt_gray(code="bgr")``), (h, w[, 3]) or (f, h, w[, 3]), sides up to
+    16384.  ``return_info``: ``(found, corners, status, counts)`` -- status 0 found, 1 fewer candidates than corners,
+    2 more candidates than the 1024 kept, 4 lattice incomplete or of another size; counts: the candidates, int32."""
+    import torch
+    across, down, relative, nms_radius = _chess_arguments(pattern, relative, nms_radius)
+    check_array(images, "images")
+    if images.ndim in (2, 3, 4) and max(images.shape[-3:-1] if images.shape[-1] == 3 else images.shape[-2:]) > CHESS_MAX_SIDE:
+        raise ValueError("images of %s; the detector takes sides up to %d" % (tuple(images.shape), CHESS_MAX_SIDE))
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    r, rmax = _chess_response(gray, f, h, w, pitch, stride)
+    peaks, counts = _chess_peaks(r, rmax, relative, nms_radius)
+    corners = torch.empty((f, across * down, 2), dtype=torch.float32, device=gray.device)
+    status = torch.empty(f, dtype=torch.int32, device=gray.device)
+    call("camd_chess_lattice", gray.device, peaks.data_ptr(), counts.data_ptr(), w, h, f, across, down, corners.data_ptr(),
+         status.data_ptr(), what="find_chessboard_corners")
+    out = (status == 0, corners, status, counts)
+    if not batched:
+        out = tuple(v[0] for v in out)
+    out = to_caller(out if return_info else out[:2], was_np)
+    if was_np and not batched:
+        out = (bool(out[0]),) + tuple(out[1:])
+    return out

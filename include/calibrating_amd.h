@@ -747,6 +747,44 @@ int camd_corner_sub_pix(const uint8_t* gray, int w, int h, size_t pitch, size_t 
 int camd_bgr_to_gray_u8(const uint8_t* src, int w, int h, size_t src_pitch, size_t src_stride, uint8_t* dst, size_t dst_pitch,
                         size_t dst_stride, int batch, int k0, int k1, int k2, int shift, void* queue);
 
+/* ---- chessboard corners from the image alone (csrc/chessboard.hip) ----
+ * Stands where the reference calls cv2.findChessboardCorners (boards.py:160) with a contract of its OWN, not cv2's
+ * (INTEGRATION.md section J): three stages, every value an integer, restated in NumPy by tests/chessboard_ref.py.      */
+#define CAMD_CHESS_CAPACITY 1024   /* candidates kept per frame */
+#define CAMD_CHESS_MAX_CORNERS 512 /* across * down */
+/* Stage 1.  gray: frames images of w x h uint8, rows `pitch` and images `stride` bytes apart.  response: frames * h * w
+ * int16, dense; response_max: one int32 per frame.  With g the image and I[0 .. 15] = g(x + dx, y + dy) at (dx, dy) =
+ * (5,0) (5,2) (4,4) (2,5) (0,5) (-2,5) (-4,4) (-5,2) (-5,0) (-5,-2) (-4,-4) (-2,-5) (0,-5) (2,-5) (4,-4) (5,-2):
+ *   sr = sum n<4 |I[n] + I[n+8] - I[n+4] - I[n+12]|, dr = sum n<8 |I[n] - I[n+8]|, ring = sum I,
+ *   local = g(x, y) + g(x-1, y) + g(x+1, y) + g(x, y-1) + g(x, y+1),  r = 5 sr - 5 dr - |5 ring - 16 local|
+ * (the ChESS response times 5), r = 0 within 5 px of a border; -30600 <= r <= 10200.  response_max >= 0.             */
+int camd_chess_response(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, int16_t* response,
+                        int* response_max, void* queue);
+/* Stage 2.  Pixel p is a candidate when r(p) > 0, relative * r(p) >= response_max[frame], and within the
+ * (2 nms_radius + 1)^2 window clipped to the image r(p) > r(q) for every q before p in pixel order and r(p) >= r(q) for
+ * every q after it.  peaks: frames x CAMD_CHESS_CAPACITY x 2 int32 (x, y), a frame's candidates in pixel order (those
+ * beyond the capacity are dropped, the entries beyond the count are not written); counts: the candidates of each frame
+ * in full.  workspace: camd_chess_peaks_workspace_bytes(h, frames) device bytes, 8-aligned.  relative 1 .. 64,
+ * nms_radius 1 .. 8, else CAMD_ERR_UNSUPPORTED.                                                                      */
+size_t camd_chess_peaks_workspace_bytes(int h, int frames);
+int camd_chess_peaks(const int16_t* response, const int* response_max, int w, int h, int frames, int relative, int nms_radius,
+                     void* workspace, int* peaks, int* counts, void* queue);
+/* Stage 3, one wavefront per frame.  status: 2 where counts > CAMD_CHESS_CAPACITY, 1 where counts < n = across * down,
+ * else the lattice is grown -- int32 / int64 squared distances and cross products, ties to the lowest candidate index:
+ *   seed s minimises |m p - sum p|^2 over the m candidates; a is the nearest to s, u = a - s; b the nearest to s with
+ *   4 cross(u, b - s)^2 >= |u|^2 |b - s|^2, v = b - s (none: status 4).  s is cell (0, 0); breadth first in queue order,
+ *   directions +i, -i, +j, -j: a neighbour cell that is still empty is predicted at p + step, step = p - (the cell
+ *   behind p) if labelled, else the same-direction step between the labelled pair beside p -- cells (i, j-1),(i+di, j-1)
+ *   then (i, j+1),(i+di, j+1) for +-i; (i-1, j),(i-1, j+dj) then (i+1, .) for +-j --, else +-u / +-v; the nearest
+ *   unlabelled candidate c takes the cell when 4 |c - prediction|^2 <= |step|^2.  Growth ends when more than n are labelled.
+ *   Found: exactly n labelled, filling a box of across x down or down x across.  Order: across fastest; of the labelings
+ *   of that shape with cross(sum of row steps, sum of column steps) > 0 (y down) the one whose corner 0 has the lowest
+ *   y * w + x.  Otherwise status 4.
+ * corners: frames x n x 2 float32, integer-valued, NaN where status != 0.  across, down >= 2, n <= CAMD_CHESS_MAX_CORNERS,
+ * w, h <= 16384, else CAMD_ERR_UNSUPPORTED.                                                                          */
+int camd_chess_lattice(const int* peaks, const int* counts, int w, int h, int frames, int across, int down, float* corners,
+                       int* status, void* queue);
+
 #ifdef __cplusplus
 }
 #endif
