@@ -9,7 +9,7 @@ GPU, computing does.
 from .__info__ import __version__
 from .camera import Cam
 from .sgbm import MODE_HH, MODE_HH4, MODE_SGBM, MODE_SGBM_3WAY, StereoSGBM, StereoSGBM_create
-from .stereo_matching import FeatureMatchingAsStereoMatching, MetaStereoMatching, SemiGlobalBlockMatching
+from .stereo_matching import FeatureMatchingAsStereoMatching, MatchingByBoard, MetaStereoMatching, SemiGlobalBlockMatching
 from .stereo_camera import Stereo
 from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, filter_overlap_uvs, flow_abs_to_normal,
                                 flow_normal_to_abs, flow_to_matched_uvs, matching_uvs_in_one_img,
@@ -32,4 +32,5 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "resolve_max_l1", "vis_stereo", "vis_align", "solve_pnp_batch", "mean_Ts",
            "calibrate_camera", "CALIB_USE_INTRINSIC_GUESS", "CALIB_FIX_PRINCIPAL_POINT", "CALIB_FIX_FOCAL_LENGTH",
            "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
-           "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard"]
+           "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard",
+           "MatchingByBoard"]

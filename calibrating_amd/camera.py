@@ -11,6 +11,8 @@ Two point methods of the reference's ``Cam`` run on the GPU: ``undistort_points`
 alignment pictures, ``vis_depth_alignment`` and ``vis_reproject_img_alignment`` (camera.py:311-342; csrc/vis.hip), and the
 pose of a target from its detected points: ``perspective_n_point``, ``solve_poses`` for every stored frame in one launch,
 ``get_T_cam2_in_self`` (camera.py:266-273, 289-296; csrc/pnp.hip).  Detecting the points stays with the caller.
+The board as ground truth: ``get_calibration_board_T``, ``get_calibration_board_depth`` and its batch form
+(camera.py:214-264; csrc/hull.hip) give the dense depth of the board's plane in an image or a whole recording.
 """
 import copy
 
@@ -222,6 +224,125 @@ class Cam(dict):
                 d.pop("T", None)
                 d.pop("reprojection_error", None)
         return {k: int(s) for k, s in zip(keys, res["status"])}
+
+    # ---- the board as ground truth (camera.py:214-264; csrc/hull.hip) ----
+    def get_board(cam=None, d=None, board=None):
+        """The board to look for: ``board`` > ``d["board"]`` > ``cam.board`` (camera.py:253-264)."""
+        if board is None:
+            if d and d.get("board"):
+                board = d.get("board")
+            elif hasattr(cam, "board"):
+                board = cam.board
+        assert board, "Please set board or cam.board"
+        return board
+
+    def get_calibration_board_T(self, img_or_d, board=None):
+        """The record of one image with the board's pose in it (camera.py:214-232): ``board.find_image_points`` sets
+        ``image_points`` / ``object_points``, ``perspective_n_point`` adds ``T``, ``retval``, ``reprojection_error``.
+        ``img_or_d``: an image (ndarray or CUDA tensor) or a record with ``"img"``; a record is copied, not changed.  A
+        board that is not found leaves the record without ``image_points`` and ``T``.  Paths are not read here."""
+        if isinstance(img_or_d, dict):
+            d = img_or_d.copy()
+            if isinstance(d.get("img"), str) or "img" not in d:
+                raise ValueError("get_calibration_board_T: images are not read from paths here -- load the image and pass it "
+                                 "as d['img']")
+        elif isinstance(img_or_d, str):
+            raise ValueError("get_calibration_board_T: images are not read from paths here -- load %r and pass the array"
+                             % (img_or_d,))
+        else:
+            d = dict(img=img_or_d)
+        assert tuple(d["img"].shape[:2][::-1]) == tuple(self.xy)
+        board = self.get_board(d, board)
+        board.find_image_points(d)
+        if "image_points" in d:
+            d.update(self.perspective_n_point(d["image_points"], d["object_points"]))
+        return d
+
+    def _board_rows(self, T, object_points):
+        """(f, n, 3) float64 CUDA rows (u, v, z) of the board's points in every frame, nearest last: ``object_points`` (n, 3)
+        through each pose of ``T`` (f, 4, 4), then the pinhole projection with K -- D is ignored, the reference's quirk
+        (``point_cloud_to_depth(xyz, K, xy)``).  Every product and sum is one elementwise float64 operation, left to
+        right, so NumPy gives the same bits.  The order is the z-buffer's: farthest first, so the last row of a pixel is
+        the nearest one."""
+        import torch
+        o = object_points.to(torch.float64)
+        x, y, z = o[None, :, 0], o[None, :, 1], o[None, :, 2]
+        cam = [T[:, i, 0, None] * x + T[:, i, 1, None] * y + T[:, i, 2, None] * z + T[:, i, 3, None] for i in range(3)]
+        K = [[float(v) for v in row] for row in np.asarray(self.K, np.float64)[:3, :3]]
+        p, q, s = (K[i][0] * cam[0] + K[i][1] * cam[1] + K[i][2] * cam[2] for i in range(3))
+        rows = torch.stack([p / s, q / s, s], -1)
+        order = torch.sort(-s, dim=1, stable=True).indices  # argsort(-z), ties in row order
+        return torch.gather(rows, 1, order[:, :, None].expand(-1, -1, 3))
+
+    def _board_depth(self, T, object_points, zero_frames, is_dense):
+        """``point_cloud_to_depth`` of the board in every frame and, dense, ``1 / fill(1 / sparse)`` inside the hull."""
+        import torch
+        from . import sparse
+        w, h = int(self.xy[0]), int(self.xy[1])
+        rows = self._board_rows(T, object_points)
+        frames = int(rows.shape[0])
+        if is_dense:
+            # what the scatter and 1 / sparse leave of a row: its pixel and its inverse depth; the last row of a pixel stays
+            samples = torch.stack([torch.round(rows[..., 0]), torch.round(rows[..., 1]), 1 / rows[..., 2]], -1)
+            return sparse.interpolate_uvzs_in_hull(samples, (h, w), reciprocal=True, keep_last_per_pixel=True, zero_frames=zero_frames)
+        # the scatter of all frames at once: frame f is rows f h .. f h + h - 1 of one tall image; what leaves its frame is dropped
+        u, v = torch.round(rows[..., 0]), torch.round(rows[..., 1])
+        inside = (u >= 0) & (u < w) & (v >= 0) & (v < h) & ~zero_frames[:, None]
+        nan = torch.full_like(u, float("nan"))
+        v = v + torch.arange(frames, dtype=torch.float64, device=u.device)[:, None] * h
+        uvz = torch.stack([torch.where(inside, u, nan), torch.where(inside, v, nan), rows[..., 2]], -1).reshape(-1, 3)
+        return sparse.uvzs_to_arr2d(uvz, (frames * h, w)).reshape(frames, h, w)
+
+    def get_calibration_board_depth(cam, img_or_d, is_dense=True, board=None):
+        """The record of ``get_calibration_board_T`` with ``depth``, the depth of the board's plane as ground truth
+        (camera.py:234-251), on the GPU: the object points through ``T``, the pinhole ``point_cloud_to_depth(xyz, K, xy)``
+        (D is ignored: the reference's quirk, kept), and with ``is_dense`` ``1 / fill(1 / sparse)`` by
+        ``sparse.interpolate_uvzs_in_hull`` -- float32, ``+inf`` outside the board's hull as in the reference; without
+        ``is_dense`` the sparse float64 depth.  Where the board is not found: zeros.  An ndarray image gives an ndarray, a CUDA
+        image a CUDA tensor."""
+        import torch
+        from ._arrays import is_np, to_caller, to_device
+        d = cam.get_calibration_board_T(img_or_d, board=board)
+        was_np = is_np(d["img"])
+        if "object_points" not in d or "T" not in d:
+            d["depth"] = np.zeros(cam.xy[::-1]) if was_np else torch.zeros(tuple(cam.xy[::-1]), dtype=torch.float64, device=d["img"].device)
+            return d
+        object_points = d["object_points"]
+        if isinstance(object_points, dict):
+            object_points = np.concatenate(list(object_points.values()), 0)
+        if was_np:
+            from . import _native
+            _native.require_device()
+        dev = torch.device("cuda", torch.cuda.current_device()) if was_np else d["img"].device
+        T = torch.from_numpy(np.ascontiguousarray(d["T"], np.float64)[None]).to(dev)
+        o = torch.from_numpy(np.ascontiguousarray(object_points)).to(dev)
+        depth = cam._board_depth(T, o, torch.zeros(1, dtype=torch.bool, device=dev), is_dense)
+        d["depth"] = to_caller(depth[0], was_np)
+        return d
+
+    def get_calibration_board_depth_batch(cam, images, board=None, is_dense=True):
+        """``get_calibration_board_depth`` of a whole recording in one call -> ``dict(depth (f, h, w), T (f, 4, 4) float64,
+        found (f,) bool, status (f,) int32)``, ndarrays for ndarray images and CUDA tensors for CUDA tensors.  ``images``:
+        (f, h, w) gray or (f, h, w, 3).  ``board.find_image_points_batch`` detects and refines, ``perspective_n_point_batch``
+        poses, one batched fill writes the depth: no frame is handled on the host, and nothing read back decides what is
+        launched beyond the one planarity test of the pose solver.  A frame without a board, or whose pose is not
+        solved, has ``found`` False, zeros for its depth and NaN in its ``T``; ``status`` is the pose solver's (0 ok).
+        Frame i equals ``get_calibration_board_depth(images[i])`` bit for bit."""
+        import torch
+        from ._arrays import check_array, is_np, to_caller, to_device
+        check_array(images, "images")
+        if len(images.shape) not in (3, 4) or tuple(images.shape[1:3][::-1]) != tuple(cam.xy):
+            raise ValueError("images must be (f, %d, %d) or (f, %d, %d, 3), got %s"
+                             % (cam.xy[1], cam.xy[0], cam.xy[1], cam.xy[0], tuple(images.shape)))
+        board = cam.get_board(None, board)
+        was_np = is_np(images)
+        imgs = to_device(images)
+        seen, corners = board.find_image_points_batch(imgs)
+        o = torch.from_numpy(np.ascontiguousarray(board.object_points)).to(imgs.device)
+        res = cam.perspective_n_point_batch(corners, o)
+        found = seen.to(torch.bool) & (res["status"] == 0)
+        depth = cam._board_depth(res["T"], o, ~found, is_dense)
+        return dict(zip(("depth", "T", "found", "status"), to_caller((depth, res["T"], found, res["status"]), was_np)))
 
     def _pose_keys(cam1, cam2):
         return [k for k in cam1.valid_keys_intersection(cam2) if "T" in cam1[k] and "T" in cam2[k]]

@@ -6,7 +6,9 @@ tensors out (csrc/sparse.hip; INTEGRATION.md section E has the tie rules and wha
 
 Arguments are checked before the device is touched: ``inter_type="rbf"`` (SciPy's dense thin-plate solve) and a truthy
 ``constrained_type`` (``cv2.convexHull`` / ``drawContours``, whose rasterisation nothing here can pin) raise
-``NotImplementedError`` on a machine without a GPU too.
+``NotImplementedError`` on a machine without a GPU too.  The fill inside the samples' convex hull is a function of its own
+with a mask contract of its own: ``interpolate_uvzs_in_hull`` / ``interpolate_sparse2d_in_hull`` / ``convex_hull_mask``
+(csrc/hull.hip), batched over frames.
 """
 import ctypes
 
@@ -19,6 +21,9 @@ from ._native import call
 MAX_DISTANCE = _native.NEAREST_MAX_RADIUS  # interpolate_uvzs(inter_type="nearest"): the search window the kernel supports
 # the plane fit hands over to np.linalg.lstsq on the host when 1 - corr(u, v)^2 of the samples is not above this
 COLLINEAR_TOL = 1e-9
+# interpolate_uvzs_in_hull / convex_hull_mask (csrc/hull.hip): the rows one frame may hold, and the bits of its status word
+MAX_HULL_POINTS = 4096  # CAMD_HULL_MAX_POINTS
+STATUS_NO_SAMPLE, STATUS_DEGENERATE, STATUS_OUT_OF_RANGE = 1, 2, 4
 
 
 def _require_finite(uv, what):
@@ -257,6 +262,156 @@ def _fit_plane(lib, uv, z, zname, n):
     a = (cuz * cvv - cvz * cuv) / det
     b = (cvz * cuu - cuz * cuv) / det
     return a, b, mz - a * mu - b * mv
+
+
+# ---- d'. the plane inside the samples' convex hull -------------------------------------------------------------------
+def _hull_layout(rows, width, counts, what):
+    """(flat rows (N, width), frame lengths, batched) of the three ways the rows are given: (n, width) one frame,
+    (f, n, width) a batch, ragged (N, width) with ``counts``.  Refuses everything else; nothing touches the device."""
+    check_array(rows, what)
+    shape = tuple(int(s) for s in rows.shape)
+    if counts is not None:
+        lengths = np.asarray(counts)
+        if lengths.ndim != 1 or lengths.dtype.kind not in "iu" or len(lengths) == 0 or (lengths < 0).any():
+            raise ValueError("counts must be a non-empty 1-d array of non-negative integers")
+        lengths = lengths.astype(np.int64)
+        if len(shape) != 2 or shape[1] != width or int(lengths.sum()) != shape[0]:
+            raise ValueError("with counts, %s is ragged rows (N, %d) with N = sum(counts) = %d, got %s"
+                             % (what, width, lengths.sum(), shape))
+        batched = True
+    elif len(shape) == 2 and shape[1] == width:
+        lengths, batched = np.array([shape[0]], np.int64), False
+    elif len(shape) == 3 and shape[2] == width and shape[0] >= 1:
+        lengths, batched = np.full(shape[0], shape[1], np.int64), True
+    else:
+        raise ValueError("%s must be (n, %d) or (f, n, %d), got %s" % (what, width, width, shape))
+    if lengths.max() > MAX_HULL_POINTS:
+        raise ValueError("%s: a frame of %d rows, at most MAX_HULL_POINTS = %d are supported" % (what, lengths.max(), MAX_HULL_POINTS))
+    return rows.reshape(-1, width), lengths, batched
+
+
+def _hull_fit(flat, lengths, hw, keep_last_per_pixel, counts_given):
+    """Stage A (``camd_hull_fit``) -> the per-frame record on the device: vertices, hull_counts, abc, status."""
+    import torch
+    frames, capacity = len(lengths), max(1, int(lengths.max()))
+    uv = to_device(flat[:, :2], dtype="float64", cast=True)
+    dev, z, zname = uv.device, None, "float64"
+    if flat.shape[1] == 3:
+        zname = "float32" if dtype_name(flat) == "float32" else "float64"
+        z = to_device(flat[:, 2], dtype=zname, cast=True, device=dev)
+    start = None
+    if counts_given:
+        start = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(dev)
+    rec = dict(vertices=torch.empty((frames, capacity, 2), dtype=torch.int32, device=dev),
+               hull_counts=torch.empty(frames, dtype=torch.int32, device=dev),
+               abc=torch.empty((frames, 3), dtype=torch.float64, device=dev),
+               status=torch.empty(frames, dtype=torch.int32, device=dev), capacity=capacity, frames=frames)
+    call("camd_hull_fit", dev, uv.data_ptr(), 2, None if z is None else z.data_ptr(), VALUE_TYPES[zname], int(uv.shape[0]),
+         None if start is None else start.data_ptr(), frames, hw[1], hw[0], int(bool(keep_last_per_pixel)), capacity,
+         rec["vertices"].data_ptr(), rec["hull_counts"].data_ptr(), rec["abc"].data_ptr(), rec["status"].data_ptr(),
+         what="interpolate_uvzs_in_hull")
+    return rec
+
+
+def _rows_that_take_part(uvz, hw, keep_last_per_pixel):
+    """Host NumPy: the rows of one frame the kernel fits (valid; with ``keep_last_per_pixel`` inside the image and the
+    last of their pixel) -- for the minimum-norm fallback of a degenerate frame."""
+    s = np.asarray(uvz, np.float64)
+    with np.errstate(invalid="ignore"):
+        r = np.rint(s[:, :2])
+        ok = np.isfinite(s).all(1) & (s[:, 2] != 0) & (np.abs(r) <= 2 ** 20).all(1)
+        if keep_last_per_pixel:
+            ok &= (r[:, 0] >= 0) & (r[:, 0] < hw[1]) & (r[:, 1] >= 0) & (r[:, 1] < hw[0])
+    idx = np.nonzero(ok)[0]
+    if keep_last_per_pixel and len(idx):
+        last = {}
+        for i in idx:
+            last[(r[i, 0], r[i, 1])] = i
+        idx = np.array(sorted(last.values()))
+    return s[idx]
+
+
+def convex_hull_mask(uvs, hw, counts=None):
+    """uint8 (h, w) -- or (f, h, w) for (f, n, 2) rows or ragged (N, 2) rows with ``counts`` -- that is 1 where the pixel
+    lies in the closed convex hull of ``int32(round(u, v))`` (half to even) of the rows with finite u, v within 2**20:
+    this package's own, integer-exact mask, not ``cv2.drawContours``'.  Points outside the
+    image take part; one point fills its pixel, collinear points the pixels whose centres lie on the segment."""
+    import torch
+    flat, lengths, batched = _hull_layout(uvs, 2, counts, "uvs")
+    h, w = positive_hw(hw)
+    was_np = is_np(uvs)
+    rec = _hull_fit(flat, lengths, (h, w), False, counts is not None)
+    out = torch.empty((rec["frames"], h, w), dtype=torch.uint8, device=rec["abc"].device)
+    call("camd_hull_mask", out.device, rec["vertices"].data_ptr(), rec["hull_counts"].data_ptr(), rec["capacity"], rec["frames"],
+         w, h, out.data_ptr(), what="convex_hull_mask")
+    return to_caller(out if batched else out[0], was_np)
+
+
+def interpolate_uvzs_in_hull(uvzs, hw, counts=None, reciprocal=False, keep_last_per_pixel=False, return_info=False,
+                             zero_frames=None):
+    """The least-squares plane z = a u + b v + c of sparse (u, v, z) rows, written only inside their convex hull and 0
+    outside: float32 (h, w) for (n, 3) rows, (f, h, w) for a batch (f, n, 3) or ragged rows (N, 3) with ``counts`` (the
+    convention of ``pnp.solve_pnp_batch``).  What the reference's ``interpolate_uvzs(..., constrained_type=True)`` is for
+    (utils.py:356-415), with the mask of ``convex_hull_mask`` in place of cv2's.  NumPy in -> NumPy out, CUDA in -> CUDA out.
+
+    A row takes part when u, v are finite, z is finite and not 0 and the rounded pixel is within 2**20.
+    ``keep_last_per_pixel``: rows whose pixel is outside the image are dropped and of several rows on one pixel the last
+    stays -- what a scatter through ``uvzs_to_arr2d`` leaves.  ``reciprocal``: float32 ``1 / that`` is written instead
+    (``+inf`` outside the hull, as the reference's ``1 / interpolate_sparse2d(...)`` gives).  At most ``MAX_HULL_POINTS``
+    rows per frame.  A frame gets the same bits alone and anywhere in a batch.
+
+    ``return_info`` adds ``dict(status, abc, hull_counts)``; status bits: 1 no row takes part (empty mask), 2 fewer than
+    three non-collinear rows, 4 a row beyond 2**20 was left out.  A batch leaves a frame of status 2 NaN inside its
+    hull; the (n, 3) form reads its one status word and takes ``np.linalg.lstsq``'s minimum-norm plane on the host, as
+    ``interpolate_uvzs`` does for such samples.  ``zero_frames`` (f,) bool, of a batch: the frames written as zeros
+    throughout, whatever ``reciprocal`` says -- the frames of a recording that show no board."""
+    import torch
+    flat, lengths, batched = _hull_layout(uvzs, 3, counts, "uvzs")
+    h, w = positive_hw(hw)
+    was_np = is_np(uvzs)
+    if zero_frames is not None:
+        check_array(zero_frames, "zero_frames")
+        if not batched or tuple(zero_frames.shape) != (len(lengths),):
+            raise ValueError("zero_frames goes with a batch and holds one flag per frame (%d), got %s"
+                             % (len(lengths), tuple(zero_frames.shape)))
+    rec = _hull_fit(flat, lengths, (h, w), keep_last_per_pixel, counts is not None)
+    dev = rec["abc"].device
+    if not batched and int(rec["status"].item()) & (STATUS_NO_SAMPLE | STATUS_DEGENERATE) == STATUS_DEGENERATE:
+        s = _rows_that_take_part(flat if was_np else flat.cpu().numpy(), (h, w), keep_last_per_pixel)
+        A = s.copy()
+        A[:, 2] = 1
+        rec["abc"].copy_(torch.from_numpy(np.linalg.lstsq(A, s[:, 2], rcond=None)[0].reshape(1, 3)))
+    out = torch.empty((rec["frames"], h, w), dtype=torch.float32, device=dev)
+    zero = None if zero_frames is None else (to_device(zero_frames, device=dev) != 0).view(torch.uint8)
+    call("camd_hull_fill", dev, rec["vertices"].data_ptr(), rec["hull_counts"].data_ptr(), rec["abc"].data_ptr(), rec["capacity"],
+         rec["frames"], w, h, int(bool(reciprocal)), None if zero is None else zero.data_ptr(), out.data_ptr(),
+         what="interpolate_uvzs_in_hull")
+    out = to_caller(out if batched else out[0], was_np)
+    if not return_info:
+        return out
+    info = to_caller((rec["status"], rec["abc"], rec["hull_counts"]), was_np)
+    return out, dict(zip(("status", "abc", "hull_counts"), info if batched else (x[0] for x in info)))
+
+
+def interpolate_sparse2d_in_hull(sparse2d, reciprocal=False):
+    """``interpolate_uvzs_in_hull`` of the non-zero, finite pixels of an (h, w) image: the image form
+    (utils.py:347-353 with ``constrained_type=True``).  More than ``MAX_HULL_POINTS`` such pixels are refused."""
+    import torch
+    check_array(sparse2d, "sparse2d")
+    if len(sparse2d.shape) != 2:
+        raise ValueError("sparse2d must be (h, w), got %s" % (tuple(sparse2d.shape),))
+    hw = positive_hw(sparse2d.shape)
+    was_np = is_np(sparse2d)
+    if was_np:  # counted on the host: the refusal comes before the device is touched
+        with np.errstate(invalid="ignore"):
+            n = int(np.count_nonzero((sparse2d != 0) & np.isfinite(sparse2d)))
+        if n > MAX_HULL_POINTS:
+            raise ValueError("sparse2d holds %d samples, at most MAX_HULL_POINTS = %d are supported" % (n, MAX_HULL_POINTS))
+    s = to_device(sparse2d)
+    uvzs = arr2d_to_uvzs(s, (s != 0) & torch.isfinite(s))
+    if int(uvzs.shape[0]) > MAX_HULL_POINTS:
+        raise ValueError("sparse2d holds %d samples, at most MAX_HULL_POINTS = %d are supported" % (uvzs.shape[0], MAX_HULL_POINTS))
+    return to_caller(interpolate_uvzs_in_hull(uvzs, hw, reciprocal=reciprocal), was_np)
 
 
 # ---- e. triangulation of matches -------------------------------------------------------------------------------------

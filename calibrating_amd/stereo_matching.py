@@ -131,3 +131,53 @@ class FeatureMatchingAsStereoMatching(MetaStereoMatching):
         disparity = sparse.interpolate_uvzs(uvds, resize_shape, constrained_type=None, inter_type="nearest",
                                             resize_hw=hw if resize_shape != hw else None)
         return dict(disparity=disparity, matched=matched)
+
+
+class MatchingByBoard(MetaStereoMatching):
+    """The disparity of a calibration board seen in both rectified images, from its image points
+    (stereo_matching.py:73-110): ground truth for a matcher.  ``board.find_image_points`` runs on both images; the points
+    are ndarrays or the reference's id -> points dicts (joined by their sorted common keys).  ``(x1, y1, x1 - x2)`` is
+    scattered into an image (last writer wins) and, with ``dense_predict``, ``1 / fill(1 / sparse)`` inside the points'
+    convex hull by ``sparse.interpolate_sparse2d_in_hull`` (``+inf`` outside the hull, as in the reference).  Returns
+    ``dict(disparity, rectify_std)``: rectify_std is the standard deviation of ``y2 - y1``, 0 for a perfect rectification.
+
+    Not the reference's: where either image shows no board the reference dies with ``KeyError``; here the disparity is
+    all zeros and ``rectify_std`` is NaN.  CUDA images stay on the device and the disparity comes back as a tensor."""
+
+    accepts_device_tensors = True
+
+    def __init__(self, board, dense_predict=True):
+        self.board = board
+        self.dense_predict = dense_predict
+
+    def __call__(self, img1, img2):
+        from . import sparse
+        d1, d2 = dict(img=img1), dict(img=img2)
+        self.board.find_image_points(d1)
+        self.board.find_image_points(d2)
+        hw = tuple(int(v) for v in img1.shape[:2])
+        was_np = is_np(img1)
+        points1, points2 = d1.get("image_points"), d2.get("image_points")
+        if isinstance(points1, dict) and isinstance(points2, dict):
+            keys = sorted(set(points1).intersection(points2))
+            points1 = np.concatenate([points1[k] for k in keys], 0) if keys else None
+            points2 = np.concatenate([points2[k] for k in keys], 0) if keys else None
+        if points1 is None or points2 is None or not len(points1):
+            if was_np:
+                return dict(disparity=np.zeros(hw, np.float32), rectify_std=float("nan"))
+            import torch
+            return dict(disparity=torch.zeros(hw, dtype=torch.float32, device=img1.device), rectify_std=float("nan"))
+        points1, points2 = np.asarray(points1), np.asarray(points2)
+        rectify_std = np.std((points2 - points1)[:, 1])
+        point_disps = (points1 - points2)[:, 0]
+        xyds = np.append(points1, point_disps[:, None], axis=-1)
+        if not was_np:
+            import torch
+            xyds = torch.from_numpy(np.ascontiguousarray(xyds)).to(img1.device)
+        sparse_disp = sparse.uvzs_to_arr2d(xyds, hw)
+        if self.dense_predict:
+            with np.errstate(divide="ignore"):  # (1 / 0 = inf marks the pixels without a sample, as in the reference)
+                disparity = sparse.interpolate_sparse2d_in_hull(1 / sparse_disp, reciprocal=True)
+        else:
+            disparity = sparse_disp
+        return dict(disparity=disparity, rectify_std=rectify_std)

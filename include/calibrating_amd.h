@@ -785,6 +785,46 @@ int camd_chess_peaks(const int16_t* response, const int* response_max, int w, in
 int camd_chess_lattice(const int* peaks, const int* counts, int w, int h, int frames, int across, int down, float* corners,
                        int* status, void* queue);
 
+/* ---- sparse samples filled by their plane inside their convex hull, batched over frames (csrc/hull.hip) ----
+ * Stands where the reference's interpolate_uvzs(..., constrained_type="convex_hull") calls cv2.convexHull and
+ * cv2.drawContours (utils.py:364-367) with a mask contract of its OWN (UNPINNED against cv2,
+ * DESIGN.md section 2, U33).  A row (u, v, z) is VALID when u, v are finite, z is finite and not 0 and
+ * |rint(u)|, |rint(v)| <= 2^20; its pixel is (int32(rint(u)), int32(rint(v))), half to even.  Pixel (x, y) is INSIDE iff the
+ * integer point lies in the closed convex hull of the valid rows' pixels; pixels outside the image take part in the hull.
+ * Only integers decide that: int64 cross products, int64 floor / ceil divisions.                                      */
+#define CAMD_HULL_MAX_POINTS 4096 /* rows of one frame, and the largest vertex_capacity */
+/* Stage A, one wavefront per frame, no workgroup barrier; a frame's record depends on its own rows only.
+ * uv: `rows` float64 rows of uv_stride >= 2 doubles; z: `rows` values of z_type CAMD_VALUE_F64 / _F32, or NULL (every z
+ * counts as 1: the mask alone).  start == NULL: frame f owns rows f * (rows / frames) ...; otherwise frames + 1 int64 ON
+ * THE DEVICE, rising, as camd_pnp_points.start.  A range that leaves the rows or is longer than vertex_capacity is read
+ * nowhere and counts as a frame without rows.  keep_last_per_pixel: rows whose pixel is outside w x h are dropped, and of
+ * several valid rows on one pixel only the highest row index takes part, in the hull and in the fit (what a scatter
+ * through camd_uvzs_to_arr2d leaves).  w, h are used for that only.
+ *   hull   gift wrapping from the lowest (x, y); the next vertex is the candidate r for which cross(q - p, r - p) < 0
+ *          against every other q, the farther one of collinear candidates: a total order, so the vertex set is unique.
+ *          vertices: frames x vertex_capacity x 2 int32 (x, y), the first hull_counts[f] of a frame are written.
+ *   plane  sums of uu, uv, u, vv, v, 1, uz, vz, z over the rows that take part, unrounded float64: row i belongs to lane
+ *          i % 64, a lane adds its rows in rising i, the lanes meet in a butterfly (xor 1, 2, ... 32); then with
+ *          mu = su / n, mv, mz alike: cuu = suu - su mu, cvv = svv - sv mv, cuv = suv - su mv, cuz = suz - su mz,
+ *          cvz = svz - sv mz, det = cuu cvv - cuv cuv, a = (cuz cvv - cvz cuv) / det, b = (cvz cuu - cuz cuv) / det,
+ *          c = mz - a mu - b mv.  abc: frames x 3 float64.
+ *   status 1: no row takes part (hull_counts 0, abc NaN); 2: fewer than three rows or !(det > 1e-9 cuu cvv), i.e.
+ *          1 - corr(u, v)^2 <= 1e-9: abc NaN; 4: a row with finite u, v and a valid z beyond 2^20 was left out.        */
+int camd_hull_fit(const double* uv, int uv_stride, const void* z, int z_type, size_t rows, const long long* start, int frames,
+                  int w, int h, int keep_last_per_pixel, int vertex_capacity, int* vertices, int* hull_counts, double* abc,
+                  int* status, void* queue);
+/* Stage B.  out: frames x h x w float32, every pixel written once: inside, float32(x * a + y * b + c) evaluated as
+ * camd_plane_eval does, with a, b, c read from abc ON THE DEVICE (a caller may have overwritten them); outside, 0.
+ * reciprocal != 0: 1.0f / that instead (IEEE division: +inf outside).  Row y is inside from
+ * max(0, min ceil(crossing)) to min(w - 1, max floor(crossing)) over the hull's edges that reach the row.
+ * zero_frames: NULL, or `frames` bytes ON THE DEVICE: a frame whose byte is not 0 is written as zeros throughout,
+ * whatever `reciprocal` says (the frames of a recording that show no board).  queue: the HIP stream of the launch.    */
+int camd_hull_fill(const int* vertices, const int* hull_counts, const double* abc, int vertex_capacity, int frames, int w, int h,
+                   int reciprocal, const uint8_t* zero_frames, float* out, void* queue);
+/* The mask alone from the same spans: frames x h x w uint8, 1 inside, 0 outside.                                       */
+int camd_hull_mask(const int* vertices, const int* hull_counts, int vertex_capacity, int frames, int w, int h, uint8_t* out,
+                   void* queue);
+
 #ifdef __cplusplus
 }
 #endif
