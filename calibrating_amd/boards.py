@@ -7,7 +7,9 @@ guess comes from ``d["corners"]`` / ``d["coarse_corners"]``: any detector's corn
 with ``cam.project_points(board.object_points, T_prev)``.  ``findChessboardCorners`` itself, a heuristic quad search, is
 not provided; ``Chessboard(..., detector="chess")`` finds the guess with this package's own detector
 instead (``imgproc.find_chessboard_corners``; csrc/chessboard.hip), whose contract is not cv2's.
-The marker boards of the reference (ArUco, ChArUco) live in cv2.aruco and are not here.
+``CharucoBoard`` is the reference's ChArUco board with a detector of this package's own as well
+(``imgproc.find_charuco_corners``; csrc/charuco.hip): boards cut by the image or partly covered are found, the caller brings
+the marker dictionary.  The stand-alone ArUco boards of the reference live in cv2.aruco and are not here.
 
 What a board computes on the host -- its object points, its printable image, the pixels of a region of interest -- is
 written from the behaviour the reference shows, which tests/golden/reference_boards.npz records bit for bit.
@@ -219,4 +221,267 @@ class Chessboard(BaseBoard):
         board.calibration_img_info = dict(hw=hw, ppi=ppi, **board.init_kwargs)
         printed_mm = round(square / ppi * 25.4, 2)
         board.calibration_img_name = "checkboard_hw%dx%d_size%smm.png" % (down - 1, across - 1, printed_mm)
+        return board
+
+
+# ---- marker dictionaries (host) ----------------------------------------------------------------------------------------
+MARKER_MIN_BITS, MARKER_MAX_BITS, MARKER_MAX_IDS = 4, 7, 1024
+
+
+def _check_marker_bits(bits):
+    b = np.asarray(bits)
+    if b.ndim != 3 or b.shape[1] != b.shape[2] or not MARKER_MIN_BITS <= b.shape[1] <= MARKER_MAX_BITS:
+        raise ValueError("a marker dictionary is (n_ids, s, s) bits with s = %d .. %d, got %s"
+                         % (MARKER_MIN_BITS, MARKER_MAX_BITS, b.shape))
+    if not 1 <= b.shape[0] <= MARKER_MAX_IDS:
+        raise ValueError("a marker dictionary holds 1 .. %d ids, got %d" % (MARKER_MAX_IDS, b.shape[0]))
+    if b.dtype.kind not in "biu" or ((b != 0) & (b != 1)).any():
+        raise ValueError("marker bits are 0 (black) or 1 (white)")
+    return np.ascontiguousarray(b, np.uint8)
+
+
+def marker_words(bits):
+    """(n_ids, s, s) bits -> (n_ids,) uint64: a marker's rows from the top, each from the left, the first bit highest --
+    bit (r, c) has the weight 2^(s*s - 1 - (r*s + c)).  What ``camd_charuco_detect`` takes as ``dictionary_words``."""
+    b = _check_marker_bits(bits)
+    s = b.shape[1]
+    weights = np.uint64(1) << np.arange(s * s - 1, -1, -1, dtype=np.uint64)
+    return (b.reshape(len(b), -1).astype(np.uint64) * weights).sum(1, dtype=np.uint64)
+
+
+def marker_bytes_list(bits):
+    """(n_ids, s, s) bits -> (n_ids, ceil(s*s / 8), 4) uint8 in the packing ``marker_bits_from_bytes_list`` reads: plane k
+    holds the marker turned k quarter turns (``np.rot90(m, -k)``), bits in row-major order, eight to a byte, the first
+    highest; a last byte that is not full holds its bits in its LOW end."""
+    b = _check_marker_bits(bits)
+    n, s = b.shape[0], b.shape[1]
+    nbytes = (s * s + 7) // 8
+    out = np.zeros((n, nbytes, 4), np.uint8)
+    for k in range(4):
+        flat = np.rot90(b, -k, axes=(1, 2)).reshape(n, -1)
+        for i in range(nbytes):
+            for bit in flat[:, 8 * i:8 * i + 8].T:
+                out[:, i, k] = out[:, i, k] * 2 + bit
+    return out
+
+
+def marker_bits_from_bytes_list(bytes_list, s):
+    """``cv2.aruco.Dictionary.bytesList`` (n_ids, ceil(s*s / 8), 4) -> (n_ids, s, s) uint8 bits, 1 = white: rotation 0
+    (plane 0), bits in row-major order, the first bit the highest of a byte, a last byte that is not full right-aligned.
+    UNPINNED (DESIGN.md section 2): written from recollection of cv2's Dictionary::getBitsFromByteList; no cv2 is at hand
+    to confirm it.  ``boards.marker_bytes_list`` is its inverse."""
+    a = np.asarray(bytes_list)
+    s = int(s)
+    if not MARKER_MIN_BITS <= s <= MARKER_MAX_BITS:
+        raise ValueError("s must be %d .. %d, got %d" % (MARKER_MIN_BITS, MARKER_MAX_BITS, s))
+    nbytes = (s * s + 7) // 8
+    if a.ndim != 3 or a.shape[1:] != (nbytes, 4) or a.dtype.kind not in "iu" or (a < 0).any() or (a > 255).any():
+        raise ValueError("bytes_list of %d x %d markers is (n_ids, %d, 4) bytes, got %s %s" % (s, s, nbytes, a.dtype, a.shape))
+    rot0 = a[:, :, 0].astype(np.uint8)
+    bits = np.zeros((len(a), s * s), np.uint8)
+    for i in range(s * s):
+        byte, pos = divmod(i, 8)
+        width = min(8, s * s - 8 * byte)  # bits the byte holds
+        bits[:, i] = (rot0[:, byte] >> (width - 1 - pos)) & 1
+    return _check_marker_bits(bits.reshape(len(a), s, s))
+
+
+def _splitmix64(state):
+    """one step of the splitmix64 generator: (next state, 64 random bits) -- plain integers, the same on every machine"""
+    state = (state + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    z = state
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return state, z ^ (z >> 31)
+
+
+def marker_distance(a, b=None):
+    """the least Hamming distance of marker a (s, s) to the four turns of marker b; without b: of a to its own three turns"""
+    a = np.asarray(a)
+    turns, b = (range(1, 4), a) if b is None else (range(4), np.asarray(b))
+    return min(int((a != np.rot90(b, k)).sum()) for k in turns)
+
+
+def make_marker_dictionary(n, s, seed=0, min_distance=None):
+    """A deterministic marker dictionary of this package's own (NOT one of cv2's tables): (n, s, s) uint8 bits, 1 = white.
+    Markers are drawn from splitmix64(seed) and kept where they lie at least ``min_distance`` bits (default s*s // 4)
+    from every turn of every marker kept before and from their own three turns, and hold at least s white and s black
+    bits.  The same arguments give the same dictionary everywhere.  ValueError where 100 000 draws do not fill it."""
+    n, s, state = int(n), int(s), int(seed) & 0xFFFFFFFFFFFFFFFF
+    if not MARKER_MIN_BITS <= s <= MARKER_MAX_BITS or not 1 <= n <= MARKER_MAX_IDS:
+        raise ValueError("n = 1 .. %d markers of s = %d .. %d bits a side, got n = %d, s = %d"
+                         % (MARKER_MAX_IDS, MARKER_MIN_BITS, MARKER_MAX_BITS, n, s))
+    need = s * s // 4 if min_distance is None else int(min_distance)
+    kept, turns = [], []
+    for _ in range(100000):
+        if len(kept) == n:
+            break
+        state, z = _splitmix64(state)
+        m = np.array([(z >> (s * s - 1 - i)) & 1 for i in range(s * s)], np.uint8).reshape(s, s)
+        if not s <= int(m.sum()) <= s * s - s or marker_distance(m) < need:
+            continue
+        if turns and int((np.stack(turns) != m).sum((1, 2)).min()) < need:
+            continue
+        kept.append(m)
+        turns += [np.rot90(m, k) for k in range(4)]
+    if len(kept) < n:
+        raise ValueError("no %d markers of %d x %d bits at distance %d from seed %d; ask for fewer or a smaller distance"
+                         % (n, s, s, need, seed))
+    return np.stack(kept)
+
+
+# ---- the ChArUco board -------------------------------------------------------------------------------------------------
+CHARUCO_MIN_POINTS = 11  # boards.py:389
+NO_DICTIONARY = ("CharucoBoard: no marker dictionary -- cv2's tables are not part of this package.  Pass dictionary=(n_ids, s, "
+                 "s) bits: boards.marker_bits_from_bytes_list(cv2.aruco.getPredefinedDictionary(tag).bytesList, s) from a machine "
+                 "with cv2.aruco, or boards.make_marker_dictionary(n, s) for a board of this package's own")
+
+
+class CharucoBoard(BaseBoard):
+    def __init__(self, square_xy=(9, 5), square_size_mm=44.95, marker_size_mm=22.475, dictionary=None, first_id=0,
+                 invert_color=False, using_marker_corner=False):
+        """The reference's ChArUco board (boards.py:311-353) with the marker dictionary supplied by the caller.
+        ``square_xy``: squares (across, down), the top-left one black; markers sit in the white squares, their ids
+        ascending from ``first_id`` in row-major order.  ``object_points``: {id: (1, 3) float32 metres} of the inner
+        corners, id = y * (across - 1) + x at ((x + 1) * square, (y + 1) * square, 0), their centre moved to the origin.
+        The layout is cv2's current one as far as known and UNPINNED.  ``invert_color``: the board
+        is printed black on white inverted; images are inverted before detection (boards.py:357-358)."""
+        if dictionary is None:
+            raise ValueError(NO_DICTIONARY)
+        if using_marker_corner:
+            raise NotImplementedError("CharucoBoard(using_marker_corner=True): the markers' own corners are not detected; "
+                                      "only the board's inner corners are")
+        self.dictionary = _check_marker_bits(dictionary)
+        sx, sy = (int(v) for v in square_xy)
+        self.square_xy, self.first_id, self.invert_color = (sx, sy), int(first_id), bool(invert_color)
+        self.square_size_mm, self.marker_size_mm = square_size_mm, marker_size_mm
+        self.init_kwargs = dict(square_xy=square_xy, square_size_mm=square_size_mm, marker_size_mm=marker_size_mm,
+                                first_id=first_id, using_marker_corner=False, invert_color=invert_color)
+        from fractions import Fraction
+        ratio = Fraction(float(marker_size_mm) / float(square_size_mm)).limit_denominator(64)
+        self.marker_ratio = (ratio.numerator, ratio.denominator)
+        from . import imgproc
+        imgproc._charuco_arguments(self.square_xy, self.dictionary, self.marker_ratio, self.first_id, 8, 3, 2, 0)
+        x, y = np.meshgrid(np.arange(sx - 1), np.arange(sy - 1))
+        grid = np.zeros(((sx - 1) * (sy - 1), 3), np.float32)
+        grid[:, 0] = (x.ravel() + 1) * (square_size_mm / 1000.0)
+        grid[:, 1] = (y.ravel() + 1) * (square_size_mm / 1000.0)
+        self.object_points = self.set_origin_to_center({i: xyz[None] for i, xyz in enumerate(grid)})
+
+    @property
+    def n_corners(self):
+        return (self.square_xy[0] - 1) * (self.square_xy[1] - 1)
+
+    def marker_squares(self):
+        """[(x, y)] of the squares that carry a marker, in the order of their ids from ``first_id``"""
+        sx, sy = self.square_xy
+        return [(x, y) for y in range(sy) for x in range(sx) if x % 2 != y % 2]
+
+    def _detect(self, images, return_info=False):
+        from . import imgproc
+        if self.invert_color:
+            images = 255 - images
+        return imgproc.find_charuco_corners(images, self.square_xy, self.dictionary, self.marker_ratio, self.first_id,
+                                            return_info=return_info)
+
+    def find_image_points_batch(self, images, return_info=False):
+        """A whole recording in one call: ``images`` (f, h, w) gray or (f, h, w, 3), NumPy or CUDA -> ``(seen, corners)``:
+        (f, n) bool and (f, n, 2) float32 of the same kind -- the inner corners the detector saw in every frame, refined
+        by ``corner_sub_pix`` with the reference's arguments (the seen corners only, as ragged rows), NaN where unseen.
+        ``return_info`` adds ``found`` (f,), ``marker_ids`` (f, across * down), ``status`` and ``counts``."""
+        import torch
+        from . import imgproc
+        found, coarse, marker_ids, status, counts = self._detect(images, return_info=True)
+        if coarse.ndim != 3:
+            raise ValueError("images must be a batch (f, h, w) or (f, h, w, 3), got %s" % (tuple(images.shape),))
+        was_np = isinstance(coarse, np.ndarray)
+        c = torch.from_numpy(coarse).to(imgproc.to_device(images).device) if was_np else coarse
+        seen = ~torch.isnan(c[..., 0])
+        lengths = seen.sum(1).cpu().numpy()
+        corners = torch.full_like(c, float("nan"))
+        if int(lengths.sum()):
+            dev_images = images if not was_np else torch.from_numpy(np.ascontiguousarray(images)).to(c.device)
+            corners[seen] = imgproc.corner_sub_pix(dev_images, c[seen], SUBPIX_WIN, SUBPIX_ZERO_ZONE, SUBPIX_CRITERIA, counts=lengths)
+        if was_np:
+            seen, corners = seen.cpu().numpy(), corners.cpu().numpy()
+        return (seen, corners, found, marker_ids, status, counts) if return_info else (seen, corners)
+
+    def to_frames(self, seen, corners, keys=None):
+        """What ``find_image_points_batch`` returned -> {key: dict(ids, image_points, object_points)} as
+        ``Cam.from_detections`` takes it: the reference's id -> points dictionaries of the frames that show at least 11
+        corners (boards.py:389).  ``keys``: one per frame, default 0 .. f - 1."""
+        seen = np.asarray(seen.cpu() if hasattr(seen, "is_cuda") else seen)
+        corners = np.asarray(corners.cpu() if hasattr(corners, "is_cuda") else corners)
+        keys = range(len(seen)) if keys is None else list(keys)
+        if len(keys) != len(seen):
+            raise ValueError("%d keys for %d frames" % (len(keys), len(seen)))
+        frames = {}
+        for key, s, c in zip(keys, seen, corners):
+            ids = np.flatnonzero(s)
+            if len(ids) >= CHARUCO_MIN_POINTS:
+                frames[key] = dict(ids=ids, image_points={int(i): c[i][None] for i in ids},
+                                   object_points={int(i): self.object_points[int(i)] for i in ids})
+        return frames
+
+    def find_image_points(self, d):
+        """boards.py:355-395 with this package's detector in place of cv2.aruco's: detects the board in ``d["img"]``,
+        refines the seen inner corners with ``corner_sub_pix`` and, where at least 11 are seen, sets ``d["ids"]``,
+        ``d["image_points"]`` and ``d["object_points"]`` ({id: (1, 2)} and {id: (1, 3)}) and ``d["corners"]`` (k, 1, 2).
+        ``d["marker_ids"]`` is set in every case: the ids decoded, in row-major order of their squares.  A record whose
+        board is not found or shows fewer corners is left without ``image_points``."""
+        img = d["img"]
+        seen, corners, found, marker_ids, _, _ = self.find_image_points_batch(img[None], return_info=True)
+        if not isinstance(seen, np.ndarray):
+            seen, corners, marker_ids = seen.cpu().numpy(), corners.cpu().numpy(), marker_ids.cpu().numpy()
+        d["marker_ids"] = marker_ids[0][marker_ids[0] >= 0]
+        frames = self.to_frames(seen, corners)
+        if 0 in frames:
+            d.update(frames[0], corners=corners[0][seen[0]][:, None])
+
+    def draw(self, square_px, margin_px=0):
+        """the board as a picture, host NumPy: (down * square_px + 2 margin, across * square_px + 2 margin) uint8, white
+        paper, a marker's cells ``round``-ed to whole pixels inside its square"""
+        sx, sy = self.square_xy
+        q, m, s = int(square_px), int(margin_px), self.dictionary.shape[1]
+        img = np.full((sy * q + 2 * m, sx * q + 2 * m), 255, np.uint8)
+        num, den = self.marker_ratio
+        side = q * num // den
+        edges = (q - side) // 2 + np.rint(np.arange(s + 3) * side / (s + 2)).astype(int)
+        ids = {sq: k for k, sq in enumerate(self.marker_squares())}
+        for y in range(sy):
+            for x in range(sx):
+                cell = img[m + y * q:m + (y + 1) * q, m + x * q:m + (x + 1) * q]
+                if x % 2 == y % 2:
+                    cell[:] = 0
+                    continue
+                k = self.first_id + ids[(x, y)]
+                if k >= len(self.dictionary):
+                    raise ValueError("the board's marker %d is not in a dictionary of %d ids" % (k, len(self.dictionary)))
+                full = np.zeros((s + 2, s + 2), np.uint8)
+                full[1:-1, 1:-1] = self.dictionary[k]
+                for r in range(s + 2):
+                    for c in range(s + 2):
+                        cell[edges[r]:edges[r + 1], edges[c]:edges[c + 1]] = 255 * full[r, c]
+        return 255 - img if self.invert_color else img
+
+    @classmethod
+    def build_with_calibration_img(cls, hw=(2480, 3508), n=10, ppi=300, dictionary=None, seed=0, invert_color=False, **init_kwargs):
+        """A board with its printable picture (boards.py:406-441), host NumPy: squares of ``max(hw) // n`` pixels, as many
+        whole ones as fit, markers of 0.75 of a square, the board centred on white paper.  ``dictionary=None`` makes one
+        with ``make_marker_dictionary(markers, 4, seed)``.  ``calibration_img`` is (h, w) uint8."""
+        height, width = int(hw[0]), int(hw[1])
+        size = max(height, width) // n
+        size_mm = round(size / ppi * 25.4, 2)
+        sx, sy = width // size, height // size
+        if dictionary is None:
+            dictionary = make_marker_dictionary(init_kwargs.get("first_id", 0) + (sx * sy) // 2, 4, seed)
+        init_kwargs.update(square_xy=(sx, sy), square_size_mm=size_mm, marker_size_mm=size_mm * 0.75, dictionary=dictionary,
+                           invert_color=invert_color)
+        board = cls(**init_kwargs)
+        img = np.full((height, width), 0 if invert_color else 255, np.uint8)
+        top, left = (height - sy * size) // 2, (width - sx * size) // 2
+        img[top:top + sy * size, left:left + sx * size] = board.draw(size)
+        board.calibration_img = img
+        board.calibration_img_info = dict(hw=hw, ppi=ppi, seed=seed, **board.init_kwargs)
+        board.calibration_img_name = "charuco_square_x%dy%d_size%smm.png" % (sx, sy, size_mm)
         return board

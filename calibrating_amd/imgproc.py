@@ -643,3 +643,83 @@ def find_chessboard_corners(images, pattern, relative=8, nms_radius=3, return_in
     if was_np and not batched:
         out = (bool(out[0]),) + tuple(out[1:])
     return out
+
+
+# ---- ChArUco boards, cut or partly covered ones included (csrc/charuco.hip; a contract of our own) ----
+CHARUCO_MIN_SQUARES, CHARUCO_MAX_SQUARES, CHARUCO_MAX_RATIO_DEN, CHARUCO_MAX_IDS = 3, 16, 64, 1024
+CHARUCO_FEW, CHARUCO_OVERFLOW, CHARUCO_NO_LATTICE, CHARUCO_NO_CONSENSUS = 1, 2, 4, 8  # find_charuco_corners' status; 0 = found
+
+
+def _charuco_arguments(squares_xy, dictionary, marker_ratio, first_id, relative, nms_radius, min_markers, max_bit_errors):
+    """(sx, sy, words (n_ids,) uint64, s, num, den, first_id, relative, nms_radius, min_markers, max_bit_errors) within
+    the detector's limits, or ValueError"""
+    from . import boards
+    try:
+        sx, sy = squares_xy
+        num, den = marker_ratio
+    except (TypeError, ValueError):
+        raise ValueError("squares_xy must be the squares (across, down) and marker_ratio two integers (numerator, denominator), "
+                         "got %r and %r" % (squares_xy, marker_ratio))
+    for name, v in (("squares across", sx), ("squares down", sy), ("the ratio's numerator", num), ("the ratio's denominator", den),
+                    ("first_id", first_id), ("min_markers", min_markers), ("max_bit_errors", max_bit_errors)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    _, _, relative, nms_radius = _chess_arguments((2, 2), relative, nms_radius)
+    sx, sy, num, den, first_id, min_markers, max_bit_errors = (int(v) for v in (sx, sy, num, den, first_id, min_markers, max_bit_errors))
+    if not (CHARUCO_MIN_SQUARES <= sx <= CHARUCO_MAX_SQUARES and CHARUCO_MIN_SQUARES <= sy <= CHARUCO_MAX_SQUARES):
+        raise ValueError("a board of %d x %d squares; the detector takes %d .. %d each way"
+                         % (sx, sy, CHARUCO_MIN_SQUARES, CHARUCO_MAX_SQUARES))
+    words = boards.marker_words(dictionary)
+    s = int(np.shape(dictionary)[1])
+    if not 0 < num < den <= CHARUCO_MAX_RATIO_DEN:
+        raise ValueError("marker_ratio %d / %d: a marker's share of its square is 0 < numerator < denominator <= %d"
+                         % (num, den, CHARUCO_MAX_RATIO_DEN))
+    if first_id < 0 or first_id + (sx * sy) // 2 > len(words):
+        raise ValueError("the board's %d markers from id %d on do not fit a dictionary of %d ids" % ((sx * sy) // 2, first_id, len(words)))
+    if min_markers < 1 or not 0 <= max_bit_errors <= s * s:
+        raise ValueError("min_markers >= 1 and max_bit_errors 0 .. %d, got %d and %d" % (s * s, min_markers, max_bit_errors))
+    return sx, sy, words, s, num, den, first_id, relative, nms_radius, min_markers, max_bit_errors
+
+
+def find_charuco_corners(images, squares_xy, dictionary, marker_ratio=(1, 2), first_id=0, relative=8, nms_radius=3, min_markers=2,
+                         return_info=False, max_bit_errors=0):
+    """The inner corners of a ChArUco board of ``squares_xy`` = (across, down) squares from the image alone, on the GPU,
+    for every frame at once, boards cut by the image or partly covered included -> ``(found, corners)``: bool and
+    float32 (n, 2) for one image, (f,) and (f, n, 2) for a batch, NumPy or CUDA like ``images``; n = (across - 1) *
+    (down - 1), row id = y * (across - 1) + x; whole pixels -- seeds for ``corner_sub_pix`` -- and NaN where a corner was
+    not seen.  The detector is this package's own, NOT cv2.aruco's: the ChESS response and
+    peaks of ``find_chessboard_corners``, then a lattice grown over whatever part of the board is in view, the markers
+    in its cells decoded against ``dictionary`` and the numbering most markers agree on.
+
+    ``dictionary``: (n_ids, s, s) bits, 1 = white, s = 4 .. 7, at most 1024 ids (``boards.make_marker_dictionary``,
+    ``boards.marker_bits_from_bytes_list``); the board's markers are ``first_id`` onward in row-major order of its white
+    squares, the top-left square black.  ``marker_ratio``: a marker's side as a share of its square, two integers.
+    ``min_markers``: decoded markers that must agree.  ``max_bit_errors``: bits a marker may differ from its entry.
+    ``return_info``: ``(found, corners, marker_ids, status, counts)`` -- marker_ids int32 (across * down,) per square, -1
+    where none was decoded; status 0 found, 1 fewer than 5 candidates, 2 more than the 1024 kept, 4 no lattice, 8 no
+    numbering enough markers agree on; counts: the candidates."""
+    import torch
+    sx, sy, words, s, num, den, first_id, relative, nms_radius, min_markers, max_bit_errors = _charuco_arguments(
+        squares_xy, dictionary, marker_ratio, first_id, relative, nms_radius, min_markers, max_bit_errors)
+    check_array(images, "images")
+    if images.ndim in (2, 3, 4) and max(images.shape[-3:-1] if images.shape[-1] == 3 else images.shape[-2:]) > CHESS_MAX_SIDE:
+        raise ValueError("images of %s; the detector takes sides up to %d" % (tuple(images.shape), CHESS_MAX_SIDE))
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    if w < 3 or h < 3:
+        raise ValueError("images of %d x %d; the detector takes sides from 3" % (w, h))
+    r, rmax = _chess_response(gray, f, h, w, pitch, stride)
+    peaks, counts = _chess_peaks(r, rmax, relative, nms_radius)
+    corners = torch.empty((f, (sx - 1) * (sy - 1), 2), dtype=torch.float32, device=gray.device)
+    marker_ids = torch.empty((f, sx * sy), dtype=torch.int32, device=gray.device)
+    status = torch.empty(f, dtype=torch.int32, device=gray.device)
+    words_t = torch.from_numpy(words.view(np.int64)).to(gray.device)
+    call("camd_charuco_detect", gray.device, peaks.data_ptr(), counts.data_ptr(), gray.data_ptr(), w, h, pitch, stride, f, sx, sy,
+         num, den, words_t.data_ptr(), len(words), s, first_id, min_markers, max_bit_errors, corners.data_ptr(),
+         marker_ids.data_ptr(), status.data_ptr(), what="find_charuco_corners")
+    out = (status == 0, corners, marker_ids, status, counts)
+    if not batched:
+        out = tuple(v[0] for v in out)
+    out = to_caller(out if return_info else out[:2], was_np)
+    if was_np and not batched:
+        out = (bool(out[0]),) + tuple(out[1:])
+    return out

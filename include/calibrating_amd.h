@@ -785,6 +785,37 @@ int camd_chess_peaks(const int16_t* response, const int* response_max, int w, in
 int camd_chess_lattice(const int* peaks, const int* counts, int w, int h, int frames, int across, int down, float* corners,
                        int* status, void* queue);
 
+/* ---- the inner corners of a ChArUco board by id, cut or partly covered boards included (csrc/charuco.hip) ----
+ * Stands where the reference calls cv2.aruco.detectMarkers / interpolateCornersCharuco (boards.py:359-368) with a contract
+ * of its OWN, every value an integer, restated in NumPy by tests/charuco_ref.py.  peaks and
+ * counts are camd_chess_peaks' of the same frames; gray as for camd_chess_response.  One wavefront per frame.
+ *   Board: squares_x x squares_y squares, the top-left one black; markers of s x s bits plus a black ring of one cell,
+ *   marker_num / marker_den of a square wide, centred in the squares with x % 2 != y % 2, their ids ascending from
+ *   first_id in row-major order; dictionary_words[id]: bit (r, c) of weight 2^(s*s - 1 - (r*s + c)), 1 = white.  Inner
+ *   corner y * (squares_x - 1) + x lies between squares (x, y) and (x + 1, y + 1).
+ *   Lattice: seeds in order of |m p - sum p|^2; a seed's steps are u to one of its 16 nearest peaks and v to one of the 16
+ *   nearest with 4 cross(u, v)^2 >= |u|^2 |v|^2, the first pair (u outermost) whose fourth corner has a peak within
+ *   min(|u|, |v|) / 4 and in whose cell a marker of the board decodes; u, v swapped where cross(u, v) < 0.  Breadth first
+ *   as camd_chess_lattice, a peak accepted within an eighth of the step, labels -15 .. 15, at most 320.
+ *   Decode: sample (a, b) of the (s + 2)^2 lies at the bilinear blend of the cell's corners with weights A / D, D =
+ *   2 den (s + 2), A[a] = den (s + 2) + num (2 a + 1 - (s + 2)), rounded to a pixel; its value is the sum of the 3 x 3
+ *   pixels there; a bit is 1 where 2 value > lo + hi of the cell's extremes, hi - lo >= 9 * 40; the ring is all 0; the
+ *   s*s bits turned 0 .. 3 quarter turns (np.rot90) against every id: the least (errors, id, turn) within max_bit_errors.
+ *   Vote: a marker fixes the turn and the offset of lattice against board; the one most markers cast (the lowest of
+ *   equals) stands where at least min_markers cast it and no more cast another.  Else the lattice's peaks seed no more
+ *   and the next seed is tried: 32 seeds scanned, 4 lattices grown.
+ * corners: frames x n x 2 float32, n = (squares_x - 1) (squares_y - 1), integer-valued, NaN where unseen; marker_ids:
+ * frames x squares_x squares_y int32, the id decoded in a square, -1 where none; status: 0 found, 1 counts < 5, 2 counts >
+ * CAMD_CHESS_CAPACITY, 4 no seed cell, 8 no vote stood.  Outside the limits below CAMD_ERR_UNSUPPORTED.             */
+#define CAMD_CHARUCO_MIN_SQUARES 3
+#define CAMD_CHARUCO_MAX_SQUARES 16
+#define CAMD_CHARUCO_MAX_RATIO_DEN 64
+#define CAMD_CHARUCO_MAX_IDS 1024
+int camd_charuco_detect(const int* peaks, const int* counts, const uint8_t* gray, int w, int h, size_t pitch, size_t stride,
+                        int frames, int squares_x, int squares_y, int marker_num, int marker_den,
+                        const unsigned long long* dictionary_words, int n_ids, int s, int first_id, int min_markers,
+                        int max_bit_errors, float* corners, int* marker_ids, int* status, void* queue);
+
 /* ---- sparse samples filled by their plane inside their convex hull, batched over frames (csrc/hull.hip) ----
  * Stands where the reference's interpolate_uvzs(..., constrained_type="convex_hull") calls cv2.convexHull and
  * cv2.drawContours (utils.py:364-367) with a mask contract of its OWN (UNPINNED against cv2,
