@@ -74,6 +74,10 @@ class PnpPoints(ctypes.Structure):  # camd_pnp_points
                 ("image_stride", c_int), ("object_shared", c_int), ("frames", c_int)]
 
 
+class CharucoBoards(ctypes.Structure):  # camd_charuco_boards
+    _fields_ = [("n", c_int), ("first_id", c_int * 8)]
+
+
 class StereoRig(ctypes.Structure):  # camd_stereo_rig
     _fields_ = [("points1", PnpPoints), ("points2", PnpPoints), ("K1", c_void_p), ("dist1", c_void_p), ("K2", c_void_p),
                 ("dist2", c_void_p), ("used", c_void_p), ("state", c_void_p), ("poses", c_void_p), ("candidate", c_void_p),
@@ -227,6 +231,10 @@ SIGNATURES = {
     "camd_chess_lattice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "camd_charuco_detect": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int, c_int, c_int, c_int,
                                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_charuco_detect_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int, c_int, c_int,
+                                          c_int, c_void_p, c_int, c_int, ctypes.POINTER(CharucoBoards), c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    "camd_laplacian_sums": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p]),
     "camd_hull_fit": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_hull_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

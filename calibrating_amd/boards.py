@@ -485,3 +485,167 @@ class CharucoBoard(BaseBoard):
         board.calibration_img_info = dict(hw=hw, ppi=ppi, seed=seed, **board.init_kwargs)
         board.calibration_img_name = "charuco_square_x%dy%d_size%smm.png" % (sx, sy, size_mm)
         return board
+
+
+# ---- several boards in one picture -------------------------------------------------------------------------------------
+NOT_A_SET = ("MultiBoards.find_image_points_batch: the boards are no set -- ChArUco boards of the same squares, sizes and "
+             "dictionary with marker ids apart, 8 at the most -- so there is no one-pass detection for them; call "
+             "find_image_points frame by frame, which falls back to each board's own detector")
+
+
+class MultiBoards(BaseBoard):
+    def __init__(self, boards, imgs=None, cam=None):
+        """Several boards that stand fixed to each other, used as ONE target (the reference's multi_boards.py:15-75).
+        ``boards``: a list, or a dict taken in the order of its sorted keys.  ``imgs`` and ``cam``: pictures that show
+        EVERY board and a calibrated camera, see ``add_board_imgs``; without them ``object_points`` is not set and only
+        detection works.  Boards that form a SET -- ``CharucoBoard``s of the same squares, sizes, colour and dictionary
+        (the same object or equal bits) whose marker ids lie apart, 8 at the most -- are detected in one pass
+        (``imgproc.find_charuco_boards``); any other mix goes board by board through each board's own
+        ``find_image_points``, as the reference loops, with that detector's limits.  ``vis_img`` is not provided."""
+        if isinstance(boards, dict):
+            boards = [boards[k] for k in sorted(boards)]
+        self.boards = list(boards)
+        self.Ts_all = []
+        self.first_ids = self._set_first_ids()
+        if imgs is not None:
+            self.add_board_imgs(imgs, cam)
+
+    def _set_first_ids(self):
+        """the boards' first marker ids where they form a set, else None"""
+        from . import imgproc
+        bs = self.boards
+        if not 1 <= len(bs) <= imgproc.CHARUCO_MAX_BOARDS or not all(isinstance(b, CharucoBoard) for b in bs):
+            return None
+        a = bs[0]
+        for b in bs[1:]:
+            if (b.square_xy, b.marker_ratio, b.invert_color, b.square_size_mm, b.marker_size_mm) != (
+                    a.square_xy, a.marker_ratio, a.invert_color, a.square_size_mm, a.marker_size_mm):
+                return None
+            if b.dictionary is not a.dictionary and not np.array_equal(b.dictionary, a.dictionary):
+                return None
+        try:
+            return imgproc._charuco_set([b.first_id for b in bs], (a.square_xy[0] * a.square_xy[1]) // 2, len(a.dictionary))
+        except ValueError:
+            return None
+
+    def add_board_imgs(self, imgs, cam=None):
+        """multi_boards.py:24-53: every picture gives each board's pose in board 0 (what ``cam.get_calibration_board_T``
+        gives per board, a set detected in one pass; a picture must show them all), the poses of all pictures so far are averaged (``geometry.mean_Ts``) and
+        ``object_points`` becomes {(boardi, id): points in board 0's frame}, their centre moved to the origin."""
+        from . import geometry, pointcloud
+        boards = self.boards
+        if hasattr(imgs, "ndim") and imgs.ndim <= 3:
+            imgs = [imgs]
+        if cam is None:
+            cam = self.cam
+        else:
+            self.cam = cam
+        for img in imgs:
+            records = self._board_records(img, cam)
+            missing = [boardi for boardi, d in enumerate(records) if "T" not in d]
+            if missing:
+                raise ValueError("MultiBoards.add_board_imgs: a picture must show every board, boards %r were not found" % (missing,))
+            Ts_in_cam = [d["T"] for d in records]
+            T_cam_in_board0 = np.linalg.inv(Ts_in_cam[0])
+            self.Ts_all.append([T_cam_in_board0 @ T for T in Ts_in_cam])
+        self.Ts = [geometry.mean_Ts([Ts[boardi] for Ts in self.Ts_all]) for boardi in range(len(boards))]
+        new_obj_points = {}
+        for boardi, board in enumerate(boards):
+            object_points = board.object_points
+            if not isinstance(object_points, dict):
+                object_points = {None: object_points}
+            for k, object_point in object_points.items():
+                new_obj_points[(boardi, k)] = pointcloud.apply_T_to_point_cloud(self.Ts[boardi], np.asarray(object_point))
+        self.object_points = self.set_origin_to_center(new_obj_points)
+
+    def _board_records(self, img, cam):
+        """``cam.get_calibration_board_T(img, board)`` for every board; a set is detected in one pass over the picture --
+        a board's own detector looks for one board and does not reach the outer ones of several"""
+        if self.first_ids is None:
+            return [cam.get_calibration_board_T(img, board) for board in self.boards]
+        seen, corners = self.find_image_points_batch(img[None])
+        if not isinstance(seen, np.ndarray):
+            seen, corners = seen.cpu().numpy(), corners.cpu().numpy()
+        records = []
+        for board, s, c in zip(self.boards, seen[0], corners[0]):
+            d = dict(img=img)
+            d.update(board.to_frames(s[None], c[None]).get(0, {}))
+            if "image_points" in d:
+                d.update(cam.perspective_n_point(d["image_points"], d["object_points"]))
+            records.append(d)
+        return records
+
+    def find_image_points_batch(self, images, return_info=False):
+        """A whole recording in one call, for boards that form a set: ``images`` (f, h, w) gray or (f, h, w, 3), NumPy or
+        CUDA -> ``(seen, corners)``: (f, B, n) bool and (f, B, n, 2) float32 of the same kind -- one detection pass for all
+        boards, then the seen corners refined by ``corner_sub_pix`` with the reference's arguments as ragged rows; NaN
+        where unseen.  ``return_info`` adds ``marker_ids`` (f, B, across * down), ``status`` (f, B) and ``counts`` (f,)."""
+        import torch
+        from . import imgproc
+        if self.first_ids is None:
+            raise ValueError(NOT_A_SET)
+        a = self.boards[0]
+        if getattr(images, "ndim", 0) not in (3, 4) or (images.ndim == 3 and images.shape[-1] == 3):
+            raise ValueError("images must be a batch (f, h, w) or (f, h, w, 3), got %s" % (tuple(getattr(images, "shape", ())),))
+        seen_in = 255 - images if a.invert_color else images
+        _, coarse, marker_ids, status, counts = imgproc.find_charuco_boards(seen_in, a.square_xy, a.dictionary, self.first_ids,
+                                                                            a.marker_ratio, return_info=True)
+        was_np = isinstance(coarse, np.ndarray)
+        c = torch.from_numpy(coarse).to(imgproc.to_device(images).device) if was_np else coarse
+        seen = ~torch.isnan(c[..., 0])
+        lengths = seen.sum((1, 2)).cpu().numpy()
+        corners = torch.full_like(c, float("nan"))
+        if int(lengths.sum()):
+            dev_images = images if not was_np else torch.from_numpy(np.ascontiguousarray(images)).to(c.device)
+            corners[seen] = imgproc.corner_sub_pix(dev_images, c[seen], SUBPIX_WIN, SUBPIX_ZERO_ZONE, SUBPIX_CRITERIA, counts=lengths)
+        if was_np:
+            seen, corners = seen.cpu().numpy(), corners.cpu().numpy()
+        return (seen, corners, marker_ids, status, counts) if return_info else (seen, corners)
+
+    def _points_by_board(self, seen, corners):
+        """{(boardi, id): (1, 2)} of one frame's rows, of the boards that show at least 11 corners (boards.py:389)"""
+        points = {}
+        for boardi, (s, c) in enumerate(zip(seen, corners)):
+            ids = np.flatnonzero(s)
+            if len(ids) >= CHARUCO_MIN_POINTS:
+                points.update({(boardi, int(i)): c[i][None] for i in ids})
+        return points
+
+    def to_frames(self, seen, corners, keys=None):
+        """What ``find_image_points_batch`` returned -> {key: dict(ids, image_points, object_points)} as
+        ``Cam.from_detections`` takes it, ids = (boardi, id), of the frames in which at least one board shows 11 corners;
+        needs ``object_points`` (``add_board_imgs``).  ``keys``: one per frame, default 0 .. f - 1."""
+        seen = np.asarray(seen.cpu() if hasattr(seen, "is_cuda") else seen)
+        corners = np.asarray(corners.cpu() if hasattr(corners, "is_cuda") else corners)
+        keys = range(len(seen)) if keys is None else list(keys)
+        if len(keys) != len(seen):
+            raise ValueError("%d keys for %d frames" % (len(keys), len(seen)))
+        frames = {}
+        for key, s, c in zip(keys, seen, corners):
+            points = self._points_by_board(s, c)
+            if points:
+                frames[key] = dict(ids=sorted(points), image_points=points, object_points={i: self.object_points[i] for i in points})
+        return frames
+
+    def find_image_points(self, d):
+        """multi_boards.py:55-75: ``d["image_points"]`` and ``d["object_points"]`` become {(boardi, id): points} over the
+        boards found in ``d["img"]``; a record in which no board is found is left alone.  A set is detected in one pass."""
+        all_image_points = {}
+        if self.first_ids is not None:
+            seen, corners = self.find_image_points_batch(d["img"][None])
+            if not isinstance(seen, np.ndarray):
+                seen, corners = seen.cpu().numpy(), corners.cpu().numpy()
+            all_image_points = self._points_by_board(seen[0], corners[0])
+        else:
+            for boardi, board in enumerate(self.boards):
+                d_ = dict(img=d["img"])
+                board.find_image_points(d_)
+                image_points = d_.get("image_points")
+                if image_points is None:
+                    continue
+                if not isinstance(image_points, dict):
+                    image_points = {None: image_points}
+                for k, image_point in image_points.items():
+                    all_image_points[(boardi, k)] = image_point
+        if len(all_image_points) > 0:
+            d.update(image_points=all_image_points, object_points={i: self.object_points[i] for i in all_image_points})

@@ -723,3 +723,99 @@ def find_charuco_corners(images, squares_xy, dictionary, marker_ratio=(1, 2), fi
     if was_np and not batched:
         out = (bool(out[0]),) + tuple(out[1:])
     return out
+
+
+# ---- several ChArUco boards of one set in a frame (csrc/charuco.hip, k_charuco_multi) ----
+CHARUCO_MAX_BOARDS = 8
+
+
+def _charuco_set(first_ids, markers, n_ids):
+    """the boards' first ids as a list of 1 .. 8 integers whose ranges of ``markers`` ids lie inside the dictionary and
+    apart from each other, or ValueError"""
+    try:
+        ids = list(first_ids)
+    except TypeError:
+        raise ValueError("first_ids must be the boards' first marker ids, one per board, got %r" % (first_ids,))
+    if not 1 <= len(ids) <= CHARUCO_MAX_BOARDS:
+        raise ValueError("a set of %d boards; the detector takes 1 .. %d" % (len(ids), CHARUCO_MAX_BOARDS))
+    for v in ids:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("first_ids must be integers, got %r" % (v,))
+    ids = [int(v) for v in ids]
+    for k, a in enumerate(ids):
+        if a < 0 or a + markers > n_ids:
+            raise ValueError("board %d's %d markers from id %d on do not fit a dictionary of %d ids" % (k, markers, a, n_ids))
+        for j, b in enumerate(ids[:k]):
+            if a < b + markers and b < a + markers:
+                raise ValueError("boards %d and %d share marker ids: %d .. %d and %d .. %d"
+                                 % (j, k, b, b + markers - 1, a, a + markers - 1))
+    return ids
+
+
+def find_charuco_boards(images, squares_xy, dictionary, first_ids, marker_ratio=(1, 2), relative=8, nms_radius=3, min_markers=2,
+                        return_info=False, max_bit_errors=0):
+    """Every board of a SET in every frame, in one pass: B = ``len(first_ids)`` boards (1 .. 8) of the same ``squares_xy``,
+    ``marker_ratio`` and ``dictionary``, board b carrying the markers ``first_ids[b]`` onward; the id ranges must lie apart.
+    -> ``(seen, corners)``: bool (B, n) and float32 (B, n, 2) for one image, (f, B, n) and (f, B, n, 2) for a batch,
+    NumPy or CUDA like ``images``; whole pixels, NaN where a corner was not seen, ``seen`` = not NaN.  The response and
+    the peaks of ``find_charuco_corners`` are computed once for all boards; then seeds are tried outward from the
+    centroid of all peaks until every board is found, each lattice numbered by the board most of its markers name (the
+    rules: include/calibrating_amd.h).  With one board it is ``find_charuco_corners`` bit for bit.  The 1024 candidates
+    are per frame, not per board, and the markers' own corners count.
+
+    ``return_info``: ``(seen, corners, marker_ids, status, counts)`` -- marker_ids int32 (f, B, across * down), status
+    int32 (f, B) with ``find_charuco_corners``' values per board (1 and 2 are the frame's), counts (f,)."""
+    import torch
+    sx, sy, words, s, num, den, _, relative, nms_radius, min_markers, max_bit_errors = _charuco_arguments(
+        squares_xy, dictionary, marker_ratio, 0, relative, nms_radius, min_markers, max_bit_errors)
+    ids = _charuco_set(first_ids, (sx * sy) // 2, len(words))
+    check_array(images, "images")
+    if images.ndim in (2, 3, 4) and max(images.shape[-3:-1] if images.shape[-1] == 3 else images.shape[-2:]) > CHESS_MAX_SIDE:
+        raise ValueError("images of %s; the detector takes sides up to %d" % (tuple(images.shape), CHESS_MAX_SIDE))
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    if w < 3 or h < 3:
+        raise ValueError("images of %d x %d; the detector takes sides from 3" % (w, h))
+    r, rmax = _chess_response(gray, f, h, w, pitch, stride)
+    peaks, counts = _chess_peaks(r, rmax, relative, nms_radius)
+    nb = len(ids)
+    corners = torch.empty((f, nb, (sx - 1) * (sy - 1), 2), dtype=torch.float32, device=gray.device)
+    marker_ids = torch.empty((f, nb, sx * sy), dtype=torch.int32, device=gray.device)
+    status = torch.empty((f, nb), dtype=torch.int32, device=gray.device)
+    words_t = torch.from_numpy(words.view(np.int64)).to(gray.device)
+    board_set = _native.CharucoBoards(nb, (ctypes.c_int * CHARUCO_MAX_BOARDS)(*ids))
+    call("camd_charuco_detect_multi", gray.device, peaks.data_ptr(), counts.data_ptr(), gray.data_ptr(), w, h, pitch, stride, f, sx,
+         sy, num, den, words_t.data_ptr(), len(words), s, ctypes.byref(board_set), min_markers, max_bit_errors, corners.data_ptr(),
+         marker_ids.data_ptr(), status.data_ptr(), what="find_charuco_boards")
+    out = (~torch.isnan(corners[..., 0]), corners, marker_ids, status, counts)
+    if not batched:
+        out = tuple(v[0] for v in out)
+    return to_caller(out if return_info else out[:2], was_np)
+
+
+def laplacian_sums(images):
+    """The exact sums behind ``sharpness``: int64 (f, 2) (a batch) or (2,) of S1 = sum L and S2 = sum L^2 over every frame,
+    L the 3 x 3 Laplacian [0 1 0; 1 -4 1; 0 1 0] of the gray image with reflect-101 borders."""
+    import torch
+    _check_image(images, "images")
+    if images.ndim in (2, 3, 4) and min(images.shape[-3:-1] if images.shape[-1] == 3 and images.ndim > 2 else images.shape[-2:]) < 2:
+        raise ValueError("images of %s; the Laplacian's mirrored border takes sides from 2" % (tuple(images.shape),))
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    sums = torch.empty((f, 2), dtype=torch.int64, device=gray.device)
+    call("camd_laplacian_sums", gray.device, gray.data_ptr(), w, h, pitch, stride, f, sums.data_ptr(), what="sharpness")
+    return to_caller(sums if batched else sums[0], was_np)
+
+
+def sharpness(images):
+    """``cv2.Laplacian(gray, cv2.CV_64F).var()`` of every image (reconstruction_with_board.py:9-12): a float for one
+    image, float64 (f,) on the host for a batch.  uint8 gray (h, w) / (f, h, w) or colour (through ``cvt_gray(code="bgr")``),
+    NumPy or CUDA, sides from 2.  The GPU gives the exact integer sums S1, S2 of the Laplacian and of its square
+    (``laplacian_sums``); the variance (N S2 - S1^2) / N^2 is formed here from Python integers, rounded once.  UNPINNED
+    against cv2."""
+    from fractions import Fraction
+    sums = laplacian_sums(images)
+    sums = sums if is_np(sums) else sums.cpu().numpy()
+    colour = images.ndim in (3, 4) and images.shape[-1] == 3
+    h, w = (images.shape[-3:-1] if colour else images.shape[-2:])
+    n = int(h) * int(w)
+    var = [float(Fraction(n * int(s2) - int(s1) ** 2, n * n)) for s1, s2 in sums.reshape(-1, 2)]
+    return var[0] if sums.ndim == 1 else np.array(var, np.float64)

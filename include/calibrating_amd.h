@@ -815,6 +815,39 @@ int camd_charuco_detect(const int* peaks, const int* counts, const uint8_t* gray
                         int frames, int squares_x, int squares_y, int marker_num, int marker_den,
                         const unsigned long long* dictionary_words, int n_ids, int s, int first_id, int min_markers,
                         int max_bit_errors, float* corners, int* marker_ids, int* status, void* queue);
+/* Every board of a SET in every frame, in one pass over one set of peaks (k_charuco_multi; restated by
+ * tests/multiboard_ref.py).  A set: boards->n = B boards, 1 .. CAMD_CHARUCO_MAX_BOARDS, of the same squares, ratio and
+ * dictionary, board b with markers first_id[b] .. first_id[b] + squares_x squares_y / 2 - 1; the ranges lie inside the
+ * dictionary and apart from each other, else CAMD_ERR_UNSUPPORTED.  `boards` is read on the host at the call.
+ *   Seeds in camd_charuco_detect's order; a peak labelled in any lattice grown so far, accepted or not, seeds no more (it
+ *   still counts as scanned).  A seed cell qualifies by a marker of a board not yet found.  Growth as above, over the peaks
+ *   no accepted lattice holds.  Every decoded marker of a board not yet found casts (board, turn, offset); the accept rule
+ *   is the one above on the winning triple (of equals the lowest board, then turn, then offset).  The winner's board is
+ *   found and its rows are written; else the lattice's peaks seed no more and the seed cell's board counts as tried.
+ *   The loop ends when every board is found, the seeds run out, 32 B seeds are scanned or 4 B lattices are grown.
+ *   With B = 1: camd_charuco_detect bit for bit.
+ * corners: frames x B x n x 2 float32; marker_ids: frames x B x squares_x squares_y int32; status: frames x B int32 -- 0
+ * found; 1, 2 (the frame's, as above) for every board; else 8 for a board that was tried, 4 for the rest.
+ * RANGE: the CAMD_CHESS_CAPACITY candidates are per FRAME, not per board, and the markers' own X-junctions count towards
+ * them: a frame in which all the boards together leave more has status 2 for every board.                           */
+#define CAMD_CHARUCO_MAX_BOARDS 8
+typedef struct camd_charuco_boards {
+    int n;
+    int first_id[CAMD_CHARUCO_MAX_BOARDS];
+} camd_charuco_boards;
+int camd_charuco_detect_multi(const int* peaks, const int* counts, const uint8_t* gray, int w, int h, size_t pitch, size_t stride,
+                              int frames, int squares_x, int squares_y, int marker_num, int marker_den,
+                              const unsigned long long* dictionary_words, int n_ids, int s, const camd_charuco_boards* boards,
+                              int min_markers, int max_bit_errors, float* corners, int* marker_ids, int* status, void* queue);
+
+/* ---- the variance of the Laplacian, a picture's sharpness (csrc/sharpness.hip) ----
+ * Stands where the reference calls cv2.Laplacian(gray, cv2.CV_64F).var() (reconstruction_with_board.py:9-12); UNPINNED
+ * against cv2.  L(x, y) = g(x-1, y) + g(x+1, y) + g(x, y-1) + g(x, y+1) - 4 g(x, y), a
+ * neighbour outside the image mirrored about the border pixel (reflect-101: -1 -> 1, w -> w - 2).  sums: frames x 2 int64,
+ * S1 = sum L and S2 = sum L^2 over a frame -- exact integers, so the order of the sum does not show; the variance is
+ * (N S2 - S1^2) / N^2 with N = w h, formed by the caller (N S2 leaves 64 bits at 4K).  gray: frames images of w x h uint8,
+ * rows `pitch` and images `stride` bytes apart.  w, h >= 2 (the mirror needs a second pixel), w h <= 2^31.            */
+int camd_laplacian_sums(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, long long* sums, void* queue);
 
 /* ---- sparse samples filled by their plane inside their convex hull, batched over frames (csrc/hull.hip) ----
  * Stands where the reference's interpolate_uvzs(..., constrained_type="convex_hull") calls cv2.convexHull and
