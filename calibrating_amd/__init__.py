@@ -22,7 +22,7 @@ from .calibrate import (CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALI
                         CALIB_FIX_PRINCIPAL_POINT, CALIB_USE_INTRINSIC_GUESS, CALIB_ZERO_TANGENT_DIST, calibrate_camera)
 from .stereo_calibrate import CALIB_FIX_INTRINSIC, CALIB_USE_EXTRINSIC_GUESS, stereo_calibrate
 from .vis import resolve_max_l1, vis_align, vis_depth, vis_depth_l1, vis_stereo
-from .boards import BaseBoard, CharucoBoard, Chessboard, MultiBoards
+from .boards import ArucoGridBoard, BaseBoard, CharucoBoard, Chessboard, MarkerBoard, MultiBoards
 from .multi_boards import MultiBoardsCam
 from .reconstruction_with_board import convert_cam_to_nerf_json, get_sharpness
 
@@ -34,5 +34,5 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "resolve_max_l1", "vis_stereo", "vis_align", "solve_pnp_batch", "mean_Ts",
            "calibrate_camera", "CALIB_USE_INTRINSIC_GUESS", "CALIB_FIX_PRINCIPAL_POINT", "CALIB_FIX_FOCAL_LENGTH",
            "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
-           "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard", "CharucoBoard",
+           "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard", "CharucoBoard", "MarkerBoard", "ArucoGridBoard",
            "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness"]

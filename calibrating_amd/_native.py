@@ -234,6 +234,12 @@ SIGNATURES = {
     "camd_charuco_detect_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p, c_int, c_int, ctypes.POINTER(CharucoBoards), c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    "camd_dark_mask": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_label_components": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_marker_candidates_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "camd_marker_candidates": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_marker_decode": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_laplacian_sums": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p]),
     "camd_hull_fit": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -9,7 +9,8 @@ not provided; ``Chessboard(..., detector="chess")`` finds the g
 instead (``imgproc.find_chessboard_corners``; csrc/chessboard.hip), whose contract is not cv2's.
 ``CharucoBoard`` is the reference's ChArUco board with a detector of this package's own as well
 (``imgproc.find_charuco_corners``; csrc/charuco.hip): boards cut by the image or partly covered are found, the caller brings
-the marker dictionary.  The stand-alone ArUco boards of the reference live in cv2.aruco and are not here.
+the marker dictionary.  ``MarkerBoard`` and ``ArucoGridBoard`` are boards of stand-alone ArUco markers, found by
+``imgproc.find_markers`` (csrc/markers.hip), a third detector of this package's own.
 
 What a board computes on the host -- its object points, its printable image, the pixels of a region of interest -- is
 written from the behaviour the reference shows, which tests/golden/reference_boards.npz records bit for bit.
@@ -649,3 +650,137 @@ class MultiBoards(BaseBoard):
                     all_image_points[(boardi, k)] = image_point
         if len(all_image_points) > 0:
             d.update(image_points=all_image_points, object_points={i: self.object_points[i] for i in all_image_points})
+
+
+# ---- boards of stand-alone markers ---------------------------------------------------------------------------------------
+class MarkerBoard(BaseBoard):
+    def __init__(self, object_points, dictionary=None, occlusion=True):
+        """Any layout of stand-alone ArUco markers as ONE target.  ``object_points``: {id: (4, 3)} metres, a marker's own
+        top-left, top-right, bottom-right, bottom-left corners; they are kept as they are given.  ``dictionary``:
+        (n_ids, s, s) bits that hold every id (see ``CharucoBoard``).  ``occlusion=False``: a frame counts only when
+        EVERY marker of the board is seen -- the rule of the reference's PredifinedArucoBoard1 (boards.py:285-287), whose
+        coordinate table is not part of this package: pass it here.  Detection is ``imgproc.find_markers`` with its
+        defaults (csrc/markers.hip; a contract of this package's own); for an inverted print
+        hand over ``255 - img``.  ``vis`` and cv2's DetectorParameters are not provided."""
+        if dictionary is None:
+            raise ValueError(NO_DICTIONARY.replace("CharucoBoard", type(self).__name__))
+        self.dictionary = _check_marker_bits(dictionary)
+        points = {}
+        for key, p in dict(object_points).items():
+            p = np.asarray(p, np.float32)
+            if isinstance(key, bool) or int(key) != key or not 0 <= int(key) < len(self.dictionary) or p.shape != (4, 3):
+                raise ValueError("object_points maps a marker id of the dictionary (0 .. %d) to its (4, 3) corners, got %r -> %s"
+                                 % (len(self.dictionary) - 1, key, p.shape))
+            points[int(key)] = p
+        if not points:
+            raise ValueError("a board of no markers")
+        self.object_points = points
+        self.ids = np.array(sorted(points))
+        self.occlusion = bool(occlusion)
+        self.detector = dict(block_radius=8, offset=7, min_side=12, max_side=512, max_bit_errors=0, refine_win=(3, 3))
+
+    def find_image_points_batch(self, images, return_info=False):
+        """A whole recording in one call: ``images`` (f, h, w) gray or (f, h, w, 3), NumPy or CUDA -> ``(seen, corners)``:
+        (f, m) bool and (f, m, 4, 2) float32 of the same kind over the board's m markers in the order of their ids, the
+        corners refined by ``corner_sub_pix``, NaN where unseen.  ``return_info`` adds ``find_markers``' info."""
+        from . import imgproc
+        if getattr(images, "ndim", 0) not in (3, 4) or (images.ndim == 3 and images.shape[-1] == 3):
+            raise ValueError("images must be a batch (f, h, w) or (f, h, w, 3), got %s" % (tuple(getattr(images, "shape", ())),))
+        seen, corners, info = imgproc.find_markers(images, self.dictionary, return_info=True, **self.detector)
+        ids = self.ids if isinstance(seen, np.ndarray) else imgproc.to_device(self.ids, device=seen.device)
+        seen, corners = seen[:, ids], corners[:, ids]
+        return (seen, corners, info) if return_info else (seen, corners)
+
+    def to_frames(self, seen, corners, keys=None):
+        """What ``find_image_points_batch`` returned -> {key: dict(ids, image_points, object_points)} as
+        ``Cam.from_detections`` takes it: {id: (4, 2)} and {id: (4, 3)}, so a frame's rows stand in id order, four per
+        marker.  A frame without a marker is left out, and with ``occlusion=False`` every frame that misses one.
+        ``keys``: one per frame, default 0 .. f - 1."""
+        seen = np.asarray(seen.cpu() if hasattr(seen, "is_cuda") else seen)
+        corners = np.asarray(corners.cpu() if hasattr(corners, "is_cuda") else corners)
+        keys = range(len(seen)) if keys is None else list(keys)
+        if len(keys) != len(seen):
+            raise ValueError("%d keys for %d frames" % (len(keys), len(seen)))
+        frames = {}
+        for key, s, c in zip(keys, seen, corners):
+            at = np.flatnonzero(s)
+            if len(at) == 0 or (not self.occlusion and len(at) != len(self.ids)):
+                continue
+            ids = self.ids[at]
+            frames[key] = dict(ids=ids, image_points={int(i): c[k] for i, k in zip(ids, at)},
+                               object_points={int(i): self.object_points[int(i)] for i in ids})
+        return frames
+
+    def find_image_points(self, d):
+        """Detects the board's markers in ``d["img"]`` and, where the frame counts, sets ``d["ids"]``,
+        ``d["image_points"]`` {id: (4, 2)} and ``d["object_points"]`` {id: (4, 3)}; ``d["valid"]`` says whether it did."""
+        seen, corners = self.find_image_points_batch(d["img"][None])
+        frames = self.to_frames(seen, corners)
+        d["valid"] = 0 in frames
+        if d["valid"]:
+            d.update(frames[0])
+
+
+class ArucoGridBoard(MarkerBoard):
+    def __init__(self, grid_size=(5, 5), marker_length_mm=60.0, marker_separation_mm=10.0, dictionary=None, first_id=0):
+        """The reference's grid of markers (boards.py:516-545) with the dictionary supplied by the caller.  Marker
+        ``first_id + j * gx + i`` has its top-left corner at (i, j) * (length + separation), x to the right, y down, z = 0,
+        its corners top-left, top-right, bottom-right, bottom-left; then the centre of all corners moves to the origin.
+        The layout is cv2.aruco.GridBoard's current one as far as known and UNPINNED."""
+        gx, gy = (int(v) for v in grid_size)
+        first_id = int(first_id)
+        if gx < 1 or gy < 1 or first_id < 0:
+            raise ValueError("a grid of %d x %d markers from id %d" % (gx, gy, first_id))
+        length, pitch = marker_length_mm / 1000.0, (marker_length_mm + marker_separation_mm) / 1000.0
+        square = np.array([[0, 0, 0], [length, 0, 0], [length, length, 0], [0, length, 0]], np.float64)
+        points = {first_id + j * gx + i: (square + (i * pitch, j * pitch, 0)).astype(np.float32) for j in range(gy) for i in range(gx)}
+        if dictionary is not None and first_id + gx * gy > len(dictionary):
+            raise ValueError("the grid's %d markers from id %d on do not fit a dictionary of %d ids" % (gx * gy, first_id, len(dictionary)))
+        super().__init__(points, dictionary)
+        self.object_points = self.set_origin_to_center(self.object_points)
+        self.grid_size, self.first_id = (gx, gy), first_id
+        self.marker_length_mm, self.marker_separation_mm = marker_length_mm, marker_separation_mm
+        self.init_kwargs = dict(grid_size=grid_size, marker_length_mm=marker_length_mm, marker_separation_mm=marker_separation_mm,
+                                first_id=first_id)
+
+    def draw(self, bit_px, margin_px=0):
+        """the sheet as a picture, host NumPy, uint8: a marker is 6 ``bit_px`` wide whatever its bits (its s + 2 cells
+        ``round``-ed to whole pixels), the separation 1 ``bit_px``, white paper, ``margin_px`` around"""
+        gx, gy = self.grid_size
+        s, q, m = self.dictionary.shape[1], int(bit_px), int(margin_px)
+        img = np.full((gy * 7 * q - q + 2 * m, gx * 7 * q - q + 2 * m), 255, np.uint8)
+        edges = np.rint(np.arange(s + 3) * (6 * q) / (s + 2)).astype(int)
+        for j in range(gy):
+            for i in range(gx):
+                full = np.zeros((s + 2, s + 2), np.uint8)
+                full[1:-1, 1:-1] = self.dictionary[self.first_id + j * gx + i]
+                cell = img[m + j * 7 * q:m + j * 7 * q + 6 * q, m + i * 7 * q:m + i * 7 * q + 6 * q]
+                for r in range(s + 2):
+                    for c in range(s + 2):
+                        cell[edges[r]:edges[r + 1], edges[c]:edges[c + 1]] = 255 * full[r, c]
+        return img
+
+    @classmethod
+    def build_with_calibration_img(cls, hw=(2480, 3508), n=6, ppi=300, dictionary=None, seed=0, **init_kwargs):
+        """A grid with its printable picture, host NumPy, in the reference's bit arithmetic (boards.py:579-607): a marker is
+        6 units wide, the separation 1, the margin 1; a unit is ``max(hw) / (7 n + 1)`` pixels (``min(hw)`` for n = 1), and as
+        many markers as fit: ``(int(side / unit + 1e-5) - 1) // 7`` each way.  Sizes in millimetres follow from ``ppi``.
+        ``dictionary=None`` makes one with ``make_marker_dictionary(markers, 4, seed)``.  ``calibration_img`` is (h, w)
+        uint8, the grid drawn with whole-pixel units (``int(unit)``) from a margin of ``round(unit)`` pixels."""
+        height, width = int(hw[0]), int(hw[1])
+        total = n * 7 + 1
+        unit = (min(height, width) if n == 1 else max(height, width)) / total
+        unit_mm = round(unit / ppi * 25.4, 2)
+        gx, gy = (int(width / unit + 1e-5) - 1) // 7, (int(height / unit + 1e-5) - 1) // 7
+        if dictionary is None:
+            dictionary = make_marker_dictionary(init_kwargs.get("first_id", 0) + gx * gy, 4, seed)
+        init_kwargs.update(grid_size=(gx, gy), marker_length_mm=unit_mm * 6, marker_separation_mm=unit_mm * 1, dictionary=dictionary)
+        board = cls(**init_kwargs)
+        margin = int(round(unit))
+        sheet = board.draw(int(unit))
+        img = np.full((height, width), 255, np.uint8)
+        img[margin:margin + sheet.shape[0], margin:margin + sheet.shape[1]] = sheet
+        board.calibration_img = img
+        board.calibration_img_info = dict(hw=hw, ppi=ppi, seed=seed, bit_px=int(unit), margin_px=margin, **board.init_kwargs)
+        board.calibration_img_name = "aruco_grid_x%dy%d_marker%smm_separation%smm.png" % (gx, gy, unit_mm * 6, unit_mm * 1)
+        return board

@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "chess_wave.hpp"
+#include "marker_decode.hpp"
 
 namespace camd {
 
@@ -24,7 +25,6 @@ constexpr int CHARUCO_RANGE = 15;                       // lattice labels run -1
 constexpr int CHARUCO_GRID = 2 * CHARUCO_RANGE + 3;     // ... and the grid one further, so a label's neighbours are in it
 constexpr int CHARUCO_LABELS = 320;                     // corners one lattice holds
 constexpr int CHARUCO_SEED_SCAN = 32, CHARUCO_SEED_TRIES = 4, CHARUCO_NEIGHBOURS = 16;
-constexpr int CHARUCO_MIN_CONTRAST = 40;                // gray levels between a marker's darkest and brightest cell
 constexpr int CHARUCO_MIN_PEAKS = 5;
 constexpr int CHARUCO_MAX_SIDE = 16384;
 constexpr uint16_t CHARUCO_ABSENT = 0xffff;
@@ -78,63 +78,12 @@ __device__ __forceinline__ int marker_square(int rank, int sx, int sy)
 }
 
 // The marker in the lattice cell with corners c00, c10 (one step along i), c01 (along j), c11, by the whole wave: id << 2 |
-// turn, or -1; the same in every lane.  Lane l takes samples l and l + 64 of the (s + 2)^2.
+// turn, or -1; the same in every lane (marker_decode.hpp samples and matches).
 __device__ int decode_cell(const CharucoBoard& B, const CharucoWave& W, int lane, int c00, int c10, int c01, int c11)
 {
-    const int c = B.s + 2, cells = c * c;
-    const long long D = 2 * B.den * c, DD = D * D;
-    const long long x00 = W.x[c00], y00 = W.y[c00], x10 = W.x[c10], y10 = W.y[c10], x01 = W.x[c01], y01 = W.y[c01], x11 = W.x[c11],
-                    y11 = W.y[c11];
-    int val[2], lo = INT_MAX, hi = INT_MIN;
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const int idx = lane + 64 * r;
-        val[r] = -1;
-        if (idx < cells) {
-            const int b = idx / c, a = idx - b * c;
-            const long long wx = B.den * c + B.num * (2 * a + 1 - c), wy = B.den * c + B.num * (2 * b + 1 - c);
-            const long long w00 = (D - wx) * (D - wy), w10 = wx * (D - wy), w01 = (D - wx) * wy, w11 = wx * wy;
-            int px = (int)((w00 * x00 + w10 * x10 + w01 * x01 + w11 * x11 + DD / 2) / DD);
-            int py = (int)((w00 * y00 + w10 * y10 + w01 * y01 + w11 * y11 + DD / 2) / DD);
-            px = px < 1 ? 1 : px > B.w - 2 ? B.w - 2 : px;  // (a blend of corners 5 px inside the image is inside it: this only
-            py = py < 1 ? 1 : py > B.h - 2 ? B.h - 2 : py;  //  keeps a caller's own peaks from reading outside the frame)
-            int sum = 0;
-#pragma unroll
-            for (int dy = -1; dy <= 1; dy++) {
-                const uint8_t* row = B.img + (size_t)(py + dy) * B.pitch + px;
-                sum += row[-1] + row[0] + row[1];
-            }
-            val[r] = sum;
-            lo = sum < lo ? sum : lo, hi = sum > hi ? sum : hi;
-        }
-    }
-    lo = -wave_max_all(-lo), hi = wave_max_all(hi);
-    if (hi - lo < 9 * CHARUCO_MIN_CONTRAST) return -1;
-    const unsigned long long f0 = __ballot(val[0] >= 0 && 2 * val[0] > lo + hi), f1 = __ballot(val[1] >= 0 && 2 * val[1] > lo + hi);
-    auto bit = [&](int idx) { return (int)((idx < 64 ? f0 >> idx : f1 >> (idx - 64)) & 1ull); };
-    int ring = 0;
-    for (int a = 0; a < c; a++) ring |= bit(a) | bit((c - 1) * c + a) | bit(a * c) | bit(a * c + c - 1);
-    if (ring) return -1;
-    const int s = B.s;
-    unsigned long long word[4] = {0, 0, 0, 0};  // the bits turned 0 .. 3 quarter turns, as np.rot90 turns them
-    for (int r = 0; r < s; r++)
-        for (int q = 0; q < s; q++) {
-            word[0] = word[0] << 1 | (unsigned)bit((r + 1) * c + q + 1);
-            word[1] = word[1] << 1 | (unsigned)bit((q + 1) * c + s - r);
-            word[2] = word[2] << 1 | (unsigned)bit((s - r) * c + s - q);
-            word[3] = word[3] << 1 | (unsigned)bit((s - q) * c + r + 1);
-        }
-    unsigned long long best = CHESS_NONE;
-    for (int id = lane; id < B.n_ids; id += 64) {
-        const unsigned long long dw = B.words[id];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int err = __popcll(word[k] ^ dw);
-            const unsigned long long key = (unsigned long long)err << 16 | (unsigned)(id << 2 | k);
-            if (err <= B.max_errors && key < best) best = key;
-        }
-    }
-    best = wave_min_all(best);
+    const MarkerImage image = {B.img, B.w, B.h, B.pitch};
+    const unsigned long long best = decode_marker(image, B.s, B.num, B.den, B.words, B.n_ids, B.max_errors, lane, W.x[c00], W.y[c00],
+                                                  W.x[c10], W.y[c10], W.x[c01], W.y[c01], W.x[c11], W.y[c11]);
     return best == CHESS_NONE ? -1 : (int)(best & 0xffff);
 }
 

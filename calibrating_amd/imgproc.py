@@ -792,6 +792,182 @@ def find_charuco_boards(images, squares_xy, dictionary, first_ids, marker_ratio=
     return to_caller(out if return_info else out[:2], was_np)
 
 
+# ---- stand-alone ArUco markers (csrc/markers.hip; a contract of our own) ----
+MARKER_CAPACITY, MARKER_MAX_RADIUS, MARKER_MAX_BOX, MARKER_MIN_SIDE = 1024, 32, 1024, 4
+MARKER_OVERFLOW = 2  # find_markers' status bit: more candidates than the 1024 kept, the frame has no markers
+MARKER_REFINE_CRITERIA = (30, 0.01)
+# the labels of a call (4 B per pixel) and the statistics beside them (16 B) stay within this; beyond it the frames go in chunks
+MARKER_PLANE_BUDGET = 1 << 30
+
+
+def _marker_integers(**named):
+    for name, v in named.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    return tuple(int(v) for v in named.values())
+
+
+def _mask_arguments(block_radius, offset):
+    block_radius, offset = _marker_integers(block_radius=block_radius, offset=offset)
+    if not 1 <= block_radius <= MARKER_MAX_RADIUS or not -255 <= offset <= 255:
+        raise ValueError("block_radius must be 1 .. %d and offset -255 .. 255, got %d and %d" % (MARKER_MAX_RADIUS, block_radius, offset))
+    return block_radius, offset
+
+
+def _marker_side_limit(shape, colour_ok=True):
+    if len(shape) in (2, 3, 4):
+        sides = shape[-3:-1] if colour_ok and len(shape) > 2 and shape[-1] == 3 else shape[-2:]
+        if max(sides) > CHESS_MAX_SIDE:
+            raise ValueError("images of %s; the detector takes sides up to %d" % (tuple(shape), CHESS_MAX_SIDE))
+
+
+def _dark_mask(gray, f, h, w, pitch, stride, block_radius, offset):
+    import torch
+    mask = torch.empty((f, h, w), dtype=torch.uint8, device=gray.device)
+    call("camd_dark_mask", gray.device, gray.data_ptr(), w, h, pitch, stride, f, block_radius, offset, mask.data_ptr(), what="dark_mask")
+    return mask
+
+
+def dark_mask(images, block_radius=8, offset=7):
+    """Stage 1 of the marker detector: uint8 in the shape of the gray image(s), 1 where a pixel is darker than its
+    surroundings -- ``(gray + offset) * A < S`` with S the sum of the (2 ``block_radius`` + 1)^2 window about it, clipped to
+    the image, and A the pixels of that part.  The inside of a black area wider than the window is not dark.  ``images``:
+    uint8 gray (h, w) / (f, h, w) or colour (through ``cvt_gray``), NumPy or CUDA; pitched views are read in place."""
+    block_radius, offset = _mask_arguments(block_radius, offset)
+    check_array(images, "images")
+    _marker_side_limit(tuple(images.shape))
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    mask = _dark_mask(gray, f, h, w, pitch, stride, block_radius, offset)
+    return to_caller(mask if batched else mask[0], was_np)
+
+
+def _label_components(mask):
+    import torch
+    f, h, w = (int(v) for v in mask.shape)
+    labels = torch.empty((f, h, w), dtype=torch.int32, device=mask.device)
+    call("camd_label_components", mask.device, mask.data_ptr(), w, h, f, labels.data_ptr(), what="label_components")
+    return labels
+
+
+def label_components(mask):
+    """Stage 2: the 4-connected components of ``mask != 0``, uint8 or bool (h, w) / (f, h, w) -> int32 of the same shape: a
+    pixel's label is the least ``y * w + x`` of its component, -1 where the mask is 0."""
+    import torch
+    check_array(mask, "mask")
+    if dtype_name(mask) not in ("uint8", "bool"):
+        raise ValueError("mask must be uint8 or bool, got %s" % mask.dtype)
+    if mask.ndim not in (2, 3) or 0 in tuple(mask.shape):
+        raise ValueError("mask must be (h, w) or (f, h, w) and not empty, got %s" % (tuple(mask.shape),))
+    _marker_side_limit(tuple(mask.shape), colour_ok=False)
+    if (mask.shape[0] if mask.ndim == 3 else 1) * mask.shape[-2] >= 2 ** 31:
+        raise ValueError("mask: %d rows in all, the kernels take fewer than 2^31" % (mask.shape[0] * mask.shape[-2]))
+    was_np = is_np(mask)
+    m = _to_image(mask.view(np.uint8) if was_np and mask.dtype == np.bool_ else mask)
+    m = m.to(torch.uint8) if m.dtype == torch.bool else m
+    m = (m if m.ndim == 3 else m[None]).contiguous()
+    labels = _label_components(m)
+    return to_caller(labels if mask.ndim == 3 else labels[0], was_np)
+
+
+def _marker_arguments(dictionary, block_radius, offset, min_side, max_side, max_bit_errors, refine_win):
+    from . import boards
+    block_radius, offset = _mask_arguments(block_radius, offset)
+    min_side, max_side, max_bit_errors = _marker_integers(min_side=min_side, max_side=max_side, max_bit_errors=max_bit_errors)
+    if not MARKER_MIN_SIDE <= min_side <= max_side <= MARKER_MAX_BOX:
+        raise ValueError("min_side %d, max_side %d; the detector takes %d <= min_side <= max_side <= %d"
+                         % (min_side, max_side, MARKER_MIN_SIDE, MARKER_MAX_BOX))
+    words = boards.marker_words(dictionary)
+    s = int(np.shape(dictionary)[1])
+    if not 0 <= max_bit_errors <= s * s:
+        raise ValueError("max_bit_errors must be 0 .. %d, got %d" % (s * s, max_bit_errors))
+    if refine_win is not None:
+        try:
+            ww, wh = (int(v) for v in refine_win)
+        except (TypeError, ValueError):
+            raise ValueError("refine_win must be None or a pair of half-sizes, got %r" % (refine_win,))
+        if ww <= 0 or wh <= 0:
+            raise ValueError("refine_win must be None or a pair of positive half-sizes, got %r" % (refine_win,))
+        refine_win = (ww, wh)
+    return words, s, block_radius, offset, min_side, max_side, max_bit_errors, refine_win
+
+
+def _marker_stages(gray, f, h, w, pitch, stride, words_t, n_ids, s, block_radius, offset, min_side, max_side, max_bit_errors):
+    """stages 1 to 6 on frames that fit the budget -> dict of CUDA tensors"""
+    import torch
+    dev = gray.device
+    mask = _dark_mask(gray, f, h, w, pitch, stride, block_radius, offset)
+    labels = _label_components(mask)
+    cand = torch.full((f, MARKER_CAPACITY, 6), -1, dtype=torch.int32, device=dev)
+    counts = torch.empty(f, dtype=torch.int32, device=dev)
+    status = torch.empty(f, dtype=torch.int32, device=dev)
+    ws = torch.empty(_native.lib().camd_marker_candidates_workspace_bytes(w, h, f) + 16, dtype=torch.uint8, device=dev)
+    ws_ptr = (ws.data_ptr() + 15) // 16 * 16
+    call("camd_marker_candidates", dev, labels.data_ptr(), w, h, f, min_side, max_side, ws_ptr, cand.data_ptr(), counts.data_ptr(),
+         status.data_ptr(), what="find_markers")
+    quads = torch.empty((f, MARKER_CAPACITY, 4, 2), dtype=torch.int32, device=dev)
+    id_turn = torch.empty((f, MARKER_CAPACITY), dtype=torch.int32, device=dev)
+    best = torch.empty((f, n_ids), dtype=torch.int32, device=dev)
+    seen = torch.empty((f, n_ids), dtype=torch.uint8, device=dev)
+    corners = torch.empty((f, n_ids, 4, 2), dtype=torch.float32, device=dev)
+    call("camd_marker_decode", dev, gray.data_ptr(), w, h, pitch, stride, f, labels.data_ptr(), cand.data_ptr(), counts.data_ptr(),
+         min_side, words_t.data_ptr(), n_ids, s, max_bit_errors, quads.data_ptr(), id_turn.data_ptr(), best.data_ptr(),
+         seen.data_ptr(), corners.data_ptr(), what="find_markers")
+    del ws
+    return dict(status=status, counts=counts, candidates=cand, quads=quads, id_turn=id_turn, seen=seen.bool(), corners=corners)
+
+
+def find_markers(images, dictionary, block_radius=8, offset=7, min_side=12, max_side=512, max_bit_errors=0, refine_win=(3, 3),
+                 return_info=False):
+    """Stand-alone ArUco markers by id from the image alone, on the GPU, for every frame at once -> ``(seen, corners)``:
+    bool (n_ids,) and float32 (n_ids, 4, 2) for one image, (f, n_ids) and (f, n_ids, 4, 2) for a batch, NumPy or CUDA like
+    ``images``; a marker's corners are its own top-left, top-right, bottom-right, bottom-left, NaN where it was not seen.
+    The detector is this package's own, NOT cv2.aruco.detectMarkers: ``dark_mask`` ->
+    ``label_components`` -> the components whose box has sides ``min_side`` .. ``max_side`` and keeps off the image's
+    outermost pixels -> the four extreme pixels of each outline -> the marker decoded inside them against ``dictionary``
+    ((n_ids, s, s) bits, 1 = white) with up to ``max_bit_errors`` wrong bits; of several candidates with one id the one with
+    the fewest errors stands.  Black markers on a light quiet zone; for an inverted print pass ``255 - images``.
+
+    The coarse corners are whole pixels, the centres of dark pixels, so they lie about half a pixel INSIDE the printed
+    outline; ``refine_win``: the half-sizes of the ``corner_sub_pix`` window (criteria (30, 0.01)) the seen corners go
+    through, ``None`` returns the coarse ones.  ``return_info``: ``(seen, corners, info)``, info a dict: ``status`` (f,) --
+    bit 2: more than 1024 candidates, the frame has no markers --, ``counts`` (f,), and per candidate ``candidates``
+    (f, 1024, 6) int32 (root, x0, y0, x1, y1, pixels), ``quads`` (f, 1024, 4, 2) int32 clockwise, -1 where rejected,
+    ``id_turn`` (f, 1024) int32 id << 2 | turn or -1, and ``coarse`` the corners before refinement."""
+    import torch
+    words, s, block_radius, offset, min_side, max_side, max_bit_errors, refine_win = _marker_arguments(
+        dictionary, block_radius, offset, min_side, max_side, max_bit_errors, refine_win)
+    check_array(images, "images")
+    _marker_side_limit(tuple(images.shape))
+    gray, f, h, w, pitch, stride, batched, was_np = _chess_gray(images, "images")
+    if w < 3 or h < 3:
+        raise ValueError("images of %d x %d; the detector takes sides from 3" % (w, h))
+    words_t = torch.from_numpy(words.view(np.int64)).to(gray.device)
+    chunk = max(1, min(f, 65535, MARKER_PLANE_BUDGET // (20 * h * w)))
+    parts = []
+    for a in range(0, f, chunk):
+        n = min(chunk, f - a)
+        parts.append(_marker_stages(gray[a:a + n] if gray.ndim == 3 else gray, n, h, w, pitch, stride, words_t, len(words), s,
+                                    block_radius, offset, min_side, max_side, max_bit_errors))
+    out = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    seen, coarse = out["seen"], out["corners"]
+    corners = coarse
+    if refine_win is not None:
+        corners = coarse.clone()
+        lengths = (4 * seen.sum(1)).cpu().numpy()
+        if int(lengths.sum()):
+            g = gray if gray.ndim == 3 else gray[None]
+            corners[seen] = corner_sub_pix(g, coarse[seen].reshape(-1, 2), refine_win, (-1, -1), MARKER_REFINE_CRITERIA,
+                                           counts=lengths).reshape(-1, 4, 2)
+    info = dict(status=out["status"], counts=out["counts"], candidates=out["candidates"], quads=out["quads"], id_turn=out["id_turn"],
+                coarse=coarse)
+    if not batched:
+        seen, corners, info = seen[0], corners[0], {k: v[0] for k, v in info.items()}
+    if not return_info:
+        return to_caller((seen, corners), was_np)
+    seen, corners = to_caller((seen, corners), was_np)
+    return seen, corners, {k: to_caller(v, was_np) for k, v in info.items()}
+
+
 def laplacian_sums(images):
     """The exact sums behind ``sharpness``: int64 (f, 2) (a batch) or (2,) of S1 = sum L and S2 = sum L^2 over every frame,
     L the 3 x 3 Laplacian [0 1 0; 1 -4 1; 0 1 0] of the gray image with reflect-101 borders."""

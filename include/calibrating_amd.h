@@ -840,6 +840,45 @@ int camd_charuco_detect_multi(const int* peaks, const int* counts, const uint8_t
                               const unsigned long long* dictionary_words, int n_ids, int s, const camd_charuco_boards* boards,
                               int min_markers, int max_bit_errors, float* corners, int* marker_ids, int* status, void* queue);
 
+/* ---- stand-alone ArUco markers by id (csrc/markers.hip) ----
+ * Stands where the reference calls cv2.aruco.detectMarkers (boards.py:280, 551) with a contract of its OWN (INTEGRATION.md
+ * section J; UNPINNED against cv2), integers from the image to the coarse corners, restated in
+ * NumPy by tests/markers_ref.py.  Images: frames of w x h, w, h <= 16384, frames * h < 2^31.  Outside a limit named below:
+ * CAMD_ERR_UNSUPPORTED, before the device is touched.
+ * Stage 1.  S(p): the sum of gray over the (2 block_radius + 1)^2 window about p clipped to the image, A(p): the pixels of
+ * that part.  mask (frames * h * w uint8, dense) is 1 iff (gray(p) + offset) * A(p) < S(p).  block_radius 1 .. 32, offset
+ * -255 .. 255.  The inside of a black area wider than the window is NOT dark: a large marker leaves a hollow ring.       */
+int camd_dark_mask(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, int block_radius, int offset,
+                   uint8_t* mask, void* queue);
+/* Stage 2.  labels (frames * h * w int32, dense): the least y * w + x of a pixel's 4-connected component of mask != 0, -1
+ * where mask == 0.  The result does not depend on the order in which threads meet.                                      */
+int camd_label_components(const uint8_t* mask, int w, int h, int frames, int* labels, void* queue);
+/* Stage 3.  A component is a candidate when both sides of its bounding box lie in [min_side, max_side] and the box does
+ * not touch the image's outermost pixel frame.  candidates: frames x CAMD_MARKER_CAPACITY x 6 int32 (root, x0, y0, x1, y1,
+ * pixels), a frame's candidates in the pixel order of their roots (those beyond the capacity are dropped, the entries
+ * beyond the count are not written); counts: the candidates of each frame in full; status: 2 where counts >
+ * CAMD_MARKER_CAPACITY, else 0.  4 <= min_side <= max_side <= 1024.  workspace: camd_marker_candidates_workspace_bytes
+ * device bytes (16 per pixel and a little), 16-aligned.                                                                 */
+#define CAMD_MARKER_CAPACITY 1024 /* candidates kept per frame */
+size_t camd_marker_candidates_workspace_bytes(int w, int h, int frames);
+int camd_marker_candidates(const int* labels, int w, int h, int frames, int min_side, int max_side, void* workspace,
+                           int* candidates, int* counts, int* status, void* queue);
+/* Stages 4 to 6, one wavefront per candidate.  Over the pixels of the candidate's box that carry its label, ties to the
+ * least pixel index throughout: a maximises |2 p - (box min + box max)|^2, b maximises |p - a|^2, c and d have the greatest
+ * and the least cross(b - a, p - a).  Rejected: cross 0 at c or d, a, d, b, c not strictly convex, or a side shorter than
+ * min_side.  quads: frames x CAMD_MARKER_CAPACITY x 4 x 2 int32, the corners a, d, b, c -- clockwise in image coordinates
+ * (x right, y down) --, -1 where rejected or beyond the count.  Decode as camd_charuco_detect's with the marker filling the
+ * quadrilateral (ratio 1 / 1): corner 0 is the cell's origin, 1 one step along i, 3 along j.  id_turn: frames x
+ * CAMD_MARKER_CAPACITY int32, id << 2 | turn or -1.  Per (frame, id) the candidate with the least (errors, index) stands:
+ * best (frames x n_ids uint32 scratch) = errors << 10 | index.  seen: frames x n_ids uint8; corners: frames x n_ids x 4 x 2
+ * float32, corner j = quad corner (j + turn) % 4 -- the marker's own top-left, top-right, bottom-right, bottom-left --, NaN
+ * where unseen.  They are centres of dark pixels: about half a pixel INSIDE the printed outline.  A frame whose count is
+ * above the capacity has no markers.  s 4 .. 8, n_ids 1 .. CAMD_CHARUCO_MAX_IDS, max_bit_errors 0 .. s*s, frames <= 65535. */
+int camd_marker_decode(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, const int* labels,
+                       const int* candidates, const int* counts, int min_side, const unsigned long long* dictionary_words,
+                       int n_ids, int s, int max_bit_errors, int* quads, int* id_turn, unsigned* best, uint8_t* seen,
+                       float* corners, void* queue);
+
 /* ---- the variance of the Laplacian, a picture's sharpness (csrc/sharpness.hip) ----
  * Stands where the reference calls cv2.Laplacian(gray, cv2.CV_64F).var() (reconstruction_with_board.py:9-12); UNPINNED
  * against cv2.  L(x, y) = g(x-1, y) + g(x+1, y) + g(x, y-1) + g(x, y+1) - 4 g(x, y), a
