@@ -245,6 +245,13 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_hull_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "camd_hull_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_essential_hypotheses": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, ctypes.c_ulonglong,
+                                          c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_essential_score": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                     c_void_p, c_void_p, c_void_p]),
+    "camd_essential_moments_blocks": (c_int, [c_size_t]),
+    "camd_essential_moments": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

@@ -114,23 +114,8 @@ __global__ __launch_bounds__(256) void k_ep_overlap_emit(const T* __restrict__ u
 // ---- fixed-order sums --------------------------------------------------------------------------------------------------
 // Q running sums per thread; thread t of block g adds rows g*256+t, +G*256, ... in that order (at most
 // m = ceil(n / (256 G)) terms); block_tree (compact.hpp) adds the block's 256 threads (8 levels) and stores Q partials;
-// k_ep_final: thread t adds partials t, t+256, t+512, t+768 as (p0 + p1) + (p2 + p3) (2 levels; absent ones are 0), then
-// the same 8-level tree: d = 18 levels above the serial part, whatever n is.
-template <int Q>
-__global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
-{
-    __shared__ double sh[256];
-    double s[Q];
-    for (int q = 0; q < Q; q++) {
-        double p[4];
-        for (int k = 0; k < 4; k++) {
-            const int g = (int)threadIdx.x + 256 * k;
-            p[k] = g < nblocks ? partials[(size_t)g * Q + q] : 0.0;
-        }
-        s[q] = (p[0] + p[1]) + (p[2] + p[3]);
-    }
-    block_tree<Q>(s, sh, sums);
-}
+// k_ep_final (compact.hpp, shared with essential.hip): thread t adds partials t, t+256, t+512, t+768 as (p0 + p1) + (p2 + p3)
+// (2 levels; absent ones are 0), then the same 8-level tree: d = 18 levels above the serial part, whatever n is.
 
 struct EpPoses {
     double k1[9], k2[9], R[4][9], t[4][3];

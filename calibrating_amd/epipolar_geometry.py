@@ -8,7 +8,8 @@ Where the work runs.  Everything that touches every match or every pixel is a ke
 intersection, the overlap filter, the depth of every match under all four candidate poses, the gathered means, the flow
 compaction and conversions.  The essential matrix itself is an SVD of at most 199 x 9 numbers (the reference subsamples
 ``[:: n // 100]``) followed by 3 x 3 algebra: init-time work on the host in NumPy float64, fed with the strided subsample
-only.
+only.  ``find_essential_matrix`` / ``EssentialMatrixStereo(robust=...)`` is the opt-in estimate for matches that hold
+wrong pairs: RANSAC over 8-point samples, every hypothesis scored against every match on the device (csrc/essential.hip).
 
 Arguments are checked before the device is touched.  Deviations from the reference:
 ``precise=True`` is refused, ``xy1`` / ``xy2`` are required, non-finite coordinates and cell windows beyond 2^28 cells
@@ -92,7 +93,11 @@ def compute_essential_matrix(xyzs1, xyzs2):
         xyzs1, xyzs2 = xyzs1[:: n // 100], xyzs2[:: n // 100]
     (x1, y1, z1), (x2, y2, z2) = xyzs1.T[:3], xyzs2.T[:3]
     A = np.stack([x1 * x2, x2 * y1, z1 * x2, x1 * y2, y1 * y2, z1 * y2, x1 * z2, y1 * z2, z1 * z2], 1).astype(np.float64)
-    E = np.linalg.svd(A)[2][-1].reshape(3, 3)
+    return _force_rank2(np.linalg.svd(A)[2][-1].reshape(3, 3))
+
+
+def _force_rank2(E):
+    """``E`` with its smallest singular value set to 0 (:39-43)."""
     U, S, Vt = np.linalg.svd(E)
     S[2] = 0
     return np.dot(U, np.dot(np.diag(S), Vt))
@@ -125,10 +130,15 @@ def _pose_candidates(uvs1, uvs2, K1, K2, baseline):
     n = int(uvs1.shape[0])
     E = compute_essential_matrix(uvs_to_xyz_noramls(_host_subsample(uvs1, n), K1),
                                  uvs_to_xyz_noramls(_host_subsample(uvs2, n), K2))
+    return E, _scaled_candidates(E, baseline)
+
+
+def _scaled_candidates(E, baseline):
+    """The four ``T_1to2`` of ``E`` with |t| = baseline."""
     Ts = decompose_essential_matrix(E)
     for T in Ts:
         T[:3, 3] *= baseline / np.linalg.norm(T[:3, 3])
-    return E, Ts
+    return Ts
 
 
 def _candidate_means(a, b, K1, K2, Ts):
@@ -161,6 +171,162 @@ def _mean(z, idx=None, what="mean"):
     if bad:
         raise IndexError("%s: %d indices lie outside the %d depths" % (what, int(bad), int(zd.shape[0])))
     return float(total) / n
+
+
+# ---- find_essential_matrix: RANSAC over 8-point samples (csrc/essential.hip) ---------------------------------------------
+ESSENTIAL_MAX_HYPOTHESES = 1 << 20  # (ESS_MAX_HYPOTHESES)
+
+
+class _EssentialRows:
+    """The matches as the three stages take them: device rows read in place (type, row strides), inv(K1), inv(K2)."""
+
+    def __init__(self, uvs1, uvs2, K1, K2):
+        self.was_np = is_np(uvs1)
+        self.uv1, self.stride1 = self._in_place(to_device(uvs1) if self.was_np else uvs1)
+        self.device = self.uv1.device
+        if self.was_np:
+            uvs2 = to_device(uvs2, device=self.device)
+        elif uvs2.device != self.device:
+            raise ValueError("inputs live on different devices: %s and %s" % (uvs2.device, self.device))
+        self.uv2, self.stride2 = self._in_place(uvs2)
+        self.n, self.type = int(uvs1.shape[0]), FLOAT_TYPES[dtype_name(uvs1)]
+        self.k1, self.k2 = Kinv9(K1), Kinv9(K2)
+
+    @staticmethod
+    def _in_place(t):
+        """(tensor, row stride in elements): a view whose rows are u, v side by side is read where it lies."""
+        if t.stride(1) == 1 and 2 <= t.stride(0) < 2 ** 31:
+            return t, int(t.stride(0))
+        return t.contiguous(), 2
+
+    def args(self):
+        return (self.uv1.data_ptr(), self.uv2.data_ptr(), self.type, self.n, self.stride1, self.stride2, self.k1.ctypes.data,
+                self.k2.ctypes.data)
+
+
+def _essential_hypotheses(rows, hypotheses, seed):
+    """Stage 1 alone: (samples (H, 8) int32, Es (H, 9) float64) on the device."""
+    import torch
+    samples = torch.empty((hypotheses, 8), dtype=torch.int32, device=rows.device)
+    Es = torch.empty((hypotheses, 9), dtype=torch.float64, device=rows.device)
+    call("camd_essential_hypotheses", rows.device, *rows.args(), int(seed) & 0xFFFFFFFFFFFFFFFF, hypotheses, samples.data_ptr(),
+         Es.data_ptr(), what="find_essential_matrix")
+    return samples, Es
+
+
+def _essential_score(rows, Es, threshold2):
+    """Stage 2 alone: (counts (H,) int32, winner (11,) float64 = the winning e, its index, its count) on the device."""
+    import torch
+    Es = to_device(Es, dtype="float64", device=rows.device)
+    hypotheses = int(Es.shape[0])
+    counts = torch.empty(hypotheses, dtype=torch.int32, device=rows.device)
+    winner = torch.empty(11, dtype=torch.float64, device=rows.device)
+    call("camd_essential_score", rows.device, *rows.args(), Es.data_ptr(), hypotheses, float(threshold2), counts.data_ptr(),
+         winner.data_ptr(), what="find_essential_matrix")
+    return counts, winner
+
+
+def _essential_moments(rows, E, threshold2):
+    """Stage 3 alone for one ``E`` (9 float64 on the device, or a host array that is uploaded): (mask (n,) uint8, sums (46,)
+    float64 = the packed lower triangle of sum a^T a over the inliers, then their number) on the device."""
+    import torch
+    E = to_device(np.ascontiguousarray(E, np.float64).reshape(9) if is_np(E) else E, dtype="float64", device=rows.device)
+    mask = torch.empty(rows.n, dtype=torch.uint8, device=rows.device)
+    partials = torch.empty(_native.lib().camd_essential_moments_blocks(rows.n) * 46, dtype=torch.float64, device=rows.device)
+    sums = torch.empty(46, dtype=torch.float64, device=rows.device)
+    call("camd_essential_moments", rows.device, *rows.args(), E.data_ptr(), float(threshold2), mask.data_ptr(), partials.data_ptr(),
+         sums.data_ptr(), what="find_essential_matrix")
+    return mask, sums
+
+
+def _positive_largest(v):
+    """``v`` with the sign that makes its entry of the largest magnitude (the first of equals) positive."""
+    return -v if v[np.argmax(np.abs(v))] < 0 else v
+
+
+def _essential_checks(uvs1, uvs2, K1, K2, threshold, hypotheses):
+    """Every refusal of find_essential_matrix that needs no device -> (K1, K2, threshold on the rays)."""
+    _float_rows(uvs1, "uvs1")
+    _float_rows(uvs2, "uvs2", uvs1)
+    if dtype_name(uvs1) not in FLOAT_TYPES or dtype_name(uvs2) != dtype_name(uvs1):
+        raise ValueError("uvs1, uvs2 must both be float64 or both float32, got %s and %s" % (dtype_name(uvs1), dtype_name(uvs2)))
+    n = int(uvs1.shape[0])
+    if int(uvs2.shape[0]) != n or not 8 <= n < 2 ** 31:
+        raise ValueError("uvs1, uvs2 must hold the same number (8 .. 2^31 - 1) of matches, got %d and %d" % (n, uvs2.shape[0]))
+    K1 = np.asarray(K1, np.float64)
+    K2 = K1 if K2 is None else np.asarray(K2, np.float64)
+    if K1.shape != (3, 3) or K2.shape != (3, 3):
+        raise ValueError("K1, K2 must be 3x3")
+    if not (np.isfinite(K1).all() and np.isfinite(K2).all()):
+        raise ValueError("K1, K2 must be finite")
+    focal = (K1[0, 0] + K1[1, 1] + K2[0, 0] + K2[1, 1]) / 4
+    if not focal > 0 or min(abs(np.linalg.det(K1)), abs(np.linalg.det(K2))) == 0:
+        raise ValueError("K1, K2 must be invertible camera matrices with a positive mean focal length")
+    if int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= ESSENTIAL_MAX_HYPOTHESES:
+        raise ValueError("hypotheses must be an integer in 1 .. 2^20, got %r" % (hypotheses,))
+    if not (float(threshold) > 0 and np.isfinite(float(threshold))):
+        raise ValueError("threshold must be a positive number of pixels, got %r" % (threshold,))
+    if is_np(uvs1) and not (np.isfinite(uvs1).all() and np.isfinite(uvs2).all()):
+        raise ValueError("find_essential_matrix: u, v must be finite")
+    return K1, K2, float(threshold) / focal
+
+
+def find_essential_matrix(uvs1, uvs2, K1, K2=None, threshold=1.0, hypotheses=1024, seed=0, refine=True, return_info=False):
+    """The essential matrix of matched pixels that holds against wrong matches: RANSAC over 8-point samples on the GPU
+    (csrc/essential.hip), a contract of this package's own -- ``cv2.findEssentialMat`` is not restated.  ``uvs1, uvs2``:
+    (n, 2) pinhole pixels, both float32 or both float64, ndarrays or CUDA tensors (read in place, a view with rows
+    ``u, v`` side by side included), n >= 8, finite.  Returns ``E`` (3, 3) host float64 of rank 2 with
+    ``ray2 @ E @ ray1 = 0`` on the rays ``(u, v, 1) @ inv(K).T``; with ``return_info=True`` the dict ``E, inliers ((n,)
+    bool of the caller's kind), n_inliers, hypothesis (the index of the winning sample), hypothesis_inliers (its count),
+    refined, status`` ("ok", or "degenerate" when no sample determined a matrix: ``E`` is then all zero).
+
+    A match is an inlier when its squared Sampson error on the rays is below ``(threshold / f)^2``, ``threshold`` in
+    pixels and ``f`` the mean of fx1, fy1, fx2, fy2 (evaluated as ``num^2 < thr^2 den``; include/calibrating_amd.h has the
+    order of the operations).
+
+    1  Hypothesis ``h`` of ``hypotheses`` draws 8 distinct matches from ``boards._splitmix64``: ``key`` is the generator's
+       output from the state ``seed``; the hypothesis' own stream starts at the state that is the generator's OUTPUT from
+       the state ``key ^ h``; a draw is ``(z * n) >> 64`` of the stream's next output ``z`` (multiply-high), made again from
+       the same stream while it repeats an earlier draw of the hypothesis.  No state is shared: hypothesis ``h`` draws the
+       same matches and gives the same matrix whatever ``hypotheses`` is.  Its matrix is the null vector of the 8 x 9
+       system in the reference's row layout; a sample that leaves more than one null direction is marked and scores 0.
+    2  Every hypothesis is scored against every match; the largest count wins, ties go to the lowest index.
+    3  ``refine=True``: the smallest eigenvector (``np.linalg.eigh``, 9 x 9) of the moment matrix of ALL inliers of the
+       winner, forced to rank 2 and scored once more, replaces the winner when it has at least as many inliers;
+       otherwise, and with ``refine=False``, the winner's matrix forced to rank 2 is returned.  ``inliers`` belong to the
+       matrix that was scored: the refit's, or the winner's before its rank was forced.
+
+    The same input and seed give the same bits on every run.  Every refusal (``ValueError``) comes before a kernel of the
+    estimator is queued; for tensors the finite check is one reduction on the device."""
+    import torch
+    K1, K2, thr = _essential_checks(uvs1, uvs2, K1, K2, threshold, hypotheses)
+    if not is_np(uvs1) and not (bool(torch.isfinite(uvs1).all()) and bool(torch.isfinite(uvs2).all())):
+        raise ValueError("find_essential_matrix: u, v must be finite")
+    rows, thr2 = _EssentialRows(uvs1, uvs2, K1, K2), thr * thr
+    _, Es = _essential_hypotheses(rows, int(hypotheses), seed)
+    _, winner = _essential_score(rows, Es, thr2)
+    won = winner.cpu().numpy()  # synchronises: the one read-back of the search
+    E_won, h, count = won[:9].reshape(3, 3), int(won[9]), int(won[10])
+    info = dict(hypothesis=h, hypothesis_inliers=count, refined=False, status="ok" if count else "degenerate")
+    if not count:
+        mask = torch.zeros(rows.n, dtype=torch.bool, device=rows.device)
+        info.update(E=np.zeros((3, 3)), n_inliers=0, inliers=to_caller(mask, rows.was_np))
+        return info if return_info else info["E"]
+    E = _force_rank2(E_won)
+    if refine or return_info:
+        mask, sums = _essential_moments(rows, winner[:9], thr2)
+    if refine:
+        M = np.zeros((9, 9))
+        M[np.tril_indices(9)] = sums[:45].cpu().numpy()
+        E_fit = _force_rank2(_positive_largest(np.linalg.eigh(M, UPLO="L")[1][:, 0]).reshape(3, 3))
+        mask_fit, sums_fit = _essential_moments(rows, E_fit, thr2)
+        if int(sums_fit[45].item()) >= count:
+            E, mask, info["refined"] = E_fit, mask_fit, True
+            count = int(sums_fit[45].item())
+    if not return_info:
+        return E
+    info.update(E=E, n_inliers=count, inliers=to_caller(mask != 0, rows.was_np))
+    return info
 
 
 # ---- filter_overlap_uvs ------------------------------------------------------------------------------------------------
@@ -491,9 +657,15 @@ def build_set2ds_by_flowds(viewds, flowds):
 class EssentialMatrixStereo(Stereo):
     """A ``Stereo`` whose pose comes from matched pixels: 8-point essential matrix, four candidate poses, the first whose
     mean depths in both cameras are positive (:100-150).  ``self.epipolar`` holds ``zs1, zs2, uvs1, uvs2`` (arrays of the
-    caller's kind), ``E`` (3x3 ndarray) and ``z1, z2`` (the winner's mean depths, floats)."""
+    caller's kind), ``E`` (3x3 ndarray) and ``z1, z2`` (the winner's mean depths, floats).
 
-    def __init__(self, uvs1=None, uvs2=None, K1=None, K2=None, baseline=1, xy1=None, xy2=None, name1="cam1", name2="cam2"):
+    ``robust=None``: the reference's plain 8-point fit of a subsample, as ever.  ``robust=True`` or a dict of
+    ``find_essential_matrix``'s keyword arguments (threshold, hypotheses, seed, refine): ``E`` comes from there, the
+    candidate is chosen by the mean depths of the INLIERS, ``zs1`` / ``zs2`` still hold every match, and ``epipolar`` gains
+    ``inliers`` ((n,) bool of the caller's kind) and ``n_inliers``; ``self.robust_info`` is the estimator's whole answer."""
+
+    def __init__(self, uvs1=None, uvs2=None, K1=None, K2=None, baseline=1, xy1=None, xy2=None, name1="cam1", name2="cam2",
+                 robust=None):
         if uvs1 is None:  # (type(self)() as Stereo.copy makes it)
             super().__init__()
             return
@@ -512,10 +684,21 @@ class EssentialMatrixStereo(Stereo):
         K1, K2 = np.asarray(K1, np.float64), np.asarray(K2, np.float64)
         if K1.shape != (3, 3) or K2.shape != (3, 3):
             raise ValueError("K1, K2 must be 3x3")
-        E, Ts = _pose_candidates(uvs1, uvs2, K1, K2, baseline)
+        info = None
+        if robust is None:
+            E, Ts = _pose_candidates(uvs1, uvs2, K1, K2, baseline)
+        else:
+            info = find_essential_matrix(uvs1, uvs2, K1, K2, return_info=True, **({} if robust is True else dict(robust)))
+            if info["status"] != "ok":
+                raise ValueError("EssentialMatrixStereo: no 8 of the matches determine an essential matrix (%s)" % info["status"])
+            E, Ts = info["E"], _scaled_candidates(info["E"], baseline)
         a = to_device(uvs1, dtype="float64", cast=True)
         b = to_device(uvs2, dtype="float64", cast=True, device=a.device)
-        means = _candidate_means(a, b, K1, K2, Ts)
+        if info is None:
+            means = _candidate_means(a, b, K1, K2, Ts)
+        else:
+            keep = to_device(info["inliers"], device=a.device)
+            means = _candidate_means(a[keep], b[keep], K1, K2, Ts)
         # the first candidate with both means positive; if none is, the last one, as the reference's loop leaves it
         self.candidate = next((c for c in range(4) if means[c, 0] > 0 and means[c, 1] > 0), 3)
         T = Ts[self.candidate]
@@ -525,13 +708,17 @@ class EssentialMatrixStereo(Stereo):
         self.load(dict(R=T[:3, :3], t=T[:3, 3], cam1=dict(xy=list(xy1), K=K1, name=str(name1)),
                        cam2=dict(xy=list(xy2), K=K2, name=str(name2))))
         self.epipolar = dict(zs, E=E, uvs1=uvs1, uvs2=uvs2, z1=float(means[self.candidate, 0]), z2=float(means[self.candidate, 1]))
+        if info is not None:
+            self.epipolar.update(inliers=info["inliers"], n_inliers=info["n_inliers"])
+            self.robust_info = info
 
     @classmethod
-    def from_stereo(cls, uvs1, uvs2, stereo, baseline=None):
+    def from_stereo(cls, uvs1, uvs2, stereo, baseline=None, robust=None):
         """The pose re-estimated from matches for an existing rig: everything of ``stereo``'s record is kept (distortion
-        included), ``R`` and ``t`` are replaced (:152-166).  ``baseline=None``: the rig's own."""
+        included), ``R`` and ``t`` are replaced (:152-166).  ``baseline=None``: the rig's own.  ``robust``: as the
+        constructor's."""
         self = cls(uvs1, uvs2, K1=stereo.cam1.K, K2=stereo.cam2.K, xy1=stereo.cam1.xy, xy2=stereo.cam2.xy,
-                   baseline=baseline or stereo.baseline)
+                   baseline=baseline or stereo.baseline, robust=robust)
         rec = stereo.dump(return_dict=True)
         rec["R"], rec["t"] = self.R, self.t
         self.load(rec)

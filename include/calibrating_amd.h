@@ -928,6 +928,48 @@ int camd_hull_fill(const int* vertices, const int* hull_counts, const double* ab
 int camd_hull_mask(const int* vertices, const int* hull_counts, int vertex_capacity, int frames, int w, int h, uint8_t* out,
                    void* queue);
 
+/* ---- the essential matrix of matched pixels by RANSAC over 8-point samples (csrc/essential.hip) ----
+ * The device side of epipolar_geometry.find_essential_matrix.  A contract of this library's OWN: cv2.findEssentialMat is
+ * not restated (UNPINNED); tests/essential_ref.py restates every stage in NumPy, bit for bit.
+ * Shared by the three entries: uv1, uv2 are [n][stride] of uv_type (CAMD_VALUE_F64 / _F32; stride >= 2 elements, u and v
+ * the first two of a row), read in place, 8 <= n < 2^31, FINITE (the caller checks; a sample that meets a non-finite
+ * value is marked).  K1inv, K2inv: inv(K) as 9 host doubles.  The rays of match i are, each product and sum rounded,
+ *   a[r] = (K1inv[3r] u1 + K1inv[3r + 1] v1) + K1inv[3r + 2],   b[r] likewise from K2inv and (u2, v2)
+ * and its row of the 8-point system is row[3 j + k] = a[k] * b[j] (row . e = b^T E a with E = e as 3 x 3, row-major).
+ * A match is an INLIER of e below threshold2 (the squared threshold, on the rays) when, with
+ *   p[r] = (e[3r] a0 + e[3r + 1] a1) + e[3r + 2] a2,   q[c] = (e[c] b0 + e[3 + c] b1) + e[6 + c] b2   (c = 0, 1),
+ *   num = (b0 p0 + b1 p1) + b2 p2,   den = ((p0 p0 + p1 p1) + q0 q0) + q1 q1:   num * num < threshold2 * den
+ * -- its squared Sampson error num^2 / den compared without the division; a zero or non-finite e has no inliers.
+ *
+ * Stage 1.  Hypothesis h < hypotheses (1 .. 2^20) draws 8 DISTINCT rows: key = the output of splitmix64 from the state
+ * `seed`; the hypothesis' stream starts at the state splitmix64 gives as OUTPUT from the state key ^ h; draw k is
+ * floor(z n / 2^64) of the stream's next output z, drawn again while it repeats one of the draws before it (after 1024
+ * repeats of one draw: the smallest index not drawn yet).  Nothing is shared between hypotheses: hypothesis h is the same
+ * whatever `hypotheses` is.  M = sum over the 8 rows, in the order drawn, of row^T row (packed lower triangle, 45 sums);
+ * e = the null vector by six rounds of inverse iteration on M + 1e-13 tr(M) I (the routine the PnP start uses), of unit
+ * norm, its entry of the largest magnitude (the first of equals) positive.  A sample is MARKED, its e all zero, when e is
+ * not finite, the Cholesky factorisation fails, or more than one pivot of it lies below 1e-10 tr(M): the matches leave
+ * more than one null direction (coincident or otherwise degenerate ones) and determine no matrix.
+ * samples: [hypotheses][8] int32, Es: [hypotheses][9] float64, both on the device.  One lane per hypothesis.           */
+int camd_essential_hypotheses(const void* uv1, const void* uv2, int uv_type, size_t n, int uv1_stride, int uv2_stride,
+                              const double K1inv[9], const double K2inv[9], unsigned long long seed, int hypotheses, int* samples,
+                              double* Es, void* queue);
+/* Stage 2.  counts[h] (device int32, cleared here) = the inliers of Es[h] among all n matches: a lane owns four matches
+ * and walks the hypotheses, the counts are added by ballot, popcount and integer atomics (exact in any order).
+ * winner (device, 11 doubles): [0 .. 8] the e of the largest count, ties to the LOWEST index, [9] that index, [10] its count. */
+int camd_essential_score(const void* uv1, const void* uv2, int uv_type, size_t n, int uv1_stride, int uv2_stride,
+                         const double K1inv[9], const double K2inv[9], const double* Es, int hypotheses, double threshold2,
+                         int* counts, double* winner, void* queue);
+/* Stage 3, for ONE matrix E (9 doubles ON THE DEVICE): mask[i] (n bytes) = 1 where match i is an inlier, and
+ * sums (device, 46 doubles): sums[p (p + 1) / 2 + q] = sum over the inliers of row[p] * row[q] (q <= p < 9), sums[45] =
+ * their number.  REDUCTION SHAPE: that of camd_epipolar_sums -- G = camd_essential_moments_blocks(n) = clamp(ceil(n / 256),
+ * 1, 1024) workgroups, thread t of workgroup g adds rows 256 g + t, + 256 G, ... in that order, d = 18 tree levels, no
+ * float atomics.  partials_ws: G * 46 doubles.                                                                       */
+int camd_essential_moments_blocks(size_t n);
+int camd_essential_moments(const void* uv1, const void* uv2, int uv_type, size_t n, int uv1_stride, int uv2_stride,
+                           const double K1inv[9], const double K2inv[9], const double* E, double threshold2, uint8_t* mask,
+                           double* partials_ws, double* sums, void* queue);
+
 #ifdef __cplusplus
 }
 #endif
