@@ -25,6 +25,7 @@ from .vis import resolve_max_l1, vis_align, vis_depth, vis_depth_l1, vis_stereo
 from .boards import ArucoGridBoard, BaseBoard, CharucoBoard, Chessboard, MarkerBoard, MultiBoards
 from .multi_boards import MultiBoardsCam
 from .reconstruction_with_board import convert_cam_to_nerf_json, get_sharpness
+from .features import BinaryFeatureMatching, detect_and_describe, match_descriptors, match_images, match_views
 
 __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "StereoSGBM",
            "StereoSGBM_create", "MODE_SGBM", "MODE_HH", "MODE_SGBM_3WAY", "MODE_HH4", "__version__",
@@ -35,4 +36,5 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "calibrate_camera", "CALIB_USE_INTRINSIC_GUESS", "CALIB_FIX_PRINCIPAL_POINT", "CALIB_FIX_FOCAL_LENGTH",
            "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
            "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard", "CharucoBoard", "MarkerBoard", "ArucoGridBoard",
-           "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness", "find_essential_matrix"]
+           "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness", "find_essential_matrix",
+           "BinaryFeatureMatching", "detect_and_describe", "match_descriptors", "match_images", "match_views"]

@@ -252,6 +252,16 @@ SIGNATURES = {
     "camd_essential_moments_blocks": (c_int, [c_size_t]),
     "camd_essential_moments": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_feature_score": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    "camd_feature_keypoints_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "camd_feature_keypoints": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_feature_describe": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "camd_feature_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_feature_filter_workspace_bytes": (c_size_t, [c_int]),
+    "camd_feature_filter": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # include/calibrating_amd_experimental.h: measurement hooks without a counterpart in the reference's interface (CU-masked

@@ -970,6 +970,59 @@ int camd_essential_moments(const void* uv1, const void* uv2, int uv_type, size_t
                            const double K1inv[9], const double K2inv[9], const double* E, double threshold2, uint8_t* mask,
                            double* partials_ws, double* sums, void* queue);
 
+/* ---- keypoints, binary descriptors and a brute-force Hamming matcher: matches from two pictures (csrc/features.hip) ----
+ * A contract of this library's OWN, NOT cv2.ORB / cv2.BFMatcher (UNPINNED):
+ * integers end to end, every tie defined, restated in NumPy by tests/features_ref.py.  gray: frames images of w x h uint8,
+ * rows `pitch` and images `stride` bytes apart; w, h <= 16384, frames * h < 2^31, else CAMD_ERR_UNSUPPORTED.
+ * Stage A, the score.  ring[0 .. 15] = g(x + dx, y + dy) at (dx, dy) = (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3)
+ * (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3); d[i] = ring[i] - g(x, y);
+ *   score = max over the 16 starts s of max(min d[s .. s + 8], -max d[s .. s + 8]) (indices mod 16), and 0 if that is below
+ *   `threshold` (1 .. 255) or the pixel lies within CAMD_FEATURE_BORDER of an image edge.  score: frames * h * w uint8, dense. */
+#define CAMD_FEATURE_BORDER 16
+int camd_feature_score(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, int threshold, uint8_t* score,
+                       void* queue);
+/* Stage A, the keypoints.  key(p) = score(p) << 32 | (0xFFFFFFFF - (y * w + x)) as u64; p is a PEAK when score(p) != 0 (and p
+ * lies CAMD_FEATURE_BORDER inside the image, whatever the plane says) and key(p) is the largest of its 3 x 3 neighbourhood.
+ * The blocks of cell x cell pixels (cell 4 .. 64) are aligned at pixel (0, 0); a block's keypoint is its peak of the largest
+ * key.  capacity = ceil(h / cell) * ceil(w / cell).  xy: frames x capacity x 2 int32 (x, y), scores: frames x capacity int32,
+ * a frame's keypoints in row-major order of their blocks (the entries beyond the count are not written); counts: frames
+ * int32.  workspace: camd_feature_keypoints_workspace_bytes device bytes, 8-aligned.                                   */
+size_t camd_feature_keypoints_workspace_bytes(int w, int h, int frames, int cell);
+int camd_feature_keypoints(const uint8_t* score, int w, int h, int frames, int cell, void* workspace, int* xy, int* scores,
+                           int* counts, void* queue);
+/* Stage B, one wavefront per keypoint, no workgroup barrier; a keypoint's outputs depend on its own pixels only.  xy, counts
+ * as above with `capacity` slots per frame (any capacity >= 1); slots at or beyond counts[f] are left as they are.
+ *   bin   m10 = sum dx g(x + dx, y + dy), m01 = sum dy g(x + dx, y + dy) over dx^2 + dy^2 <= 13^2 (int32);  the bin is the
+ *         k in 0 .. 31 that maximises m10 C[k] + m01 S[k] in int64, the lowest of equals, C[k] = rint(16384 cos(2 pi k / 32)),
+ *         S[k] = C[(k + 24) % 32]
+ *   box   B(p) = the sum of g over the 5 x 5 window about p
+ *   bits  pattern: 32 x 256 x 4 int8 ON THE DEVICE, 4-aligned: (x1, y1, x2, y2) of test i at rotation k, each clamped to
+ *         -14 .. 14 when read; bit i = B(x + x1, y + y1) < B(x + x2, y + y2) with the tests of rotation `bin`
+ * descriptors: frames x capacity x 32 uint8, 8-aligned, bit r of byte b = test 8 b + r; bins: frames x capacity int32.
+ * A point nearer than CAMD_FEATURE_BORDER to an edge reads nothing: its descriptor is zero and its bin -1.             */
+int camd_feature_describe(const uint8_t* gray, int w, int h, size_t pitch, size_t stride, int frames, const int* xy, const int* counts,
+                          int capacity, const int8_t* pattern, uint8_t* descriptors, int* bins, void* queue);
+/* Stage C, the search, both ways in one launch.  Two sets of descriptors (they may be the same): desc frames x capacity x
+ * 32 uint8, 16-aligned, counts frames int32 (clamped to 0 .. capacity).  pairs: npairs x 2 int32 ON THE DEVICE, (frame of
+ * set 1, frame of set 2); a frame outside its set counts as empty.  For query row q of the first frame, over the train rows
+ * t of the second in rising t: distance d = the differing bits; d < d_best: d_second = d_best, d_best = d, best = t; else
+ * d < d_second: d_second = d -- so best has the smallest (d, t) and d_second is the smallest d among the other rows, 257
+ * where there is none.  best12: npairs x capacity1 int32 (-1 beyond the count or without a train row), dist12: npairs x
+ * capacity1 x 2 int32 (d_best, d_second; 257 likewise); best21, dist21: the same with the roles swapped, npairs x
+ * capacity2.  1 .. 65535 pairs, npairs * capacity < 2^30.                                                              */
+int camd_feature_search(const uint8_t* desc1, const int* counts1, int frames1, int capacity1, const uint8_t* desc2, const int* counts2,
+                        int frames2, int capacity2, const int* pairs, int npairs, int* best12, int* dist12, int* best21, int* dist21,
+                        void* queue);
+/* Stage C, the filter.  Query q of pair p is KEPT when d_best <= max_distance (0 .. 256), d_best * ratio_den <= ratio_num *
+ * d_second (1 <= num <= den <= 2^20) and, with cross_check != 0, best21[p][best12[p][q]] == q.  matches: npairs x capacity1 x 2
+ * int32 (q, best), distances: npairs x capacity1 int32, a pair's kept queries in rising q by the shared ordered compaction
+ * (the entries beyond the count are not written); match_counts: npairs int32.  workspace:
+ * camd_feature_filter_workspace_bytes device bytes, 8-aligned.                                                         */
+size_t camd_feature_filter_workspace_bytes(int npairs);
+int camd_feature_filter(const int* counts1, int frames1, int capacity1, int capacity2, const int* pairs, int npairs, const int* best12,
+                        const int* dist12, const int* best21, int max_distance, int ratio_num, int ratio_den, int cross_check,
+                        void* workspace, int* matches, int* distances, int* match_counts, void* queue);
+
 #ifdef __cplusplus
 }
 #endif
