@@ -17,6 +17,8 @@ written from the behaviour the reference shows, which tests/golden/reference_boa
 """
 import numpy as np
 
+from ._frames import integer
+
 SUBPIX_WIN, SUBPIX_ZERO_ZONE = (4, 4), (-1, -1)  # boards.py:166-167
 SUBPIX_CRITERIA = (2 + 1, 30, 0.01)  # boards.py:161: cv2.TERM_CRITERIA_EPS + cv2.TERM_CRITERIA_MAX_ITER, 30, 0.01
 POINT_KEYS = ("image_points", "corners", "marker_corners")  # what a region of interest moves back into the whole image
@@ -361,8 +363,8 @@ class CharucoBoard(BaseBoard):
         from fractions import Fraction
         ratio = Fraction(float(marker_size_mm) / float(square_size_mm)).limit_denominator(64)
         self.marker_ratio = (ratio.numerator, ratio.denominator)
-        from . import imgproc
-        imgproc._charuco_arguments(self.square_xy, self.dictionary, self.marker_ratio, self.first_id, 8, 3, 2, 0)
+        from . import detect
+        detect.charuco_arguments(self.square_xy, self.dictionary, self.marker_ratio, self.first_id, 8, 3, 2, 0)
         x, y = np.meshgrid(np.arange(sx - 1), np.arange(sy - 1))
         grid = np.zeros(((sx - 1) * (sy - 1), 3), np.float32)
         grid[:, 0] = (x.ravel() + 1) * (square_size_mm / 1000.0)
@@ -513,9 +515,9 @@ class MultiBoards(BaseBoard):
 
     def _set_first_ids(self):
         """the boards' first marker ids where they form a set, else None"""
-        from . import imgproc
+        from . import detect
         bs = self.boards
-        if not 1 <= len(bs) <= imgproc.CHARUCO_MAX_BOARDS or not all(isinstance(b, CharucoBoard) for b in bs):
+        if not 1 <= len(bs) <= detect.CHARUCO_MAX_BOARDS or not all(isinstance(b, CharucoBoard) for b in bs):
             return None
         a = bs[0]
         for b in bs[1:]:
@@ -525,7 +527,7 @@ class MultiBoards(BaseBoard):
             if b.dictionary is not a.dictionary and not np.array_equal(b.dictionary, a.dictionary):
                 return None
         try:
-            return imgproc._charuco_set([b.first_id for b in bs], (a.square_xy[0] * a.square_xy[1]) // 2, len(a.dictionary))
+            return detect.charuco_set([b.first_id for b in bs], (a.square_xy[0] * a.square_xy[1]) // 2, len(a.dictionary))
         except ValueError:
             return None
 
@@ -668,7 +670,7 @@ class MarkerBoard(BaseBoard):
         points = {}
         for key, p in dict(object_points).items():
             p = np.asarray(p, np.float32)
-            if isinstance(key, bool) or int(key) != key or not 0 <= int(key) < len(self.dictionary) or p.shape != (4, 3):
+            if not 0 <= integer(key, "a marker id of object_points") < len(self.dictionary) or p.shape != (4, 3):
                 raise ValueError("object_points maps a marker id of the dictionary (0 .. %d) to its (4, 3) corners, got %r -> %s"
                                  % (len(self.dictionary) - 1, key, p.shape))
             points[int(key)] = p

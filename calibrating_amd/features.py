@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _native
 from ._arrays import check_array, dtype_name, is_np, to_device
+from ._frames import device_frames, integer, layout
 from ._native import call
 from .boards import _splitmix64
 from .hostio import to_host_list
@@ -45,9 +46,7 @@ def brief_pattern(seed=0):
     two ends coincide is drawn again.  Rotation k is ``rint`` of the float64 rotation of both ends by ``2 pi k / 32``
     (x' = x cos - y sin, y' = x sin + y cos: towards +y, which is down in an image), so the reach is at most 14.  The
     same seed gives the same table everywhere."""
-    if isinstance(seed, bool) or int(seed) != seed:
-        raise ValueError("seed must be an integer, got %r" % (seed,))
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed = integer(seed, "seed") & 0xFFFFFFFFFFFFFFFF
     if seed not in _PATTERNS:
         state, base = seed, np.empty((256, 4), np.int64)
         for i in range(256):
@@ -84,32 +83,22 @@ def _device_pattern(seed, device):
     return _DEVICE_PATTERNS[key]
 
 
-# ---- the refusals: all of them before the device is touched ----------------------------------------------------------
-def _integer(v, name, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise ValueError("%s must be an integer, got %r" % (name, v))
-    if not lo <= int(v) <= hi:
-        raise ValueError("%s must be %d .. %d, got %d" % (name, lo, hi, v))
-    return int(v)
-
-
+# ---- the refusals: all of them before the device is touched (the knobs take integer types only: 3.0 is refused) ------
 def _detect_knobs(threshold, cell, seed):
     brief_pattern(seed)
-    return _integer(threshold, "threshold", 1, 255), _integer(cell, "cell", 4, 64), int(seed)
+    return integer(threshold, "threshold", (1, 255), strict=True), integer(cell, "cell", (4, 64), strict=True), int(seed)
 
 
 def _match_knobs(max_distance, ratio, cross_check):
-    max_distance = _integer(max_distance, "max_distance", 0, 256)
+    max_distance = integer(max_distance, "max_distance", (0, 256), strict=True)
     try:
         num, den = ratio
+        num, den = integer(num, "num", strict=True), integer(den, "den", strict=True)
     except (TypeError, ValueError):
         raise ValueError("ratio must be (num, den), two positive integers with num <= den, got %r" % (ratio,))
-    for v in (num, den):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError("ratio must be (num, den), two positive integers with num <= den, got %r" % (ratio,))
     if not 1 <= num <= den <= MAX_RATIO:
         raise ValueError("ratio must be (num, den), two positive integers with num <= den <= %d, got %r" % (MAX_RATIO, ratio))
-    return max_distance, int(num), int(den), bool(cross_check)
+    return max_distance, num, den, bool(cross_check)
 
 
 def _split_knobs(knobs):
@@ -120,37 +109,15 @@ def _split_knobs(knobs):
     return _detect_knobs(*(k[n] for n in _DETECT_KNOBS)), _match_knobs(*(k[n] for n in _MATCH_KNOBS))
 
 
-def _check_images(images, what):
-    """(colour, batched, f, h, w) of uint8 images (h, w[, 3]) or (f, h, w[, 3]), checked on the host."""
+def _layout(images, what):
+    """the frames of a detector's images as ``layout`` reads them off the shape, checked on the host"""
     check_array(images, what)
-    if dtype_name(images) != "uint8":
-        raise ValueError("%s must be uint8, got %s" % (what, images.dtype))
-    shape = tuple(int(v) for v in images.shape)
-    colour = len(shape) in (3, 4) and shape[-1] == 3  # (a gray image 3 wide has no pixel 16 from its borders)
-    if len(shape) not in (2, 3, 4) or (len(shape) == 4 and not colour):
-        raise ValueError("%s must be (h, w), (f, h, w), (h, w, 3) or (f, h, w, 3), got %s" % (what, shape))
-    if 0 in shape:
-        raise ValueError("%s is empty: %s" % (what, shape))
-    batched = len(shape) - (1 if colour else 0) == 3
-    h, w = shape[-3:-1] if colour else shape[-2:]
-    f = shape[0] if batched else 1
-    if max(h, w) > MAX_SIDE or f * h >= 2 ** 31:
-        raise ValueError("%s of %s; the detector takes sides up to %d and fewer than 2^31 rows in all" % (what, shape, MAX_SIDE))
-    return colour, batched, f, h, w
+    return layout(images, what, max_side=MAX_SIDE)
 
 
 def _same_kind(arrays, names):
     if len({is_np(a) for a in arrays}) > 1:
         raise TypeError("%s must all be NumPy arrays or all be CUDA tensors" % ", ".join(names))
-
-
-def _gray(images, colour):
-    """(gray CUDA tensor, f, h, w, pitch, stride): colour goes through ``cvt_gray(code="rgb")``, gray is used as it is."""
-    from . import imgproc
-    t = imgproc._to_image(images)
-    if colour:
-        t = imgproc.cvt_gray(t, "rgb")
-    return imgproc._image_rows(t, 1)
 
 
 # ---- the stages on device tensors --------------------------------------------------------------------------------------
@@ -218,13 +185,12 @@ def _match(d1, c1, d2, c2, pairs, match_knobs):
     return _filter(c1, d1.shape[0], d2.shape[1], pairs, best12, dist12, best21, *match_knobs)
 
 
-def _detect(images, layout, detect_knobs):
+def _detect(images, lay, detect_knobs):
     """dict(xy, scores, counts, descriptors, bins) on the device for checked images"""
     threshold, cell, seed = detect_knobs
-    gray, f, h, w, pitch, stride = _gray(images, layout[0])
-    score = _score(gray, f, h, w, pitch, stride, threshold)
-    xy, scores, counts = _keypoints(score, cell)
-    desc, bins = _describe(gray, f, h, w, pitch, stride, xy, counts, seed)
+    fr = device_frames(images, lay, "rgb")
+    xy, scores, counts = _keypoints(_score(fr.data, fr.f, fr.h, fr.w, fr.pitch, fr.stride, threshold), cell)
+    desc, bins = _describe(fr.data, fr.f, fr.h, fr.w, fr.pitch, fr.stride, xy, counts, seed)
     return dict(xy=xy, scores=scores, counts=counts, descriptors=desc, bins=bins)
 
 
@@ -240,16 +206,16 @@ def _host(d, was_np):
 def _score_plane(images, threshold=20):
     """Stage A's score plane, uint8 in the shape of the gray image(s)."""
     threshold = _detect_knobs(threshold, 8, 0)[0]
-    colour, batched, *_ = _check_images(images, "images")
-    score = _score(*_gray(images, colour), threshold)
-    return _host(dict(s=score if batched else score[0]), is_np(images))["s"]
+    lay = _layout(images, "images")
+    fr = device_frames(images, lay, "rgb")
+    score = _score(fr.data, fr.f, fr.h, fr.w, fr.pitch, fr.stride, threshold)
+    return _host(dict(s=score if lay.batched else score[0]), is_np(images))["s"]
 
 
 def _keypoints_of(score, cell=8):
     """Stage A's keypoints of score planes (f, h, w) uint8 -> (xy (f, cap, 2) filled with -1, scores (f, cap), counts (f,))."""
     cell = _detect_knobs(20, cell, 0)[1]
-    layout = _check_images(score, "score")
-    if score.ndim != 3 or layout[0]:
+    if _layout(score, "score").colour or score.ndim != 3:
         raise ValueError("score must be (f, h, w), got %s" % (tuple(score.shape),))
     out = _keypoints(to_device(score), cell)
     return tuple(_host(dict(enumerate(out)), is_np(score)).values())
@@ -259,17 +225,18 @@ def _describe_at(images, xy, counts, seed=0):
     """Stage B for given keypoints: images (f, h, w[, 3]), xy (f, cap, 2) int32, counts (f,) int32 -> (descriptors
     (f, cap, 32), bins (f, cap)); a slot beyond its frame's count keeps zeros and -1."""
     _detect_knobs(20, 8, seed)
-    colour, batched, f, h, w = _check_images(images, "images")
+    lay = _layout(images, "images")
     check_array(xy, "xy")
     check_array(counts, "counts")
     _same_kind((images, xy, counts), ("images", "xy", "counts"))
     if dtype_name(xy) != "int32" or dtype_name(counts) != "int32":
         raise ValueError("xy and counts must be int32, got %s and %s" % (xy.dtype, counts.dtype))
-    if not batched or xy.ndim != 3 or tuple(xy.shape[::2]) != (f, 2) or xy.shape[1] < 1 or tuple(counts.shape) != (f,):
+    if not lay.batched or xy.ndim != 3 or tuple(xy.shape[::2]) != (lay.f, 2) or xy.shape[1] < 1 or tuple(counts.shape) != (lay.f,):
         raise ValueError("images (f, h, w[, 3]) take xy (f, cap, 2) with cap >= 1 and counts (f,), got %s, %s and %s"
                          % (tuple(images.shape), tuple(xy.shape), tuple(counts.shape)))
-    gray, f, h, w, pitch, stride = _gray(images, colour)
-    out = _describe(gray, f, h, w, pitch, stride, to_device(xy, device=gray.device), to_device(counts, device=gray.device), seed)
+    fr = device_frames(images, lay, "rgb")
+    dev = fr.data.device
+    out = _describe(fr.data, fr.f, fr.h, fr.w, fr.pitch, fr.stride, to_device(xy, device=dev), to_device(counts, device=dev), seed)
     return tuple(_host(dict(enumerate(out)), is_np(images)).values())
 
 
@@ -284,10 +251,10 @@ def detect_and_describe(images, threshold=20, cell=8, seed=0, return_info=False)
     ``return_info`` adds the orientation bin and the score (int32): two more arrays, or ``bins`` and ``scores`` in the
     dict.  An image with a side below 33 has no keypoints.  ``threshold`` 1 .. 255, ``cell`` 4 .. 64."""
     knobs = _detect_knobs(threshold, cell, seed)
-    layout = _check_images(images, "images")
-    d = _detect(images, layout, knobs)
+    lay = _layout(images, "images")
+    d = _detect(images, lay, knobs)
     keys = ("xy", "descriptors") + (("bins", "scores") if return_info else ())
-    if layout[1]:
+    if lay.batched:
         return _host({k: d[k] for k in keys[:2] + ("counts",) + keys[2:]}, is_np(images))
     n = int(d["counts"][0])
     out = _host({k: d[k][0, :n] for k in keys}, is_np(images))
@@ -395,10 +362,10 @@ def _match_two(img1, img2, knobs):
     """(uvs1, uvs2, distances) on the device, (w, h) of the first image"""
     import torch
     detect_knobs, match_knobs = _split_knobs(knobs)
-    layouts = [_check_images(img, name) for img, name in ((img1, "img1"), (img2, "img2"))]
+    layouts = [_layout(img, name) for img, name in ((img1, "img1"), (img2, "img2"))]
     _same_kind((img1, img2), ("img1", "img2"))
-    for layout, name in zip(layouts, ("img1", "img2")):
-        if layout[1]:
+    for lay, name in zip(layouts, ("img1", "img2")):
+        if lay.batched:
             raise ValueError("%s must be one image (h, w) or (h, w, 3); match_views takes batches" % name)
     a = _detect(img1, layouts[0], detect_knobs)
     dev = a["xy"].device
@@ -408,7 +375,7 @@ def _match_two(img1, img2, knobs):
     pairs = torch.zeros((1, 2), dtype=torch.int32, device=dev)
     matches, distances, counts = _match(a["descriptors"], a["counts"], b["descriptors"], b["counts"], pairs, match_knobs)
     m = int(counts[0])
-    return (_uvs(a["xy"][0], matches[0, :m, 0]), _uvs(b["xy"][0], matches[0, :m, 1]), distances[0, :m]), layouts[0][4], layouts[0][3]
+    return (_uvs(a["xy"][0], matches[0, :m, 0]), _uvs(b["xy"][0], matches[0, :m, 1]), distances[0, :m]), layouts[0].w, layouts[0].h
 
 
 def match_images(img1, img2, **knobs):
@@ -460,10 +427,10 @@ def match_views(images, pairs=None, **knobs):
         if len({str(img.dtype) for img in images}) != 1:
             raise ValueError("views must share one dtype")
         images = np.stack(images) if is_np(images[0]) else torch.stack(list(images))
-    layout = _check_images(images, "images")
-    if not layout[1]:
+    lay = _layout(images, "images")
+    if not lay.batched:
         raise ValueError("images must be a batch (f, h, w[, 3]) or a sequence of views, got %s" % (tuple(images.shape),))
-    f = layout[2]
+    f = lay.f
     if pairs is None:
         pairs = [(i, j) for i in range(f) for j in range(i + 1, f)]
     host_pairs = _check_pairs(np.asarray(pairs, np.int64).reshape(-1, 2) if len(pairs) else np.zeros((0, 2), np.int64), f, f)
@@ -474,7 +441,7 @@ def match_views(images, pairs=None, **knobs):
     host_pairs = np.sort(host_pairs, 1)
     if len({tuple(p) for p in host_pairs.tolist()}) != len(host_pairs):
         raise ValueError("pairs repeat")
-    d = _detect(images, layout, detect_knobs)
+    d = _detect(images, lay, detect_knobs)
     dev = d["xy"].device
     matches, _, counts = _match(d["descriptors"], d["counts"], d["descriptors"], d["counts"], torch.from_numpy(host_pairs).to(dev),
                                 match_knobs)

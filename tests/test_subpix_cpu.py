@@ -130,6 +130,12 @@ def test_corner_sub_pix_refuses_before_the_device():
         imgproc.corner_sub_pix(torch.zeros((20, 30), dtype=torch.uint8), torch.zeros((5, 2)))
     with pytest.raises(TypeError):
         imgproc.corner_sub_pix([[0]], c)
+    # an input that breaks two rules: the images' dtype is refused before the corners are looked at, their rank after
+    for images, corners in [(img.astype(np.float32), c.tolist()), (img.astype(np.float32), torch.zeros((5, 2))), (img.astype(np.int8), c.astype(np.int32))]:
+        with pytest.raises(ValueError, match="uint8"):
+            imgproc.corner_sub_pix(images, corners)
+    with pytest.raises(TypeError):
+        imgproc.corner_sub_pix(img[None, None, None], c.tolist())
     with pytest.raises(ValueError):
         imgproc.cvt_gray(np.zeros((4, 4), np.uint8))
     with pytest.raises(ValueError):

@@ -73,6 +73,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("gpu_features_time.py measures on the GPU; none is visible")
     from calibrating_amd import features
+    from calibrating_amd._frames import device_frames
     import features_ref as fr
     knobs = features._split_knobs({})
     threshold, cell, seed = knobs[0]
@@ -80,7 +81,8 @@ def main():
 
     for f in (1, 16, 64):
         imgs = frames_1080p(f, torch)
-        gray, f_, h, w, pitch, stride = features._gray(imgs, False)
+        fr_ = device_frames(imgs, features._layout(imgs, "images"), "rgb")
+        gray, h, w, pitch, stride = fr_.data, fr_.h, fr_.w, fr_.pitch, fr_.stride
         score = features._score(gray, f, h, w, pitch, stride, threshold)
         xy, scores, counts = features._keypoints(score, cell)
         desc, bins = features._describe(gray, f, h, w, pitch, stride, xy, counts, seed)

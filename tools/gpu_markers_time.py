@@ -61,7 +61,8 @@ def main():
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "needs a GPU: there is no CPU fallback to time"
-    from calibrating_amd import boards, imgproc
+    from calibrating_amd import boards, detect, imgproc
+    from calibrating_amd._frames import Frames
     import charuco_cases as cc
     import markers_cases as mc
     import markers_ref as ref
@@ -112,10 +113,11 @@ def main():
         gray = g1[None].repeat(f, 1, 1)
         n = min(f, imgproc.MARKER_PLANE_BUDGET // (20 * H * W))  # the stages alone on one chunk of frames
         part = gray[:n]
-        stage = lambda: imgproc._marker_stages(part, n, H, W, W, H * W, words, 25, 4, 8, 7, 12, 512, 0)  # noqa: E731
-        m = imgproc._dark_mask(part, n, H, W, W, H * W, 8, 7)
-        mask_ms = gpu_ms(lambda: imgproc._dark_mask(part, n, H, W, W, H * W, 8, 7))
-        label_ms = gpu_ms(lambda: imgproc._label_components(m))
+        fr = Frames(part, n, H, W, W, H * W, batched=True, was_np=False, colour=False)
+        stage = lambda: detect._marker_stages(fr, words, 25, 4, 8, 7, 12, 512, 0)  # noqa: E731
+        m = detect._dark_mask(fr, 8, 7)
+        mask_ms = gpu_ms(lambda: detect._dark_mask(fr, 8, 7))
+        label_ms = gpu_ms(lambda: detect._label_components(m))
         stages_ms = gpu_ms(stage)
         coarse_ms = gpu_ms(lambda: imgproc.find_markers(gray, dictionary, refine_win=None))
         whole_ms = gpu_ms(lambda: imgproc.find_markers(gray, dictionary))
@@ -125,7 +127,7 @@ def main():
                                 chunk_stages_1_to_6_ms=stages_ms, chunk_candidates_quad_decode_ms=stages_ms[0] - mask_ms[0] - label_ms[0],
                                 coarse_ms=coarse_ms, whole_ms=whole_ms, refinement_ms=whole_ms[0] - coarse_ms[0],
                                 whole_us_per_frame=1e3 * whole_ms[0] / f, find_charuco_corners_ms=charuco_ms))
-        del gray, part, m, ch
+        del gray, part, fr, m, ch
     rings = nested_rings()
     s, c, i = imgproc.find_markers(rings, dictionary, refine_win=None, return_info=True)
     boxes = i["candidates"][:int(i["counts"])]
