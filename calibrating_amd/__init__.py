@@ -15,6 +15,7 @@ from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, f
                                 flow_abs_to_normal, flow_normal_to_abs, flow_to_matched_uvs, matching_uvs_in_one_img,
                                 matching_uvs_in_one_img_batch)
 from .reconstruction_epipolar_geometry import ReconstructionExtrinsics
+from .bundle import bundle_adjust_pairs
 from .flow_utils import warp_flow
 from .geometry import mean_Ts
 from .pnp import solve_pnp_batch
@@ -37,4 +38,4 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
            "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard", "CharucoBoard", "MarkerBoard", "ArucoGridBoard",
            "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness", "find_essential_matrix",
-           "BinaryFeatureMatching", "detect_and_describe", "match_descriptors", "match_images", "match_views"]
+           "BinaryFeatureMatching", "detect_and_describe", "match_descriptors", "match_images", "match_views", "bundle_adjust_pairs"]

@@ -50,6 +50,11 @@ CALIB_STATE_DOUBLES, CALIB_WORKSPACE_DOUBLES, CALIB_CANDIDATE_DOUBLES = 40, 136,
 STEREO_STATE_DOUBLES, STEREO_WORKSPACE_DOUBLES, STEREO_CANDIDATE_DOUBLES, STEREO_PARTIAL_DOUBLES = 40, 91, 16, 36
 (STEREO_DONE, STEREO_ACCEPT, STEREO_LAMBDA, STEREO_COST, STEREO_EVALUATIONS, STEREO_ITERATIONS, STEREO_STATUS, STEREO_CONVERGED,
  STEREO_RIG, STEREO_STEP, STEREO_CANDIDATE, STEREO_SOLVED, STEREO_PIVOT) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 20, 26, 38, 39
+# camd_bundle_*: the sizes and the places of the state (CAMD_BUNDLE_*)
+BUNDLE_MAX_VIEWS, BUNDLE_CHUNK, BUNDLE_SEGMENT, BUNDLE_PARTIAL_DOUBLES, BUNDLE_EVAL_DOUBLES, BUNDLE_STATE_DOUBLES = 16, 256, 1024, 104, 4, 576
+(BUNDLE_DONE, BUNDLE_ACCEPT, BUNDLE_LAMBDA, BUNDLE_COST, BUNDLE_EVALUATIONS, BUNDLE_ITERATIONS, BUNDLE_STATUS, BUNDLE_CONVERGED,
+ BUNDLE_SOLVED, BUNDLE_PIVOT, BUNDLE_FIXED, BUNDLE_ANCHOR, BUNDLE_AXIS, BUNDLE_COST0, BUNDLE_LABEL, BUNDLE_POSES, BUNDLE_CANDIDATE,
+ BUNDLE_STEP, BUNDLE_K) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 16, 32, 224, 416, 512
 
 
 class SgbmParams(ctypes.Structure):
@@ -83,6 +88,14 @@ class StereoRig(ctypes.Structure):  # camd_stereo_rig
                 ("dist2", c_void_p), ("used", c_void_p), ("state", c_void_p), ("poses", c_void_p), ("candidate", c_void_p),
                 ("workspace", c_void_p), ("partials", c_void_p), ("frame_error", c_void_p), ("ndist1", c_int), ("ndist2", c_int),
                 ("used_n", c_int), ("reserved", c_int)]
+
+
+class Bundle(ctypes.Structure):  # camd_bundle
+    POINTERS = ("uv_a", "uv_b", "pair_views", "pair_start", "seg_first", "seg_n", "chunk_table", "pair_chunk", "status", "points",
+                "rowoff", "rowcount", "uv_used_a", "uv_used_b", "X", "candidate", "src", "partials", "pair_blocks", "eval_partials",
+                "eval_blocks", "state", "pair_error", "rows_a", "rows_b")
+    _fields_ = [(n, c_void_p) for n in POINTERS] + [("threshold", c_double), ("matches", ctypes.c_longlong), ("used", ctypes.c_longlong)] + \
+               [(n, c_int) for n in ("uv_type", "views", "pairs", "segments", "chunks", "reserved")]
 
 
 # name -> (restype, argtypes); every symbol include/calibrating_amd.h declares
@@ -221,6 +234,10 @@ SIGNATURES = {
     "camd_stereo_linearise": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
     "camd_stereo_step": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
     "camd_stereo_finish": (c_int, [ctypes.POINTER(StereoRig), c_void_p]),
+    "camd_bundle_start": (c_int, [ctypes.POINTER(Bundle), ctypes.c_longlong, c_void_p]),
+    "camd_bundle_emit": (c_int, [ctypes.POINTER(Bundle), c_void_p]),
+    "camd_bundle_step": (c_int, [ctypes.POINTER(Bundle), c_void_p]),
+    "camd_bundle_finish": (c_int, [ctypes.POINTER(Bundle), c_void_p]),
     "camd_corner_sub_pix": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_int, c_size_t, c_void_p, c_int,
                                     c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_bgr_to_gray_u8": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_int,

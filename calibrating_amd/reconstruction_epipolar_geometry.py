@@ -251,6 +251,13 @@ class ReconstructionExtrinsics:
             for uvs, zs, other in blocks[k]:
                 _pack(buf, at, uvs, zs, other)
                 at += int(uvs.shape[0])
+        self._normalise(buf, start, rows, was_np)
+
+    def _normalise(self, buf, start, rows, was_np):
+        """The class's normalisation of the packed rows ``buf`` (view k owns rows ``start[k] .. start[k] + rows[k]``) and of
+        the poses: mean depth 1 over all rows, view 0 at ``z = -its mean depth``; then every view gets its ``uvzis``."""
+        viewds = self.viewds
+        total = int(buf.shape[0])
         z_mean = _column_sum(buf, 0, total) / total
         rate = 1 / np.float64(z_mean)
         _column_scale(buf, 0, total, rate)
@@ -262,6 +269,53 @@ class ReconstructionExtrinsics:
         for k, viewd in viewds.items():
             viewd["uvzis"] = rows_all[start[k]:start[k] + rows[k]]
         self.apply_T(T=T0_target @ inv(viewds[0]["T_re"]))
+
+    def refine(self, threshold=None, fixed_view=0):
+        """Refine every view's ``T_re`` and one world point per match of EVERY pair of ``set2ds`` together
+        (``bundle.bundle_adjust_pairs``: its gauge, its refusals), write the poses back and rebuild every view's ``uvzis``
+        from the refined points: views in the order of ``viewds``, within a view the pairs in the order of ``set2ds``; then
+        the class's own normalisation.  Unlike after the constructor, ``uvzis`` then holds rows of every pair of ``set2ds``,
+        not only of the rigs the propagation built, and only of the matches the refinement used.  ``fixed_view`` is a key of
+        ``viewds``.  The result dict is kept as ``self.refinement``; -> ``self.viewds``."""
+        import torch
+        from . import bundle
+        viewds, set2ds = self.viewds, self.set2ds
+        keys = list(viewds)
+        if fixed_view not in viewds:
+            raise ValueError("fixed_view must be a key of viewds, got %r" % (fixed_view,))
+        index = {k: i for i, k in enumerate(keys)}
+        order = []  # (a, b, uvs_a, uvs_b) with index[a] < index[b], pairs in set2ds order
+        for set2, d in set2ds.items():
+            i, j = sorted(set2)
+            if int(d["uvs_i"].shape[0]) == 0:
+                continue
+            flip = index[i] > index[j]
+            order.append((j, i, d["uvs_j"], d["uvs_i"]) if flip else (i, j, d["uvs_i"], d["uvs_j"]))
+        if not order:
+            raise ValueError("set2ds holds no matches")
+        was_np = is_np(order[0][2])
+        cat = np.concatenate if was_np else torch.cat
+        res = bundle.bundle_adjust_pairs(
+            np.stack([np.asarray(viewds[k]["K"], np.float64)[:3, :3] for k in keys]), np.stack([viewds[k]["T_re"] for k in keys]),
+            np.array([(index[a], index[b]) for a, b, _, _ in order], np.int32), cat([o[2] for o in order]), cat([o[3] for o in order]),
+            np.array([int(o[2].shape[0]) for o in order], np.int64), fixed_view=index[fixed_view], threshold=threshold,
+            return_rows=True, view_labels=[float(k) for k in keys])
+        for k in keys:
+            viewds[k]["T_re"] = res["T"][index[k]].copy()
+        rows_a, rows_b = (to_device(res[n], dtype="float64") for n in ("rows_a", "rows_b"))
+        bounds = np.concatenate([[0], np.cumsum(res["used_counts"])])
+        blocks = {k: [] for k in keys}
+        for p, (a, b, _, _) in enumerate(order):
+            blocks[a].append(rows_a[bounds[p]:bounds[p + 1]])
+            blocks[b].append(rows_b[bounds[p]:bounds[p + 1]])
+        rows = {k: sum(int(x.shape[0]) for x in blocks[k]) for k in keys}
+        start, at = {}, 0
+        for k in keys:
+            start[k], at = at, at + rows[k]
+        buf = torch.cat([x for k in keys for x in blocks[k]])
+        self._normalise(buf, start, rows, was_np)
+        self.refinement = res
+        return self.viewds
 
     build_set2ds_by_flowds = staticmethod(eg.build_set2ds_by_flowds)
 

@@ -703,6 +703,81 @@ int camd_stereo_step(const camd_stereo_rig* rig, void* queue);
  * used frame.  Needs partials and frame_error.                                                                     */
 int camd_stereo_finish(const camd_stereo_rig* rig, void* queue);
 
+/* ---- the poses of N views and a world point per match, refined together (csrc/bundle.hip) ----
+ * The joint refinement after ReconstructionExtrinsics' propagation; the reference has none, the contract is this project's
+ * (INTEGRATION.md section F).  3 <= views <= CAMD_BUNDLE_MAX_VIEWS; pair p = (a, b), a < b, owns rows pair_start[p] ..
+ * pair_start[p + 1] of uv_a / uv_b ([matches][2] pinhole pixels of uv_type CAMD_VALUE_F64 / F32, read in place); every
+ * match is one world point with two observations.  A float64 Levenberg-Marquardt on pixels over 3 unknowns per used match
+ * and 6 per view (camd_pnp_refine's local update of the world-to-camera pose), solved through the Schur complement on the
+ * views' block; damping, stopping and acceptance as in camd_calib_step; a candidate that puts a used point at z <= 0 in
+ * either of its views is rejected.  Held: the pose of view [CAMD_BUNDLE_FIXED] and coordinate [CAMD_BUNDLE_AXIS] of the
+ * world centre of view [CAMD_BUNDLE_ANCHOR].  All sums have a fixed order and there are no atomics.
+ *
+ * state (CAMD_BUNDLE_STATE_DOUBLES device doubles), written by the caller before camd_bundle_start: [LAMBDA] = 1e-3,
+ * [FIXED], [ANCHOR], [AXIS], [LABEL + v] the number written for view v into the depth rows, [POSES + 12 v ..) = R (9,
+ * row-major), t (3) of view v (x_cam = R x_world + t), [K + 4 v ..) = fx fy cx cy, everything else 0.  Its first places are
+ * camd_calib's, read by camd_calib_read.
+ *
+ * camd_bundle_start: status[row] = 0 ok / 1 a non-finite coordinate / 2 the rays' midpoint is at z <= 0 in either view or
+ * |d_a x d_b| < 0.03 for the unit rays / 3 (threshold >= 0 only) the midpoint's reprojection error exceeds `threshold`
+ * pixels in either view; points[row] = the midpoint (NaN unless status 0); rowoff = the exclusive scan of the used rows of
+ * every segment (segments + 1 entries; segment s owns seg_n[s] <= CAMD_BUNDLE_SEGMENT rows from seg_first[s], of ONE pair).
+ * The caller reads rowoff, sizes the arrays below and makes chunk_table (chunks x 4 int32: pair, first used point, points
+ * <= CAMD_BUNDLE_CHUNK, 0; a chunk never straddles two pairs; rising) and pair_chunk (pairs + 1).
+ * camd_bundle_emit: the used rows, in their order, to uv_used_a / uv_used_b (used x 2 of uv_type), X (used x 3), src (used).
+ * camd_bundle_step: one evaluation; afterwards [DONE], [ACCEPT] as in camd_stereo_step (nothing else is needed between steps).
+ * camd_bundle_finish: [STATUS] 0 ok / 3 singular (a pivot of the undamped unit-diagonal reduced matrix below 1e-10, in
+ * [PIVOT]) or not stopped at 100 evaluations, [COST], [COST0]; pair_error[p] = sqrt(cost_p / 2 n_p); points[src] = the
+ * refined points; rows_a / rows_b (used x 4, or both NULL) = [u, v, z, label of the other view] of every used point in view
+ * a / view b of its pair (camd_uvzi_pack's layout).                                                                     */
+#define CAMD_BUNDLE_MAX_VIEWS 16
+#define CAMD_BUNDLE_CHUNK 256
+#define CAMD_BUNDLE_SEGMENT 1024
+#define CAMD_BUNDLE_PARTIAL_DOUBLES 104 /* S_aa 21, S_bb 21, S_ba 36, g_a 6, g_b 6, diag U_a 6, diag U_b 6, cost, points that did not factor */
+#define CAMD_BUNDLE_EVAL_DOUBLES 4      /* the candidate's cost, |dX|^2, |X|^2, points it puts behind a view */
+#define CAMD_BUNDLE_STATE_DOUBLES 576
+enum {
+    CAMD_BUNDLE_DONE = 0, CAMD_BUNDLE_ACCEPT = 1, CAMD_BUNDLE_LAMBDA = 2, CAMD_BUNDLE_COST = 3, CAMD_BUNDLE_EVALUATIONS = 4,
+    CAMD_BUNDLE_ITERATIONS = 5, CAMD_BUNDLE_STATUS = 6, CAMD_BUNDLE_CONVERGED = 7, CAMD_BUNDLE_SOLVED = 8, CAMD_BUNDLE_PIVOT = 9,
+    CAMD_BUNDLE_FIXED = 10, CAMD_BUNDLE_ANCHOR = 11, CAMD_BUNDLE_AXIS = 12, CAMD_BUNDLE_COST0 = 13, CAMD_BUNDLE_LABEL = 16,
+    CAMD_BUNDLE_POSES = 32, CAMD_BUNDLE_CANDIDATE = 224, CAMD_BUNDLE_STEP = 416, CAMD_BUNDLE_K = 512
+};
+typedef struct camd_bundle {
+    const void* uv_a;
+    const void* uv_b;
+    const int* pair_views;       /* pairs x 2 */
+    const long long* pair_start; /* pairs + 1 */
+    const long long* seg_first;  /* segments */
+    const int* seg_n;            /* segments */
+    const int* chunk_table;      /* chunks x 4 */
+    const long long* pair_chunk; /* pairs + 1 */
+    int* status;                 /* matches */
+    double* points;              /* matches x 3 */
+    unsigned long long* rowoff;  /* segments + 1 */
+    uint32_t* rowcount;          /* segments */
+    void* uv_used_a;
+    void* uv_used_b;
+    double* X;
+    double* candidate;           /* used x 3 */
+    long long* src;              /* used */
+    double* partials;            /* chunks x CAMD_BUNDLE_PARTIAL_DOUBLES */
+    double* pair_blocks;         /* pairs x CAMD_BUNDLE_PARTIAL_DOUBLES */
+    double* eval_partials;       /* chunks x CAMD_BUNDLE_EVAL_DOUBLES */
+    double* eval_blocks;         /* pairs x CAMD_BUNDLE_EVAL_DOUBLES */
+    double* state;
+    double* pair_error;          /* pairs */
+    double* rows_a;
+    double* rows_b;
+    double threshold;            /* pixels; < 0: none */
+    long long matches, used;
+    int uv_type, views, pairs, segments, chunks, reserved;
+} camd_bundle;
+/* max_pair_rows: the rows of the largest pair (the launch's width) */
+int camd_bundle_start(const camd_bundle* bundle, long long max_pair_rows, void* queue);
+int camd_bundle_emit(const camd_bundle* bundle, void* queue);
+int camd_bundle_step(const camd_bundle* bundle, void* queue);
+int camd_bundle_finish(const camd_bundle* bundle, void* queue);
+
 /* ---- detected corners refined to sub-pixel, every corner of every frame in one launch (csrc/subpix.hip) ----
  * replaces cv2.cornerSubPix(gray, corners, win, zero_zone, criteria) of Chessboard.find_image_points (boards.py:163-169):
  * UNPINNED against cv2.  One wavefront per corner, four corners per workgroup, no workgroup
