@@ -11,7 +11,7 @@ from .camera import Cam
 from .sgbm import MODE_HH, MODE_HH4, MODE_SGBM, MODE_SGBM_3WAY, StereoSGBM, StereoSGBM_create
 from .stereo_matching import FeatureMatchingAsStereoMatching, MatchingByBoard, MetaStereoMatching, SemiGlobalBlockMatching
 from .stereo_camera import Stereo
-from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, filter_overlap_uvs, find_essential_matrix,
+from .epipolar_geometry import (EssentialMatrixStereo, build_set2ds_by_flowds, filter_overlap_uvs, find_essential_matrices, find_essential_matrix,
                                 flow_abs_to_normal, flow_normal_to_abs, flow_to_matched_uvs, matching_uvs_in_one_img,
                                 matching_uvs_in_one_img_batch)
 from .reconstruction_epipolar_geometry import ReconstructionExtrinsics
@@ -37,5 +37,5 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "calibrate_camera", "CALIB_USE_INTRINSIC_GUESS", "CALIB_FIX_PRINCIPAL_POINT", "CALIB_FIX_FOCAL_LENGTH",
            "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
            "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard", "CharucoBoard", "MarkerBoard", "ArucoGridBoard",
-           "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness", "find_essential_matrix",
+           "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness", "find_essential_matrix", "find_essential_matrices",
            "BinaryFeatureMatching", "detect_and_describe", "match_descriptors", "match_images", "match_views", "bundle_adjust_pairs"]

@@ -269,6 +269,12 @@ SIGNATURES = {
     "camd_essential_moments_blocks": (c_int, [c_size_t]),
     "camd_essential_moments": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_essential_batch_hypotheses": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_int, ctypes.c_ulonglong,
+                                                c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_essential_batch_score": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "camd_essential_batch_moments": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                             c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_feature_score": (c_int, [c_void_p, c_int, c_int, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p]),
     "camd_feature_keypoints_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "camd_feature_keypoints": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

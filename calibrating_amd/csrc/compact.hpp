@@ -185,9 +185,8 @@ static inline int sum_blocks(size_t n)
 // the last step of such a sum (epipolar.hip, essential.hip), one workgroup: thread t adds the partials of blocks t, t + 256,
 // t + 512, t + 768 as (p0 + p1) + (p2 + p3) (absent ones are 0), then the block's tree
 template <int Q>
-__global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
+__device__ __forceinline__ void ep_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums, double* sh)
 {
-    __shared__ double sh[256];
     double s[Q];
     for (int q = 0; q < Q; q++) {
         double p[4];
@@ -198,6 +197,12 @@ __global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ par
         s[q] = (p[0] + p[1]) + (p[2] + p[3]);
     }
     block_tree<Q>(s, sh, sums);
+}
+template <int Q>
+__global__ __launch_bounds__(256) void k_ep_final(const double* __restrict__ partials, int nblocks, double* __restrict__ sums)
+{
+    __shared__ double sh[256];
+    ep_final<Q>(partials, nblocks, sums, sh);
 }
 
 }  // namespace camd

@@ -9,7 +9,8 @@ intersection, the overlap filter, the depth of every match under all four candid
 compaction and conversions.  The essential matrix itself is an SVD of at most 199 x 9 numbers (the reference subsamples
 ``[:: n // 100]``) followed by 3 x 3 algebra: init-time work on the host in NumPy float64, fed with the strided subsample
 only.  ``find_essential_matrix`` / ``EssentialMatrixStereo(robust=...)`` is the opt-in estimate for matches that hold
-wrong pairs: RANSAC over 8-point samples, every hypothesis scored against every match on the device (csrc/essential.hip).
+wrong pairs: RANSAC over 8-point samples, every hypothesis scored against every match on the device (csrc/essential.hip);
+``find_essential_matrices`` is the same estimate for every pair of a batch in one pass, bit for bit.
 
 Arguments are checked before the device is touched.  Deviations from the reference:
 ``precise=True`` is refused, ``xy1`` / ``xy2`` are required, non-finite coordinates and cell windows beyond 2^28 cells
@@ -327,6 +328,204 @@ def find_essential_matrix(uvs1, uvs2, K1, K2=None, threshold=1.0, hypotheses=102
         return E
     info.update(E=E, n_inliers=count, inliers=to_caller(mask != 0, rows.was_np))
     return info
+
+
+# ---- find_essential_matrices: every pair of a batch in one pass -----------------------------------------------------------
+ESSENTIAL_SCORE_ROWS = 1024  # rows a workgroup of the batch's score kernel owns (256 * ESS_SCORE_ROWS)
+ESSENTIAL_LDS_SUM = True  # the score kernel adds the four waves' counts in LDS (DESIGN.md has the timing of both)
+STATUS_OK, STATUS_DEGENERATE, STATUS_TOO_FEW = 0, 1, 2
+
+
+def essential_moments_blocks(n):
+    """``camd_essential_moments_blocks(n)`` without the library: clamp(ceil(n / 256), 1, 1024)."""
+    return min(max(-(-int(n) // 256), 1), 1024)
+
+
+def essential_score_blocks(counts):
+    """The score kernel's block table, counts in, table out: ``(B, 4)`` int32 rows ``(pair, g, G, 0)`` -- workgroup ``g`` of the
+    pair's ``G`` owns the pair's rows ``1024 g .. 1024 g + 1023`` -- for the pairs of at least 8 rows, pairs in order.  No
+    block names two pairs; every row of such a pair lies in exactly one block."""
+    table = []
+    for p, n in enumerate(int(c) for c in counts):
+        if n >= 8:
+            G = -(-n // ESSENTIAL_SCORE_ROWS)
+            table += [(p, g, G, 0) for g in range(G)]
+    return np.array(table, np.int32).reshape(-1, 4)
+
+
+def essential_moments_tables(counts, take):
+    """The moments launch's two tables for the pairs ``take`` marks: blocks ``(B, 4)`` int32 ``(pair, g, G, 0)`` with ``G =
+    essential_moments_blocks(rows of the pair)`` -- thread ``t`` of workgroup ``g`` adds the pair's rows ``256 g + t, + 256 G,
+    ...`` -- and finals ``(F, 4)`` ``(pair, the pair's first block, G, 0)``."""
+    blocks, finals = [], []
+    for p, n in enumerate(int(c) for c in counts):
+        if take[p]:
+            G = essential_moments_blocks(n)
+            finals.append((p, len(blocks), G, 0))
+            blocks += [(p, g, G, 0) for g in range(G)]
+    return np.array(blocks, np.int32).reshape(-1, 4), np.array(finals, np.int32).reshape(-1, 4)
+
+
+def _essential_batch_checks(K, pairs, uvs_a, uvs_b, counts, threshold, hypotheses):
+    """Every refusal of find_essential_matrices that needs no device -> (pairs (P, 2) int64, counts (P,) int64, the pair
+    table's host part (P, 21) float64 without the row columns: inv(K_a), inv(K_b), threshold2 on the rays)."""
+    _float_rows(uvs_a, "uvs_a")
+    _float_rows(uvs_b, "uvs_b", uvs_a)
+    if dtype_name(uvs_a) not in FLOAT_TYPES or dtype_name(uvs_b) != dtype_name(uvs_a):
+        raise ValueError("uvs_a, uvs_b must both be float64 or both float32, got %s and %s" % (dtype_name(uvs_a), dtype_name(uvs_b)))
+    M = int(uvs_a.shape[0])
+    if int(uvs_b.shape[0]) != M or M >= 2 ** 31:
+        raise ValueError("uvs_a, uvs_b must hold the same number (below 2^31) of matches, got %d and %d" % (M, uvs_b.shape[0]))
+    K = np.asarray(K, np.float64)
+    if K.ndim != 3 or K.shape[1:] != (3, 3):
+        raise ValueError("K must be (N, 3, 3), got %s" % (K.shape,))
+    pairs = np.asarray(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+        raise ValueError("pairs must be (P, 2) integers, got shape %s dtype %s" % (pairs.shape, pairs.dtype))
+    if pairs.shape[0] == 0:
+        raise ValueError("find_essential_matrices needs at least one pair (P == 0)")
+    pairs = pairs.astype(np.int64)
+    if (pairs < 0).any() or (pairs >= K.shape[0]).any():
+        raise ValueError("a pair names a view outside 0 .. %d" % (K.shape[0] - 1))
+    if (pairs[:, 0] == pairs[:, 1]).any():
+        raise ValueError("every pair (a, b) must have a != b")
+    counts = np.asarray(counts)
+    if counts.shape != (len(pairs),) or counts.dtype.kind not in "iu" or (counts < 0).any():
+        raise ValueError("counts must be (P,) non-negative integers, got shape %s dtype %s" % (counts.shape, counts.dtype))
+    counts = counts.astype(np.int64)
+    if int(counts.sum()) != M:
+        raise ValueError("counts sum to %d, uvs_a has %d rows" % (int(counts.sum()), M))
+    named = np.unique(pairs)
+    if not np.isfinite(K[named]).all():
+        raise ValueError("K of every view a pair names must be finite")
+    if (np.abs(np.linalg.det(K[named])) == 0).any():
+        raise ValueError("K of every view a pair names must be an invertible camera matrix")
+    Ka, Kb = K[pairs[:, 0]], K[pairs[:, 1]]
+    focal = (Ka[:, 0, 0] + Ka[:, 1, 1] + Kb[:, 0, 0] + Kb[:, 1, 1]) / 4
+    if not (focal > 0).all():
+        raise ValueError("K1, K2 must be invertible camera matrices with a positive mean focal length")
+    if int(hypotheses) != hypotheses or not 1 <= int(hypotheses) <= ESSENTIAL_MAX_HYPOTHESES:
+        raise ValueError("hypotheses must be an integer in 1 .. 2^20, got %r" % (hypotheses,))
+    if not (float(threshold) > 0 and np.isfinite(float(threshold))):
+        raise ValueError("threshold must be a positive number of pixels, got %r" % (threshold,))
+    if is_np(uvs_a) and not (np.isfinite(uvs_a).all() and np.isfinite(uvs_b).all()):
+        raise ValueError("find_essential_matrices: u, v must be finite")
+    inv_of = {int(v): Kinv9(K[v]) for v in named}
+    table = np.zeros((len(pairs), 21))
+    for p, (a, b) in enumerate(pairs):
+        thr = float(threshold) / focal[p]
+        table[p, 2:11], table[p, 11:20], table[p, 20] = inv_of[int(a)], inv_of[int(b)], thr * thr
+    return pairs, counts, table
+
+
+def _essential_batch_stages(uvs_a, uvs_b, counts, table, hypotheses, seed, lds_sum=None):
+    """The search of every pair: device (samples (P, H, 8), Es (P, H, 9), counts (P, H), winner (P, 11)) and the call's ``batch``
+    arguments; one launch per stage, nothing is read back."""
+    import torch
+    was_np = is_np(uvs_a)
+    ua, stride_a = _EssentialRows._in_place(to_device(uvs_a) if was_np else uvs_a)
+    dev = ua.device
+    if not was_np and uvs_b.device != dev:
+        raise ValueError("inputs live on different devices: %s and %s" % (uvs_b.device, dev))
+    ub, stride_b = _EssentialRows._in_place(to_device(uvs_b, device=dev) if was_np else uvs_b)
+    P, M = len(counts), int(ua.shape[0])
+    table[:, 0:2].view(np.int64)[:] = np.stack([np.cumsum(counts) - counts, counts], 1)
+    d_table = torch.from_numpy(table).to(dev)
+    batch = (ua.data_ptr(), ub.data_ptr(), FLOAT_TYPES[dtype_name(ua)], M, stride_a, stride_b, d_table.data_ptr(), P)
+    keep = (ua, ub, d_table)  # (alive while the launches are queued)
+    samples = torch.empty((P, hypotheses, 8), dtype=torch.int32, device=dev)
+    Es = torch.empty((P, hypotheses, 9), dtype=torch.float64, device=dev)
+    call("camd_essential_batch_hypotheses", dev, *batch, int(seed) & 0xFFFFFFFFFFFFFFFF, hypotheses, samples.data_ptr(), Es.data_ptr(),
+         what="find_essential_matrices")
+    blocks = torch.from_numpy(essential_score_blocks(counts)).to(dev)
+    hcounts = torch.empty((P, hypotheses), dtype=torch.int32, device=dev)
+    winner = torch.empty((P, 11), dtype=torch.float64, device=dev)
+    call("camd_essential_batch_score", dev, *batch, blocks.data_ptr(), int(blocks.shape[0]), Es.data_ptr(), hypotheses,
+         int(ESSENTIAL_LDS_SUM if lds_sum is None else lds_sum), hcounts.data_ptr(), winner.data_ptr(), what="find_essential_matrices")
+    return samples, Es, hcounts, winner, batch, keep
+
+
+def _essential_batch_moments(batch, counts, take, E, E_stride):
+    """Stage 3 of the pairs ``take`` marks, each with its matrix ``E[pair * E_stride ..]`` (device): (mask (M,) uint8, zero on
+    the rows of the other pairs, sums (P, 46) float64) on the device."""
+    import torch
+    dev = E.device
+    P, M = len(counts), batch[3]
+    blocks, finals = (torch.from_numpy(t).to(dev) for t in essential_moments_tables(counts, take))
+    mask = torch.zeros(M, dtype=torch.uint8, device=dev)
+    partials = torch.empty((int(blocks.shape[0]), 46), dtype=torch.float64, device=dev)
+    sums = torch.zeros((P, 46), dtype=torch.float64, device=dev)
+    call("camd_essential_batch_moments", dev, *batch, blocks.data_ptr(), int(blocks.shape[0]), finals.data_ptr(), int(finals.shape[0]),
+         E.data_ptr(), int(E_stride), mask.data_ptr(), partials.data_ptr(), sums.data_ptr(), what="find_essential_matrices")
+    return mask, sums
+
+
+def find_essential_matrices(K, pairs, uvs_a, uvs_b, counts, threshold=1.0, hypotheses=1024, seed=0, refine=True):
+    """``find_essential_matrix`` for every pair of a batch in one pass: one launch per stage for all pairs and a constant
+    number of read-backs (the winners, the winners' sums, the refits' sums; for tensors the finite check) instead of three
+    per pair.  The argument layout is ``bundle_adjust_pairs``' own: ``K`` (N, 3, 3); ``pairs`` (P, 2) integers, ``a != b``
+    (either order: ``uvs_a`` shows view ``pairs[p, 0]``); ``uvs_a`` / ``uvs_b`` (M, 2) pinhole pixels, both float32 or both
+    float64, ndarrays or CUDA tensors read in place (a view with ``u, v`` side by side included); ``counts`` (P,) rows of
+    each pair, the pairs' rows one after the other.
+
+    -> ``dict(E (P, 3, 3) host float64, inliers (M,) bool of the caller's kind, n_inliers, hypothesis, hypothesis_inliers
+    (P,) int64, refined (P,) bool, status (P,) int64)``.  ``status``: 0 ok; 1 degenerate (no sample determined a matrix:
+    ``E`` zero, no inliers -- ``find_essential_matrix``'s ``"degenerate"``); 2 fewer than 8 rows, the empty pair included
+    (``E`` zero, no inliers).  For every pair of status 0 or 1 every field equals, bit for bit, what
+    ``find_essential_matrix(uvs_a[rows of p], uvs_b[rows of p], K[a], K[b], threshold, hypotheses, seed, refine,
+    return_info=True)`` returns for that pair alone, whatever the other pairs are and wherever it stands: every pair uses
+    the same ``seed``, its own ``threshold / f``, sample indices local to its rows, and its moments are summed in the single
+    call's order; the rank-2 forcing and the refit's ``eigh`` (one call on the stacked moments) stay on the host.
+
+    ``ValueError`` before the device is touched (for tensors after the one finite reduction): everything
+    ``find_essential_matrix`` refuses per argument; ``pairs`` out of range or with ``a == b``; ``counts`` negative or not
+    summing to M; ``M >= 2^31``; ``P == 0``; a ``K`` of a view some pair names that is not finite or not invertible."""
+    import torch
+    pairs, counts, table = _essential_batch_checks(K, pairs, uvs_a, uvs_b, counts, threshold, hypotheses)
+    was_np = is_np(uvs_a)
+    if not was_np and not bool(torch.isfinite(uvs_a).all() & torch.isfinite(uvs_b).all()):
+        raise ValueError("find_essential_matrices: u, v must be finite")
+    P, M, H = len(pairs), int(uvs_a.shape[0]), int(hypotheses)
+    res = dict(E=np.zeros((P, 3, 3)), n_inliers=np.zeros(P, np.int64), hypothesis=np.zeros(P, np.int64),
+               hypothesis_inliers=np.zeros(P, np.int64), refined=np.zeros(P, bool), status=np.where(counts < 8, STATUS_TOO_FEW, STATUS_OK))
+    if (counts < 8).all():  # nothing to estimate: no kernel is queued
+        if was_np:
+            res["inliers"] = np.zeros(M, bool)
+        else:
+            res["inliers"] = torch.zeros(M, dtype=torch.bool, device=uvs_a.device)
+        return res
+    _, _, _, winner, batch, keep = _essential_batch_stages(uvs_a, uvs_b, counts, table, H, seed)
+    dev = winner.device
+    won = winner.cpu().numpy()  # synchronises: the one read-back of the search, all pairs
+    live = counts >= 8
+    res["hypothesis"][live], res["hypothesis_inliers"][live] = won[live, 9].astype(np.int64), won[live, 10].astype(np.int64)
+    res["status"][live & (won[:, 10] == 0)] = STATUS_DEGENERATE
+    take = res["status"] == STATUS_OK
+    res["n_inliers"][take] = res["hypothesis_inliers"][take]
+    mask = torch.zeros(M, dtype=torch.uint8, device=dev)
+    if take.any():
+        for p in np.flatnonzero(take):
+            res["E"][p] = _force_rank2(won[p, :9].reshape(3, 3))
+        mask, sums = _essential_batch_moments(batch, counts, take, winner, 11)
+        if refine:
+            idx = np.flatnonzero(take)
+            Ms = np.zeros((len(idx), 9, 9))
+            Ms[(slice(None),) + np.tril_indices(9)] = sums.cpu().numpy()[idx, :45]  # synchronises: the winners' sums
+            vectors = np.linalg.eigh(Ms, UPLO="L")[1][:, :, 0]  # ONE call on the stacked moments
+            E_fit = np.zeros((P, 9))
+            for k, p in enumerate(idx):
+                E_fit[p] = _force_rank2(_positive_largest(vectors[k]).reshape(3, 3)).reshape(9)
+            mask_fit, sums_fit = _essential_batch_moments(batch, counts, take, torch.from_numpy(E_fit).to(dev), 9)
+            fit_counts = sums_fit[:, 45].cpu().numpy().astype(np.int64)  # synchronises: the refits' sums
+            kept = take & (fit_counts >= res["hypothesis_inliers"])
+            res["refined"] = kept
+            res["E"][kept], res["n_inliers"][kept] = E_fit[kept].reshape(-1, 3, 3), fit_counts[kept]
+            if kept.any():  # rows of the pairs whose refit is kept take its mask, the others the winner's
+                rows_kept = torch.repeat_interleave(torch.from_numpy(kept).to(dev), torch.from_numpy(counts).to(dev), output_size=M)
+                mask = torch.where(rows_kept, mask_fit, mask)
+    del keep
+    res["inliers"] = to_caller(mask != 0, was_np)
+    return res
 
 
 # ---- filter_overlap_uvs ------------------------------------------------------------------------------------------------
@@ -662,10 +861,13 @@ class EssentialMatrixStereo(Stereo):
     ``robust=None``: the reference's plain 8-point fit of a subsample, as ever.  ``robust=True`` or a dict of
     ``find_essential_matrix``'s keyword arguments (threshold, hypotheses, seed, refine): ``E`` comes from there, the
     candidate is chosen by the mean depths of the INLIERS, ``zs1`` / ``zs2`` still hold every match, and ``epipolar`` gains
-    ``inliers`` ((n,) bool of the caller's kind) and ``n_inliers``; ``self.robust_info`` is the estimator's whole answer."""
+    ``inliers`` ((n,) bool of the caller's kind) and ``n_inliers``; ``self.robust_info`` is the estimator's whole answer.
+    ``estimate``: a ``find_essential_matrix(..., return_info=True)`` answer for these very matches, oriented view 1 -> view 2
+    (``find_essential_matrices`` gives every pair's in one pass): nothing is estimated, ``E``, ``inliers`` and ``n_inliers``
+    come from it and the rest is the ``robust`` branch; giving both is a ``ValueError``."""
 
     def __init__(self, uvs1=None, uvs2=None, K1=None, K2=None, baseline=1, xy1=None, xy2=None, name1="cam1", name2="cam2",
-                 robust=None):
+                 robust=None, estimate=None):
         if uvs1 is None:  # (type(self)() as Stereo.copy makes it)
             super().__init__()
             return
@@ -684,11 +886,16 @@ class EssentialMatrixStereo(Stereo):
         K1, K2 = np.asarray(K1, np.float64), np.asarray(K2, np.float64)
         if K1.shape != (3, 3) or K2.shape != (3, 3):
             raise ValueError("K1, K2 must be 3x3")
+        if robust is not None and estimate is not None:
+            raise ValueError("EssentialMatrixStereo: give robust or estimate, not both")
         info = None
-        if robust is None:
+        if robust is None and estimate is None:
             E, Ts = _pose_candidates(uvs1, uvs2, K1, K2, baseline)
         else:
-            info = find_essential_matrix(uvs1, uvs2, K1, K2, return_info=True, **({} if robust is True else dict(robust)))
+            if estimate is not None:
+                info = dict(estimate)
+            else:
+                info = find_essential_matrix(uvs1, uvs2, K1, K2, return_info=True, **({} if robust is True else dict(robust)))
             if info["status"] != "ok":
                 raise ValueError("EssentialMatrixStereo: no 8 of the matches determine an essential matrix (%s)" % info["status"])
             E, Ts = info["E"], _scaled_candidates(info["E"], baseline)
@@ -713,12 +920,12 @@ class EssentialMatrixStereo(Stereo):
             self.robust_info = info
 
     @classmethod
-    def from_stereo(cls, uvs1, uvs2, stereo, baseline=None, robust=None):
+    def from_stereo(cls, uvs1, uvs2, stereo, baseline=None, robust=None, estimate=None):
         """The pose re-estimated from matches for an existing rig: everything of ``stereo``'s record is kept (distortion
-        included), ``R`` and ``t`` are replaced (:152-166).  ``baseline=None``: the rig's own.  ``robust``: as the
-        constructor's."""
+        included), ``R`` and ``t`` are replaced (:152-166).  ``baseline=None``: the rig's own.  ``robust``, ``estimate``: as
+        the constructor's."""
         self = cls(uvs1, uvs2, K1=stereo.cam1.K, K2=stereo.cam2.K, xy1=stereo.cam1.xy, xy2=stereo.cam2.xy,
-                   baseline=baseline or stereo.baseline, robust=robust)
+                   baseline=baseline or stereo.baseline, robust=robust, estimate=estimate)
         rec = stereo.dump(return_dict=True)
         rec["R"], rec["t"] = self.R, self.t
         self.load(rec)

@@ -120,13 +120,72 @@ def _pack(buf, row0, uvs, zs, other):
          buf.data_ptr(), int(buf.shape[0]), row0, what="ReconstructionExtrinsics")
 
 
+def _inlier_rows(uvs_a, uvs_b, inliers, total):
+    """``(uvs_a[inliers], uvs_b[inliers])`` of device rows, order kept, without a read-back: ``total`` = the number of
+    inliers, which the estimator has already reported.  The emit step of the compaction ``filter_overlap_uvs`` uses."""
+    import torch
+    dev, n = uvs_a.device, int(uvs_a.shape[0])
+    a, b = uvs_a.contiguous(), uvs_b.contiguous()
+    blocks = _native.lib().camd_overlap_blocks(n)
+    keep = torch.zeros(blocks * 256, dtype=torch.uint8, device=dev)
+    keep[:n] = inliers
+    start = torch.zeros(blocks + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(keep.view(blocks, 256).sum(1, dtype=torch.int64), 0, out=start[1:])  # the exclusive scan between count and emit
+    out = torch.empty((2, total, 2), dtype=a.dtype, device=dev)
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    call("camd_overlap_emit", dev, a.data_ptr(), b.data_ptr(), FLOAT_TYPES[dtype_name(a)], n, 2, keep.data_ptr(), start.data_ptr(),
+         out[0].data_ptr(), out[1].data_ptr(), total, counter.data_ptr(), what="ReconstructionExtrinsics")
+    return out[0], out[1]
+
+
+def robust_set2ds(viewds, set2ds, robust):
+    """``cfg["robust"]``: every pair of ``set2ds`` through ONE ``find_essential_matrices`` call (pairs in ``set2ds`` order, the
+    lower key first, ``K`` from ``viewds``) -> (the pairs reduced to their inliers, order kept: ``{set2: dict(uvs_i, uvs_j)}``,
+    new dicts; the estimator's answer with ``keys``: the pairs' ``(i, j)``).  A pair whose status is not 0 is left with 0
+    rows."""
+    import torch
+    kw = {} if robust is True else dict(robust)
+    keys = list(viewds)
+    index = {k: n for n, k in enumerate(keys)}
+    order = [tuple(sorted(set2)) for set2 in set2ds]
+    parts_i, parts_j = [set2ds[frozenset(ij)]["uvs_i"] for ij in order], [set2ds[frozenset(ij)]["uvs_j"] for ij in order]
+    was_np = is_np(parts_i[0])
+    cat = np.concatenate if was_np else torch.cat
+    uvs_i, uvs_j = cat(parts_i), cat(parts_j)
+    counts = np.array([int(p.shape[0]) for p in parts_i], np.int64)
+    K = np.stack([np.asarray(viewds[k]["K"], np.float64)[:3, :3] for k in keys])
+    res = eg.find_essential_matrices(K, np.array([(index[i], index[j]) for i, j in order], np.int64).reshape(-1, 2), uvs_i, uvs_j,
+                                     counts, **kw)
+    res["keys"] = order
+    kept = np.where(res["status"] == 0, res["n_inliers"], 0)
+    if not was_np and int(kept.sum()):
+        rows_i, rows_j = _inlier_rows(uvs_i, uvs_j, res["inliers"], int(kept.sum()))
+    else:
+        rows_i, rows_j = uvs_i[:0], uvs_j[:0]
+    bounds, at = np.concatenate([[0], np.cumsum(counts)]), np.concatenate([[0], np.cumsum(kept)])
+    filtered = {}
+    for p, ij in enumerate(order):
+        if was_np:
+            on = res["inliers"][bounds[p]:bounds[p + 1]]
+            filtered[frozenset(ij)] = dict(uvs_i=parts_i[p][on], uvs_j=parts_j[p][on])
+        else:
+            filtered[frozenset(ij)] = dict(uvs_i=rows_i[at[p]:at[p + 1]], uvs_j=rows_j[at[p]:at[p + 1]])
+    return filtered, res
+
+
 class ReconstructionExtrinsics:
     def __init__(self, viewds, set2ds=None, flowds=None, cfg=None):
         """``viewds[k]``: ``K`` and the view's size (``img`` / ``xy`` / ``mask``); ``set2ds[frozenset((i, j))]``: ``uvs_i``,
         ``uvs_j`` matched points of the pair, i < j -- or ``flowds[(a, b)]``: ``flow_abs`` / ``flow_normal`` and
         ``common_fov_mask``, from which ``set2ds`` is built.  Afterwards every view holds ``T_re`` (4x4 float64 ndarray,
         camera to world) and ``uvzis`` ((m, 4) float64 rows [u, v, z, other view]: ndarray for ndarray matches, CUDA tensor
-        for tensor matches); mean depth 1 over all views, view ``0`` at ``z = -its mean depth`` looking down +z."""
+        for tensor matches); mean depth 1 over all views, view ``0`` at ``z = -its mean depth`` looking down +z.
+
+        ``cfg["robust"]``: ``True`` or a dict of ``find_essential_matrices``' keywords (threshold, hypotheses, seed, refine) for
+        matches that hold wrong pairs -- every pair is estimated robustly in one pass and reduced to its inliers before
+        anything else (``robust_set2ds``); the rigs then take the pair's ``E`` from there instead of the plain 8-point fit.
+        ``self.set2ds`` holds the filtered pairs (``refine()`` bundles inliers only), ``self.set2ds_all`` the caller's, which
+        are not mutated, ``self.robust`` the estimator's answer.  Absent or ``None``: the constructor as ever."""
         self.cfg = cfg or {}
         self.viewds = viewds
         stage = self.cfg.get("triple_stage", TRIPLE_STAGE)
@@ -145,8 +204,25 @@ class ReconstructionExtrinsics:
             set2ds = self.build_set2ds_by_flowds(viewds, flowds)
         if not set2ds:
             raise ValueError("set2ds or flowds with at least one pair of views is required")
+        self.set2ds_all, self.robust = set2ds, None
+        estimates = {}
+        if self.cfg.get("robust") is not None:
+            set2ds, self.robust = robust_set2ds(viewds, set2ds, self.cfg["robust"])
+            for p, ij in enumerate(self.robust["keys"]):
+                if self.robust["status"][p] == 0:
+                    estimates[ij] = self.robust["E"][p]
         self.set2ds = set2ds
         self.flowds = flowds
+
+        def estimate_of(ii, jj, uvs):
+            """the pair's answer oriented ii -> jj for its filtered rows: every row is an inlier"""
+            if self.robust is None:
+                return None
+            import torch
+            n = int(uvs.shape[0])
+            E = estimates[(ii, jj)] if ii < jj else estimates[(jj, ii)].T
+            ones = np.ones(n, bool) if is_np(uvs) else torch.ones(n, dtype=torch.bool, device=uvs.device)
+            return dict(E=np.array(E), inliers=ones, n_inliers=n, status="ok")
 
         def uvsd_of(idx_sorted):
             ii, jj, kk = idx_sorted
@@ -199,7 +275,8 @@ class ReconstructionExtrinsics:
                 if (ii, jj) not in stereods:
                     stereods[(ii, jj)] = eg.EssentialMatrixStereo(
                         uvsd[jj]["uvs_main"], uvsd[jj]["uvs_other"], K1=viewds[ii]["K"], K2=viewds[jj]["K"], xy1=xys[ii],
-                        xy2=xys[jj], name1=ii, name2=jj, baseline=propagate_baseline.get(frozenset([ii, jj]), 1))
+                        xy2=xys[jj], name1=ii, name2=jj, baseline=propagate_baseline.get(frozenset([ii, jj]), 1),
+                        estimate=estimate_of(ii, jj, uvsd[jj]["uvs_main"]))
                 return stereods[(ii, jj)]
 
             stereo_new = get_stereo(idx_main, idx_new)

@@ -1044,6 +1044,31 @@ int camd_essential_moments_blocks(size_t n);
 int camd_essential_moments(const void* uv1, const void* uv2, int uv_type, size_t n, int uv1_stride, int uv2_stride,
                            const double K1inv[9], const double K2inv[9], const double* E, double threshold2, uint8_t* mask,
                            double* partials_ws, double* sums, void* queue);
+/* The same three stages for MANY pairs of views, one launch a stage (the device side of find_essential_matrices).  uv_a, uv_b:
+ * [m][stride] as above, 1 <= m < 2^31, the pairs' rows one after the other.  pair_table (device, [pairs][21] doubles): pair p's
+ * [0], [1] = its first row and its number of rows as int64 BIT PATTERNS, [2 .. 10] = inv(K) of the view uv_a shows, [11 .. 19] =
+ * of the view uv_b shows, [20] = its threshold2.  A record that leaves the m rows is skipped by every kernel.  Pair p's outputs
+ * are, bit for bit, what the single entries give for its rows alone: sample indices are local to the pair, every pair runs the
+ * streams of `seed`, and the kernels' bodies are the single entries' own.
+ * Stage 1: samples [pairs][hypotheses][8], Es [pairs][hypotheses][9]; a pair of fewer than 8 rows gets samples -1 and Es 0.  */
+int camd_essential_batch_hypotheses(const void* uv_a, const void* uv_b, int uv_type, size_t m, int uv_a_stride, int uv_b_stride,
+                                    const double* pair_table, int pairs, unsigned long long seed, int hypotheses, int* samples,
+                                    double* Es, void* queue);
+/* Stage 2: counts [pairs][hypotheses] int32 (cleared here), winner [pairs][11].  block_table (device, [blocks][4] int32,
+ * 16-aligned): workgroup b owns rows 1024 g .. 1024 g + 1023 of pair block_table[b] = (pair, g, -, -), so no workgroup reads two
+ * pairs; pairs of fewer than 8 rows have no workgroup and keep count 0.  lds_sum != 0: the four waves' counts of a hypothesis are
+ * added in LDS and ONE atomic per (workgroup, hypothesis) reaches memory; 0: one per wave.  The counts are the same either way. */
+int camd_essential_batch_score(const void* uv_a, const void* uv_b, int uv_type, size_t m, int uv_a_stride, int uv_b_stride,
+                               const double* pair_table, int pairs, const int* block_table, int blocks, const double* Es,
+                               int hypotheses, int lds_sum, int* counts, double* winner, void* queue);
+/* Stage 3 for one matrix per pair, E + pair * E_stride (device), of the pairs the tables name: block_table[b] = (pair, g, G, -)
+ * makes workgroup b the g-th of the G = camd_essential_moments_blocks(rows of the pair) that sum the pair, its partials the b-th 46
+ * of partials_ws ([blocks][46]); final_table[f] = (pair, the pair's first workgroup, G, -) sums them into sums[pair] ([pairs][46]).
+ * mask: the ONE [m] array; rows and sums of pairs no table names are left as they are.                                    */
+int camd_essential_batch_moments(const void* uv_a, const void* uv_b, int uv_type, size_t m, int uv_a_stride, int uv_b_stride,
+                                 const double* pair_table, int pairs, const int* block_table, int blocks, const int* final_table,
+                                 int finals, const double* E, int E_stride, uint8_t* mask, double* partials_ws, double* sums,
+                                 void* queue);
 
 /* ---- keypoints, binary descriptors and a brute-force Hamming matcher: matches from two pictures (csrc/features.hip) ----
  * A contract of this library's OWN, NOT cv2.ORB / cv2.BFMatcher (UNPINNED):
