@@ -244,11 +244,13 @@ class Problem:
             out.append(point_terms((R[a], t[a], self.k[a]), (R[b], t[b], self.k[b]), X[s:e], self.ua[s:e], self.ub[s:e], lam))
         return out
 
-    def system(self, terms):
+    def system(self, terms, blocks=None):
+        """S, g, diag U over all views, the cost, the points that did not factor, the pairs' costs; ``blocks``: the pairs'
+        sums where they are not ``pair_block`` of the terms"""
         n6 = 6 * self.N
         S, g, dU, cost, bad, pair_cost = np.zeros((n6, n6)), np.zeros(n6), np.zeros(n6), 0.0, 0, []
-        for (a, b), o in zip(self.pairs, terms):
-            blk = pair_block(o)
+        for p, ((a, b), o) in enumerate(zip(self.pairs, terms)):
+            blk = pair_block(o) if blocks is None else blocks[p]
             sa, sb = slice(6 * a, 6 * a + 6), slice(6 * b, 6 * b + 6)
             S[sa, sa] += blk["aa"]
             S[sb, sb] += blk["bb"]
@@ -271,6 +273,103 @@ class Problem:
         M[s, s] = anchor_matrix(R[self.anchor], t[self.anchor])
         A, g = M.T @ A @ M, M.T @ g
         return A[np.ix_(self.keep, self.keep)], g[self.keep], M
+
+
+def shared_step(prob, S, g, dU, lam, R, t):
+    """(y, x): the step of every view in its gauge parameters (6 N; zero where held) and x = M y, every view's (w, d); None
+    where the damped reduced matrix does not factor or the step is not finite"""
+    A, gk, M = prob.reduced(S, g, dU, lam, R, t)
+    L, _ = _cholesky(A)
+    if L is None:
+        return None
+    y = _solve(L, -gk)
+    if not np.isfinite(y).all():
+        return None
+    yy = np.zeros(6 * prob.N)
+    yy[prob.keep] = y
+    return yy, M @ yy
+
+
+def candidate_poses(prob, R, t, yy):
+    """every view's candidate: R' = exp([w]x) R, t' = t + d; the anchor's c' = c + e, t' = -R' c'"""
+    R2, t2 = R.copy(), t.copy()
+    for v in range(prob.N):
+        w = yy[6 * v:6 * v + 6]
+        R2[v] = rotate_left(w[:3], R[v])
+        if v == prob.anchor:
+            c2v = -(R[v].T @ t[v]) + w[3:]
+            t2[v] = -(R2[v] @ c2v)
+        else:
+            t2[v] = t[v] + w[3:]
+    return R2, t2
+
+
+def point_steps(o, da, db):
+    """dX (n, 3) of one pair's points from its terms and the (w, d) steps of its two views"""
+    n = len(o["y"])
+    sa, sb = np.zeros((n, 3)), np.zeros((n, 3))
+    for p in range(6):
+        sa, sb = sa + o["Za"][:, :, p] * da[p], sb + o["Zb"][:, :, p] * db[p]
+    r = -(o["y"] + (sa + sb))
+    l10, l20, l21 = o["L"]
+    i0, i1, i2 = o["il"]
+    d2 = r[:, 2] * i2
+    d1 = (r[:, 1] - l21 * d2) * i1
+    d0 = (r[:, 0] - l10 * d1 - l20 * d2) * i0
+    return np.stack([d0, d1, d2], 1)
+
+
+def candidate(prob, R, t, X, terms, yy, x, steps=point_steps):
+    """the candidate of one evaluation: dict(R2, t2, X2, c2 (infinite where a point lies behind a view), step, norm (the
+    squared sizes lm_small compares), pairs: per pair (cost, |dX|^2, |X|^2, bad) with bad the points behind a view)"""
+    R2, t2 = candidate_poses(prob, R, t, yy)
+    X2 = X.copy()
+    c2, step, norm, behind, pairs = 0.0, (x * x).sum(), sum(3.0 + (t[v] * t[v]).sum() for v in range(prob.N)), False, []
+    for (a, b), (s, e), o in zip(prob.pairs, prob.offsets, terms):
+        d = steps(o, x[6 * a:6 * a + 6], x[6 * b:6 * b + 6])
+        X2[s:e] = X[s:e] + d
+        za, ra = observe(R2[a], t2[a], prob.k[a], X2[s:e], prob.ua[s:e], terms=False)
+        zb, rb = observe(R2[b], t2[b], prob.k[b], X2[s:e], prob.ub[s:e], terms=False)
+        cc = (ra[:, 0] * ra[:, 0] + ra[:, 1] * ra[:, 1]) + (rb[:, 0] * rb[:, 0] + rb[:, 1] * rb[:, 1])
+        bad = (za <= 0) | (zb <= 0) | ~np.isfinite(cc)
+        behind = behind or bool(bad.any())
+        pairs.append((cc.sum(), (d * d).sum(), (X[s:e] * X[s:e]).sum(), int(bad.sum())))
+        c2 += pairs[-1][0]
+        step += pairs[-1][1]
+        norm += pairs[-1][2]
+    if behind:
+        c2 = np.inf
+    return dict(R2=R2, t2=t2, X2=X2, c2=c2, step=step, norm=norm, pairs=pairs)
+
+
+def better(c2, c):
+    """lm_better: a lower cost, or one within the rounding of the sums"""
+    return bool(c2 < c or c2 - c <= COST_RESOLUTION * c)
+
+
+def final_stage(prob, R, t, X):
+    """the undamped stage: (cost, points that did not factor, the pairs' costs, the smallest pivot of the kept reduced
+    matrix scaled to a unit diagonal, its factor or None)"""
+    terms = prob.terms(R, t, X, 0.0)
+    S, g, dU, cost, bad, pair_cost = prob.system(terms)
+    A, _, _ = prob.reduced(S, g, dU, 0.0, R, t)
+    with np.errstate(all="ignore"):
+        s = 1.0 / np.sqrt(np.diag(A))
+        L, pivot = _cholesky(A * s[:, None] * s[None, :])
+    return cost, bad, pair_cost, pivot, L
+
+
+def depths(prob, R, t, X):
+    out = []
+    for (a, b), (s0, e0) in zip(prob.pairs, prob.offsets):
+        out.append((observe(R[a], t[a], prob.k[a], X[s0:e0], prob.ua[s0:e0], terms=False)[0],
+                    observe(R[b], t[b], prob.k[b], X[s0:e0], prob.ub[s0:e0], terms=False)[0]))
+    return out
+
+
+def pair_errors(pair_cost, used_counts):
+    with np.errstate(all="ignore"):
+        return np.array([np.sqrt(c / (2.0 * n)) if n else np.nan for c, n in zip(pair_cost, used_counts)])
 
 
 def solve(K, T, pairs, uvs_a, uvs_b, counts, fixed_view=0, threshold=None):
@@ -303,79 +402,26 @@ def solve(K, T, pairs, uvs_a, uvs_b, counts, fixed_view=0, threshold=None):
         terms = prob.terms(R, t, X, lam)
         S, g, dU, c, bad, _ = prob.system(terms)
         cost0 = c if cost0 is None else cost0
-        better = small = False
-        y = None
-        if bad == 0:
-            A, gk, M = prob.reduced(S, g, dU, lam, R, t)
-            L, _ = _cholesky(A)
-            if L is not None:
-                y = _solve(L, -gk)
-                if not np.isfinite(y).all():
-                    y = None
-        if y is not None:
-            yy = np.zeros(6 * N)
-            yy[prob.keep] = y
-            x = M @ yy
-            R2, t2 = R.copy(), t.copy()
-            for v in range(N):
-                w = yy[6 * v:6 * v + 6]
-                R2[v] = rotate_left(w[:3], R[v])
-                if v == anchor:
-                    c2v = -(R[v].T @ t[v]) + w[3:]
-                    t2[v] = -(R2[v] @ c2v)
-                else:
-                    t2[v] = t[v] + w[3:]
-            X2 = X.copy()
-            c2, step, norm, behind = 0.0, (x * x).sum(), sum(3.0 + (t[v] * t[v]).sum() for v in range(N)), False
-            for (a, b), (s, e), o in zip(prob.pairs, prob.offsets, terms):
-                da, db = x[6 * a:6 * a + 6], x[6 * b:6 * b + 6]
-                sa, sb = np.zeros((e - s, 3)), np.zeros((e - s, 3))
-                for p in range(6):
-                    sa, sb = sa + o["Za"][:, :, p] * da[p], sb + o["Zb"][:, :, p] * db[p]
-                r = -(o["y"] + (sa + sb))
-                l10, l20, l21 = o["L"]
-                i0, i1, i2 = o["il"]
-                d2 = r[:, 2] * i2
-                d1 = (r[:, 1] - l21 * d2) * i1
-                d0 = (r[:, 0] - l10 * d1 - l20 * d2) * i0
-                d = np.stack([d0, d1, d2], 1)
-                X2[s:e] = X[s:e] + d
-                za, ra = observe(R2[a], t2[a], prob.k[a], X2[s:e], prob.ua[s:e], terms=False)
-                zb, rb = observe(R2[b], t2[b], prob.k[b], X2[s:e], prob.ub[s:e], terms=False)
-                cc = (ra[:, 0] * ra[:, 0] + ra[:, 1] * ra[:, 1]) + (rb[:, 0] * rb[:, 0] + rb[:, 1] * rb[:, 1])
-                behind = behind or bool(((za <= 0) | (zb <= 0) | ~np.isfinite(cc)).any())
-                c2 += cc.sum()
-                step += (d * d).sum()
-                norm += (X[s:e] * X[s:e]).sum()
-            if behind:
-                c2 = np.inf
-            small = np.sqrt(step) < EPS * (np.sqrt(norm) + EPS)
-            better = bool(c2 < c or c2 - c <= COST_RESOLUTION * c)
-            if better:
-                R, t, X, its = R2, t2, X2, its + 1
-        lam = lam * 0.1 if better else lam * 10.0
+        taken = small = False
+        step = shared_step(prob, S, g, dU, lam, R, t) if bad == 0 else None
+        if step is not None:
+            cand = candidate(prob, R, t, X, terms, *step)
+            small = np.sqrt(cand["step"]) < EPS * (np.sqrt(cand["norm"]) + EPS)
+            taken = better(cand["c2"], c)
+            if taken:
+                R, t, X, its = cand["R2"], cand["t2"], cand["X2"], its + 1
+        lam = lam * 0.1 if taken else lam * 10.0
         stopped = bool(small or lam < 1e-12 or lam > 1e12)
-    terms = prob.terms(R, t, X, 0.0)
-    S, g, dU, cost, bad, pair_cost = prob.system(terms)
-    A, _, _ = prob.reduced(S, g, dU, 0.0, R, t)
-    with np.errstate(all="ignore"):
-        s = 1.0 / np.sqrt(np.diag(A))
-        L, pivot = _cholesky(A * s[:, None] * s[None, :])
+    cost, bad, pair_cost, pivot, L = final_stage(prob, R, t, X)
     good = L is not None and bad == 0 and pivot >= SINGULAR_PIVOT and np.isfinite(cost) and stopped
     points = np.full((len(status), 3), np.nan)
     points[used] = X
     Tout = T_from_poses(R, t)
     Tout[fixed_view] = T[fixed_view]
     n_used = int(used.sum())
-    with np.errstate(all="ignore"):
-        pair_error = np.array([np.sqrt(c / (2.0 * n)) if n else np.nan for c, n in zip(pair_cost, used_counts)])
-    depths = []
-    for (a, b), (s0, e0) in zip(prob.pairs, prob.offsets):
-        depths.append((observe(R[a], t[a], prob.k[a], X[s0:e0], prob.ua[s0:e0], terms=False)[0],
-                       observe(R[b], t[b], prob.k[b], X[s0:e0], prob.ub[s0:e0], terms=False)[0]))
     return dict(T=Tout, points=points, status=status, retval=float(np.sqrt(cost / (2.0 * n_used))), cost0=float(cost0), cost=float(cost),
-                pair_error=pair_error, iterations=its, evaluations=evals, anchor=(anchor, axis), start=X0,
-                rig_status=0 if good else 3, min_pivot=pivot, depths=depths, used_counts=used_counts)
+                pair_error=pair_errors(pair_cost, used_counts), iterations=its, evaluations=evals, anchor=(anchor, axis), start=X0,
+                rig_status=0 if good else 3, min_pivot=pivot, depths=depths(prob, R, t, X), used_counts=used_counts)
 
 
 def _aligned(T, T_true):
