@@ -27,6 +27,7 @@ from .boards import ArucoGridBoard, BaseBoard, CharucoBoard, Chessboard, MarkerB
 from .multi_boards import MultiBoardsCam
 from .reconstruction_with_board import convert_cam_to_nerf_json, get_sharpness
 from .features import BinaryFeatureMatching, detect_and_describe, match_descriptors, match_images, match_views
+from .lidar import calibrate_lidar2cam, uvs_on_depth_to_xyzs, xyzs_to_dense_depth
 
 __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "StereoSGBM",
            "StereoSGBM_create", "MODE_SGBM", "MODE_HH", "MODE_SGBM_3WAY", "MODE_HH4", "__version__",
@@ -38,4 +39,5 @@ __all__ = ["Cam", "Stereo", "MetaStereoMatching", "SemiGlobalBlockMatching", "St
            "CALIB_ZERO_TANGENT_DIST", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
            "stereo_calibrate", "CALIB_FIX_INTRINSIC", "CALIB_USE_EXTRINSIC_GUESS", "BaseBoard", "Chessboard", "CharucoBoard", "MarkerBoard", "ArucoGridBoard",
            "MatchingByBoard", "MultiBoards", "MultiBoardsCam", "convert_cam_to_nerf_json", "get_sharpness", "find_essential_matrix", "find_essential_matrices",
-           "BinaryFeatureMatching", "detect_and_describe", "match_descriptors", "match_images", "match_views", "bundle_adjust_pairs"]
+           "BinaryFeatureMatching", "detect_and_describe", "match_descriptors", "match_images", "match_views", "bundle_adjust_pairs",
+           "xyzs_to_dense_depth", "uvs_on_depth_to_xyzs", "calibrate_lidar2cam"]

@@ -262,6 +262,13 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_hull_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "camd_hull_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_cloud_workspace_bytes": (c_size_t, [c_size_t]),
+    "camd_cloud_to_uvzs": (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_void_p,
+                                   c_size_t, c_void_p, c_void_p, c_void_p]),
+    "camd_hull_row_range": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
+    "camd_hull_extremes": (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_nearest_fill_in_hull": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_double, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p]),
     "camd_essential_hypotheses": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, ctypes.c_ulonglong,
                                           c_int, c_void_p, c_void_p, c_void_p]),
     "camd_essential_score": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,

@@ -14,15 +14,11 @@
 // by the centred moments.  A frame's record depends on nothing but its own rows: alone or anywhere in a batch, the
 // same bits.  Stage B (k_hull_fill): one wavefront per image row, the row's closed span from the hull's edges, every
 // pixel written exactly once, 16 bytes per lane where the row's address allows.
-#include <climits>
-
+#include "hull_common.hpp"
 #include "pnp_common.hpp"
 
 namespace camd {
 
-enum { HULL_NO_SAMPLE = 1, HULL_DEGENERATE = 2, HULL_OUT_OF_RANGE = 4 };
-constexpr int HULL_MAX_POINTS = CAMD_HULL_MAX_POINTS;
-constexpr double HULL_MAX_COORD = 1048576.;    // 2^20: differences fit 22 bits, their products 43: all int64
 constexpr double HULL_COLLINEAR_TOL = 1e-9;    // sparse.COLLINEAR_TOL
 constexpr int HULL_DROPPED = INT_MIN;          // px of a row that takes no part
 
@@ -187,46 +183,7 @@ __global__ __launch_bounds__(64) void k_hull_fit(HullFitArgs a)
 }
 
 // ---- stage B ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long floor_div(long long a, long long b)  // b > 0
-{
-    const long long q = a / b;
-    return q * b > a ? q - 1 : q;
-}
-__device__ __forceinline__ long long ceil_div(long long a, long long b)  // b > 0
-{
-    const long long q = a / b;
-    return q * b < a ? q + 1 : q;
-}
-
-// The closed span [xl, xr] of row y inside the hull, clipped to [0, w - 1]; xl > xr: the row is empty.  The line y = const
-// meets a convex polygon in one segment: its ends are the lowest and the highest crossing with an edge that reaches the
-// row, so xl = min over those edges of ceil(crossing), xr = max of floor(crossing).  An edge along the row gives both its
-// ends.  One vertex is the edge from itself to itself.  The same in every lane.
-__device__ __forceinline__ void hull_span(const int* __restrict__ verts, int count, int y, int w, int lane, int* xl, int* xr)
-{
-    long long lo = LLONG_MAX, hi = LLONG_MIN;
-    for (int k = lane; k < count; k += 64) {
-        const int k2 = k + 1 < count ? k + 1 : 0;
-        const long long ax = verts[k * 2], ay = verts[k * 2 + 1], bx = verts[k2 * 2], by = verts[k2 * 2 + 1];
-        if ((y < ay && y < by) || (y > ay && y > by)) continue;
-        if (ay == by) {
-            lo = min(lo, min(ax, bx)), hi = max(hi, max(ax, bx));
-            continue;
-        }
-        long long den = by - ay, num = ax * den + ((long long)y - ay) * (bx - ax);  // crossing = num / den
-        if (den < 0) den = -den, num = -num;
-        lo = min(lo, ceil_div(num, den)), hi = max(hi, floor_div(num, den));
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        lo = min(lo, (long long)__shfl_xor(lo, m, 64));
-        hi = max(hi, (long long)__shfl_xor(hi, m, 64));
-    }
-    lo = max(lo, 0ll), hi = min(hi, (long long)w - 1);
-    if (lo > hi) lo = 1, hi = 0;
-    *xl = (int)lo, *xr = (int)hi;
-}
-
+// (the closed span of a row inside the hull, hull_span, lives in hull_common.hpp: lidar.hip fills by it too)
 struct HullPlane {  // the value: exactly k_sp_plane_eval's expression (sparse.hip); 1 / that with `reciprocal`
     double a, b, c;
     int reciprocal, zero;  // zero: the whole frame is 0, whatever `reciprocal` says

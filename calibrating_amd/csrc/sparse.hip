@@ -11,13 +11,12 @@
 // reduced in a fixed order without float atomics.
 #include "common.hpp"
 #include "compact.hpp"
+#include "nearest.hpp"
 #include "triangulate.hpp"
 
 #include <cmath>
 
 namespace camd {
-
-constexpr int SP_MAX_RADIUS = CAMD_NEAREST_MAX_RADIUS;
 
 // ---- a. scatter ------------------------------------------------------------------------------------------------------
 // xs, ys = np.int32(uvs.round()) (half to even); rows outside the image -- NaN and inf among them -- are dropped (:312-313)
@@ -67,14 +66,7 @@ struct MaskRows : MaskOn {
 };
 
 // ---- c. nearest fill -------------------------------------------------------------------------------------------------
-// A sample (u, v) lies in the integer cell (floor(u), floor(v)).  A pixel x can only be nearer than `distance` <= R to
-// samples with x - R < u < x + R, i.e. cells x - R .. x + R - 1 (the float64 difference x - u is monotonic in u and R is
-// representable, so rounding cannot move a sample across that bound).  Cells -R .. w + R - 2 therefore serve every pixel
-// of a w-wide grid: bins_w = w + 2R - 1, bins_h = h + 2R - 1; samples in no such cell cannot be anybody's answer.
-struct SpBins {
-    int w, h, R, bw, bh;
-};
-
+// (the bins, SpBins, and the search of one pixel through them, sp_nearest_value, live in nearest.hpp: lidar.hip searches too)
 __device__ __forceinline__ bool sp_cell(const double* __restrict__ uv, size_t i, int stride, const SpBins& b, uint32_t* cell)
 {
     const double fu = floor(uv[i * stride]), fv = floor(uv[i * stride + 1]);
@@ -116,9 +108,7 @@ struct SpOut {
     float mul, div;    // stereo_matching.py:139: disparity * hw[1] / resize_shape[1], two float32 roundings
 };
 
-// One thread per output pixel, a wave = 64 consecutive pixels of a row: neighbouring lanes walk the same cells.  The
-// 2R cells of one bin row that a pixel needs are adjacent, so each bin row is one contiguous run of sorted samples.
-// Both loops are bounded by input sizes (2R rows, the samples binned into them).
+// One thread per output pixel, a wave = 64 consecutive pixels of a row: neighbouring lanes walk the same cells.
 template <typename Z>
 __global__ __launch_bounds__(256) void k_sp_nearest(const double* __restrict__ sorted_uv, const uint32_t* __restrict__ sorted_idx,
                                                     const uint32_t* __restrict__ start, const Z* __restrict__ z, SpBins b,
@@ -131,21 +121,7 @@ __global__ __launch_bounds__(256) void k_sp_nearest(const double* __restrict__ s
         x = min((int)floor(X * o.ifx), b.w - 1);
         y = min((int)floor(Y * o.ify), b.h - 1);
     }
-    const double px = (double)x, py = (double)y;
-    double best = INFINITY;
-    uint32_t best_i = 0xffffffffu;
-    for (int r = 0; r < 2 * b.R; r++) {
-        const size_t row = (size_t)(y + r) * b.bw;  // bin row of cell y - R + r
-        const uint32_t s = start[row + x], e = start[row + x + 2 * b.R];
-        for (uint32_t k = s; k < e; k++) {
-            const double dx = px - sorted_uv[(size_t)k * 2], dy = py - sorted_uv[(size_t)k * 2 + 1];
-            const double d = __dsqrt_rn(dx * dx + dy * dy);
-            const uint32_t i = sorted_idx[k];
-            if (d < best || (d == best && i < best_i)) { best = d; best_i = i; }
-        }
-    }
-    float v = 0.0f;
-    if (best < distance) v = (float)z[best_i];
+    float v = sp_nearest_value(sorted_uv, sorted_idx, start, z, 1, b, distance, x, y);
     if (o.scaled) v = __fdiv_rn(__fmul_rn(v, o.mul), o.div);
     out[(size_t)Y * o.ow + X] = v;
 }
@@ -199,23 +175,6 @@ __global__ __launch_bounds__(256) void k_sp_triangulate(const double* __restrict
     double x1[3], b[3];
     tri_rays(m.k1, m.k2, u1, v1, u2, v2, x1, b);
     tri_solve(x1, b, m.R, m.t, zs1 + i, zs2 + i);
-}
-
-static int make_bins(SpBins* b, int w, int h, double distance, const char* who)
-{
-    if (w <= 0 || h <= 0) { set_error("%s: bad grid size %d x %d", who, w, h); return CAMD_ERR_BAD_ARG; }
-    if (!(distance == distance) || distance > (double)SP_MAX_RADIUS) {
-        set_error("%s: distance %g needs a search window beyond the supported %d cells each way (distance <= %d)", who,
-                  distance, SP_MAX_RADIUS, SP_MAX_RADIUS);
-        return CAMD_ERR_UNSUPPORTED;
-    }
-    int R = distance > 1.0 ? (int)ceil(distance) : 1;  // (distance <= 0: nothing is ever nearer, the window may be minimal)
-    b->w = w; b->h = h; b->R = R; b->bw = w + 2 * R - 1; b->bh = h + 2 * R - 1;
-    if ((unsigned long long)b->bw * (unsigned long long)b->bh >= 0x7fffffffull || h > 65535) {
-        set_error("%s: a %d x %d grid is beyond the 32-bit cell index / 65535 rows", who, w, h);
-        return CAMD_ERR_UNSUPPORTED;
-    }
-    return CAMD_OK;
 }
 
 }  // namespace camd

@@ -347,9 +347,157 @@ def convex_hull_mask(uvs, hw, counts=None):
     return to_caller(out if batched else out[0], was_np)
 
 
+# ---- d''. the hull of any number of samples; the nearest sample inside it (csrc/lidar.hip) -----------------------------
+def _cloud_hull_record(uv, uv_stride, n, rows_range=None, what="cloud_hull"):
+    """The hull record (vertices (1, capacity, 2), hull_counts (1,), capacity, status (1,)) of ``n`` (u, v) rows on the device,
+    ``uv_stride`` doubles apart, however many: the per-row extremes of their pixels (``camd_hull_extremes``) are the candidates,
+    ``camd_hull_fit`` takes them in chunks of ``MAX_HULL_POINTS`` and the surviving vertices go round again until one frame
+    holds them.  ``rows_range`` = (y0, rows) when the caller knows the pixel rows the samples can reach; else one device
+    min / max of the rounded v and one read-back."""
+    import torch
+    dev = uv.device
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if rows_range is None:
+        rng = torch.empty(3, dtype=torch.int32, device=dev)
+        call("camd_hull_row_range", dev, uv.data_ptr(), uv_stride, n, rng.data_ptr(), what=what)
+        lo, hi = (int(x) for x in rng[:2].cpu().numpy())  # (the status bits come with the extremes)
+        rows_range = (lo, hi - lo + 1) if lo <= hi else (0, 1)
+    y0, rows = rows_range
+    table = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+    cand = torch.empty((2 * rows, 2), dtype=torch.float64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    call("camd_hull_extremes", dev, uv.data_ptr(), uv_stride, n, y0, rows, table.data_ptr(), cand.data_ptr(), count.data_ptr(),
+         status.data_ptr(), what=what)
+    m = int(count.item())
+    cand = cand[:m]
+    while True:
+        frames = max(1, -(-m // MAX_HULL_POINTS))
+        capacity = max(1, min(m, MAX_HULL_POINTS))
+        start = torch.from_numpy(np.minimum(np.arange(frames + 1, dtype=np.int64) * MAX_HULL_POINTS, m)).to(dev)
+        verts = torch.empty((frames, capacity, 2), dtype=torch.int32, device=dev)
+        hull_counts = torch.empty(frames, dtype=torch.int32, device=dev)
+        abc = torch.empty((frames, 3), dtype=torch.float64, device=dev)
+        fit_status = torch.empty(frames, dtype=torch.int32, device=dev)
+        call("camd_hull_fit", dev, cand.data_ptr(), 2, None, VALUE_TYPES["float64"], m, start.data_ptr(), frames, 1, 1, 0, capacity,
+             verts.data_ptr(), hull_counts.data_ptr(), abc.data_ptr(), fit_status.data_ptr(), what=what)
+        if frames == 1:
+            status |= fit_status & STATUS_NO_SAMPLE
+            return dict(vertices=verts, hull_counts=hull_counts, capacity=capacity, status=status, table=table, rows_range=rows_range)
+        keep = torch.arange(capacity, device=dev)[None, :] < hull_counts[:, None]
+        cand = verts[keep].to(torch.float64)  # the frames' vertices in frame order (synchronises: the length is data dependent)
+        if int(cand.shape[0]) >= m:
+            raise ValueError("%s: a round over %d candidates left %d; the hull has more than MAX_HULL_POINTS = %d vertices"
+                             % (what, m, int(cand.shape[0]), MAX_HULL_POINTS))
+        m = int(cand.shape[0])
+
+
+def _one_frame_uv(uvs, what):
+    check_array(uvs, what)
+    if len(uvs.shape) != 2 or uvs.shape[1] != 2:
+        raise ValueError("%s must be one frame (n, 2), got %s" % (what, tuple(uvs.shape)))
+    if int(uvs.shape[0]) >= 2 ** 31:
+        raise ValueError("%d rows do not fit the 32-bit row index" % uvs.shape[0])
+    return int(uvs.shape[0])
+
+
+def cloud_hull(uvs):
+    """(k, 2) int32: the vertices of the convex hull of ``int32(round(u, v))`` (half to even) of ONE frame of any number of
+    rows, in ``camd_hull_fit``'s order (from the lowest (x, y), each next vertex the one that leaves every other point on one
+    side).  The validity rule and the contract are ``convex_hull_mask``'s."""
+    n = _one_frame_uv(uvs, "uvs")
+    uv = to_device(uvs, dtype="float64", cast=True)
+    rec = _cloud_hull_record(uv, 2, n)
+    k = int(rec["hull_counts"].item())
+    return to_caller(rec["vertices"][0, :k].contiguous(), is_np(uvs))
+
+
+def cloud_hull_mask(uvs, hw):
+    """``convex_hull_mask`` of ONE frame (n, 2) of any number of rows: uint8 (h, w).  For a frame of at most
+    ``MAX_HULL_POINTS`` rows the two are the same bits."""
+    import torch
+    n = _one_frame_uv(uvs, "uvs")
+    h, w = positive_hw(hw)
+    uv = to_device(uvs, dtype="float64", cast=True)
+    rec = _cloud_hull_record(uv, 2, n, what="cloud_hull_mask")
+    out = torch.empty((1, h, w), dtype=torch.uint8, device=uv.device)
+    call("camd_hull_mask", out.device, rec["vertices"].data_ptr(), rec["hull_counts"].data_ptr(), rec["capacity"], 1, w, h,
+         out.data_ptr(), what="cloud_hull_mask")
+    return to_caller(out[0], is_np(uvs))
+
+
+def _check_nearest_distance(distance):
+    distance = float(distance)
+    if distance != distance or distance > MAX_DISTANCE:
+        raise ValueError("distance %r: the search window would exceed the %d cells each way the kernel supports "
+                         "(distance <= %d)" % (distance, MAX_DISTANCE, MAX_DISTANCE))
+    return distance
+
+
+def _nearest_in_hull(rows, n, hw, distance, zname, rows_range=None, z=None, what="interpolate_uvzs_in_hull"):
+    """(float32 (h, w) tensor, hull record): ``rows`` is (n, 3) float64 (u, v, z) on the device -- or (n, 2) with ``z`` a
+    contiguous tensor of ``zname`` -- read in place; bins as ``interpolate_uvzs("nearest")`` makes them."""
+    import torch
+    h, w = hw
+    dev, stride = rows.device, int(rows.shape[1])
+    lib = _native.lib()
+    R, bw, bh = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _native.check(lib.camd_sparse_bin_grid(w, h, distance, ctypes.byref(R), ctypes.byref(bw), ctypes.byref(bh)), what)
+    rec = _cloud_hull_record(rows, stride, n, rows_range, what)
+    ncell = bw.value * bh.value
+    counts = torch.empty(ncell, dtype=torch.int32, device=dev)
+    call("camd_sparse_bin_count", dev, rows.data_ptr(), n, stride, w, h, distance, counts.data_ptr(), what=what)
+    start = torch.zeros(ncell + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int32, out=start[1:])
+    cursor = start[:-1].clone()
+    suv = torch.empty((max(n, 1), 2), dtype=torch.float64, device=dev)
+    sidx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    call("camd_sparse_bin_fill", dev, rows.data_ptr(), n, stride, w, h, distance, cursor.data_ptr(), n, suv.data_ptr(),
+         sidx.data_ptr(), what=what)
+    zptr, zstride = (rows.data_ptr() + 16, stride) if z is None else (z.data_ptr(), 1)
+    out = torch.empty((h, w), dtype=torch.float32, device=dev)
+    call("camd_nearest_fill_in_hull", dev, suv.data_ptr(), sidx.data_ptr(), start.data_ptr(), zptr, VALUE_TYPES[zname], zstride, w, h,
+         distance, rec["vertices"].data_ptr(), rec["hull_counts"].data_ptr(), rec["capacity"], out.data_ptr(), what=what)
+    return out, rec
+
+
+def _interpolate_nearest_in_hull(uvzs, hw, counts, reciprocal, keep_last_per_pixel, return_info, zero_frames, distance):
+    check_array(uvzs, "uvzs")
+    if counts is not None or len(uvzs.shape) != 2 or uvzs.shape[1] != 3:
+        raise ValueError('inter_type="nearest" takes one frame (n, 3) without counts, got %s%s'
+                         % (tuple(uvzs.shape), "" if counts is None else " with counts"))
+    if reciprocal or keep_last_per_pixel or zero_frames is not None:
+        raise ValueError('reciprocal, keep_last_per_pixel and zero_frames go with inter_type="lstsq"')
+    n = int(uvzs.shape[0])
+    if n >= 2 ** 31:
+        raise ValueError("%d samples do not fit the 32-bit sample index" % n)
+    distance = _check_nearest_distance(distance)
+    h, w = positive_hw(hw)
+    if h > 65535:
+        raise ValueError("grids of more than 65535 rows are not supported")
+    was_np = is_np(uvzs)
+    _require_finite(uvzs[:, :2], "interpolate_uvzs_in_hull")
+    zname = "float32" if dtype_name(uvzs) == "float32" else "float64"
+    uv = to_device(uvzs[:, :2], dtype="float64", cast=True)
+    z = to_device(uvzs[:, 2], dtype=zname, cast=True, device=uv.device)
+    out, rec = _nearest_in_hull(uv, n, (h, w), distance, zname, z=z)
+    out = to_caller(out, was_np)
+    if not return_info:
+        return out
+    status, hull_counts = to_caller((rec["status"], rec["hull_counts"]), was_np)
+    return out, dict(status=status[0], hull_counts=hull_counts[0])
+
+
 def interpolate_uvzs_in_hull(uvzs, hw, counts=None, reciprocal=False, keep_last_per_pixel=False, return_info=False,
-                             zero_frames=None):
-    """The least-squares plane z = a u + b v + c of sparse (u, v, z) rows, written only inside their convex hull and 0
+                             zero_frames=None, inter_type="lstsq", distance=2):
+    """``inter_type="nearest"`` (with ``distance``): ONE frame (n, 3) of any n < 2**31 -> float32 (h, w) that is
+    ``interpolate_uvzs(uvzs, hw, None, "nearest", distance)`` where ``cloud_hull_mask(uvzs[:, :2], hw)`` is 1 and 0 elsewhere,
+    without forming either (pixels outside the hull are not searched): what the reference's
+    ``interpolate_uvzs(constrained_type="convex_hull", inter_type="nearest")`` is for, a LiDAR sweep as a depth image.  Every
+    row with finite u, v takes part, whatever its z; non-finite u, v are refused; ``return_info`` adds ``dict(status,
+    hull_counts)`` with the bits 1 and 4 below.  A batch, ``counts``, ``reciprocal``, ``keep_last_per_pixel`` and
+    ``zero_frames`` are refused.  The default, ``"lstsq"``, is:
+
+    The least-squares plane z = a u + b v + c of sparse (u, v, z) rows, written only inside their convex hull and 0
     outside: float32 (h, w) for (n, 3) rows, (f, h, w) for a batch (f, n, 3) or ragged rows (N, 3) with ``counts`` (the
     convention of ``pnp.solve_pnp_batch``).  What the reference's ``interpolate_uvzs(..., constrained_type=True)`` is for
     (utils.py:356-415), with the mask of ``convex_hull_mask`` in place of cv2's.  NumPy in -> NumPy out, CUDA in -> CUDA out.
@@ -366,6 +514,10 @@ def interpolate_uvzs_in_hull(uvzs, hw, counts=None, reciprocal=False, keep_last_
     ``interpolate_uvzs`` does for such samples.  ``zero_frames`` (f,) bool, of a batch: the frames written as zeros
     throughout, whatever ``reciprocal`` says -- the frames of a recording that show no board."""
     import torch
+    if inter_type == "nearest":
+        return _interpolate_nearest_in_hull(uvzs, hw, counts, reciprocal, keep_last_per_pixel, return_info, zero_frames, distance)
+    if inter_type != "lstsq":
+        raise ValueError('inter_type must be "lstsq" or "nearest", got %r' % (inter_type,))
     flat, lengths, batched = _hull_layout(uvzs, 3, counts, "uvzs")
     h, w = positive_hw(hw)
     was_np = is_np(uvzs)

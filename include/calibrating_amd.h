@@ -1003,6 +1003,48 @@ int camd_hull_fill(const int* vertices, const int* hull_counts, const double* ab
 int camd_hull_mask(const int* vertices, const int* hull_counts, int vertex_capacity, int frames, int w, int h, uint8_t* out,
                    void* queue);
 
+/* ---- a LiDAR cloud as a dense depth image: projection, the hull of any number of samples, the nearest sample inside it
+ *      (csrc/lidar.hip) ----
+ * The device side of xyzs_to_dense_depth in the reference's example/calibrate_lidar2cam_by_PnP/calibrate_lidar2cam_pnp.py:13-42.
+ *
+ * a. The cloud's rows inside the image.  xyz: n points (n < 2^31) of xyz_type CAMD_VALUE_F64 / _F32, xyz_stride >= 3 elements
+ * apart (a column view of a wider array is read in place).  T: NULL or 16 host doubles (4 x 4, row-major); K: 9 host doubles,
+ * all of them used; lens distortion takes no part.  Per point, in float64, every product and sum rounded on its own:
+ *   X' = ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3]      (r = 0, 1, 2; without T: X' = X)
+ *   p[r] = (K[r][0] X' + K[r][1] Y') + K[r][2] Z',   u = p0 / p2,   v = p1 / p2
+ * and the point is KEPT iff p2 > 0, u >= 0, v >= 0, u < w and v < h (a NaN or an infinity fails a comparison).  stages is
+ * 1 (count), 2 (emit) or 3 (both):
+ *   count  counters[0] = the kept points, counters[1] = the points with p2 > 0 (uint64, on the device), and the workspace
+ *          (camd_cloud_workspace_bytes(n) bytes, 8-aligned) is left ready for an emit of the same arguments;
+ *   emit   rows[k] = (u * rate, v * rate, Z') float64 of the k-th kept point, in input order (the compaction of compact.hpp
+ *          over rows of a fixed number of points); slots at or beyond `capacity` are not written.
+ * Between the two a caller may read counters[1] back and choose `rate` from it.                                          */
+size_t camd_cloud_workspace_bytes(size_t n);
+int camd_cloud_to_uvzs(const void* xyz, int xyz_type, size_t n, int xyz_stride, const double* T, const double K[9], int w, int h,
+                       double rate, int stages, double* rows, size_t capacity, unsigned long long* counters, void* workspace,
+                       void* queue);
+/* b. The convex hull of ANY number of samples, under camd_hull_fit's mask contract.  A sample (u, v) has the pixel
+ * (int32(rint(u)), int32(rint(v))), half to even, when u, v are finite and |rint| <= 2^20; beyond that it is left out and
+ * status bit 4 is set.  A point set and its per-row extremes have the same hull:
+ *   camd_hull_row_range  range[0], range[1] = the lowest and the highest pixel row of the samples (INT_MAX, INT_MIN when
+ *                        none has a pixel), range[2] = the status bits; 3 int32 on the device.
+ *   camd_hull_extremes   table: rows x 2 int32, (xmin, xmax) of the samples on pixel row y0 + r, (INT_MAX, INT_MIN) where
+ *                        there is none -- integer atomicMin / atomicMax, the same bits on every run; samples on other rows take
+ *                        no part.  candidates: the non-empty rows' (xmin, y), (xmax, y) as float64 rows of 2, in rising y,
+ *                        min before max (room for 2 * rows of them); *count = their number; *status as above.
+ * The candidates go to camd_hull_fit with z = NULL: at most CAMD_HULL_MAX_POINTS of them as one frame, more as consecutive
+ * chunks of that many (the frames of one call with `start`), whose surviving vertices, concatenated in frame order, are the
+ * candidates of the next round.  uv: n float64 rows, uv_stride >= 2 doubles apart; 1 <= rows <= 2^21 + 1, |y0| <= 2^20.  */
+int camd_hull_row_range(const double* uv, int uv_stride, size_t n, int* range, void* queue);
+int camd_hull_extremes(const double* uv, int uv_stride, size_t n, int y0, int rows, int* table, double* candidates,
+                       unsigned long long* count, int* status, void* queue);
+/* c. camd_nearest_fill restricted to ONE hull record (vertices, hull_counts[0], vertex_capacity as camd_hull_fit leaves them):
+ * out[y][x] (h x w float32) = what camd_nearest_fill gives for the same bins where the pixel lies in the row's closed span
+ * (camd_hull_fill's), 0 elsewhere -- without a search there.  z: the samples' values, z_stride elements apart.            */
+int camd_nearest_fill_in_hull(const double* sorted_uv, const uint32_t* sorted_idx, const uint32_t* start, const void* z, int z_type,
+                              size_t z_stride, int w, int h, double distance, const int* vertices, const int* hull_counts,
+                              int vertex_capacity, float* out, void* queue);
+
 /* ---- the essential matrix of matched pixels by RANSAC over 8-point samples (csrc/essential.hip) ----
  * The device side of epipolar_geometry.find_essential_matrix.  A contract of this library's OWN: cv2.findEssentialMat is
  * not restated (UNPINNED); tests/essential_ref.py restates every stage in NumPy, bit for bit.
