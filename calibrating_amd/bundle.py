@@ -12,11 +12,10 @@ import ctypes
 
 import numpy as np
 
-from . import _native
+from . import _lm, _native
 from ._arrays import FLOAT_TYPES, check_array, dtype_name, is_np, to_caller, to_device
+from ._lm import STATUS_OK, STATUS_SINGULAR, STATUS_TEXT  # noqa: F401
 
-STATUS_OK, STATUS_SINGULAR = 0, 3
-STATUS_TEXT = {0: "ok", 3: "singular or not converged at the cap"}
 MATCH_STATUS_TEXT = {0: "ok", 1: "a non-finite coordinate", 2: "no start point: the rays are nearly parallel or meet behind a view",
                      3: "the start's reprojection error exceeds the threshold"}
 MIN_VIEWS, MAX_VIEWS = 3, _native.BUNDLE_MAX_VIEWS
@@ -95,12 +94,6 @@ def check_arguments(K, T, pairs, uvs_a, uvs_b, counts, fixed_view=0, threshold=N
     if not 1 <= M < 2 ** 31:
         raise ValueError("1 <= M < 2^31 matches are required, got %d" % M)
     return K, T, pairs.astype(np.int32), counts, was_np
-
-
-def _read(state, dev, count):
-    out = np.empty(count)
-    _native.call("camd_calib_read", dev, state.data_ptr(), count, out.ctypes.data, what="bundle_adjust_pairs")
-    return out
 
 
 def _segments(counts):
@@ -224,16 +217,10 @@ def bundle_adjust_pairs(K, T, pairs, uvs_a, uvs_b, counts, fixed_view=0, thresho
     b.eval_partials, b.eval_blocks, b.pair_error = eval_partials.data_ptr(), eval_blocks.data_ptr(), pair_error.data_ptr()
     b.used, b.chunks = U, chunks
     _native.call("camd_bundle_emit", dev, ctypes.byref(b), what=what)
-    while True:
-        _native.call("camd_bundle_step", dev, ctypes.byref(b), what=what)
-        done, _accept = _read(state, dev, 2)  # the only read-back of an evaluation: 16 bytes
-        if done:
-            break
+    _lm.iterate(state, dev, what, lambda: _native.call("camd_bundle_step", dev, ctypes.byref(b), what=what))
     _native.call("camd_bundle_finish", dev, ctypes.byref(b), what=what)
     s = state.cpu().numpy()
-    if int(s[_native.BUNDLE_STATUS]) != STATUS_OK:
-        raise ValueError("%s: status %d (%s) after %d evaluations, smallest pivot %.3g"
-                         % (what, s[_native.BUNDLE_STATUS], STATUS_TEXT[3], s[_native.BUNDLE_EVALUATIONS], s[_native.BUNDLE_PIVOT]))
+    _lm.check_status(what, s[_native.BUNDLE_STATUS], s[_native.BUNDLE_EVALUATIONS], s[_native.BUNDLE_PIVOT])
     final = s[_native.BUNDLE_POSES:_native.BUNDLE_POSES + 12 * N].reshape(N, 12)
     T_out = T_from_poses(final[:, :9].reshape(N, 3, 3), final[:, 9:])
     T_out[fixed_view] = T[fixed_view]

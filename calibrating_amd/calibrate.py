@@ -13,8 +13,9 @@ import ctypes
 
 import numpy as np
 
-from . import _native, pnp
+from . import _lm, _native, pnp
 from ._arrays import to_caller
+from ._lm import STATUS_OK, STATUS_SINGULAR, STATUS_TEXT  # noqa: F401
 
 # cv2's values
 CALIB_USE_INTRINSIC_GUESS = 0x00001
@@ -42,8 +43,6 @@ WITHOUT_EFFECT = CALIB_FIX_K4 | CALIB_FIX_K5 | CALIB_FIX_K6  # coefficients this
 UNDISTORTED_FLAGS = (CALIB_ZERO_TANGENT_DIST | CALIB_FIX_K1 | CALIB_FIX_K2 | CALIB_FIX_K3 | CALIB_FIX_K4 | CALIB_FIX_K5 |
                      CALIB_FIX_K6)
 
-STATUS_OK, STATUS_SINGULAR = 0, 3
-STATUS_TEXT = {0: "ok", 3: "singular or not converged at the cap"}
 FRAME_STATUS_TEXT = {0: "ok", 1: "too few points", 2: "non-finite input", 3: "no start pose"}
 
 
@@ -89,12 +88,6 @@ def initial_camera_matrix(H, xy):
     if not (np.isfinite(fx) and np.isfinite(fy)):
         raise ValueError("calibrate_camera: the homographies give no focal length (every frame sees the target head-on?)")
     return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]])
-
-
-def _read(state, dev, count):
-    out = np.empty(count)
-    _native.call("camd_calib_read", dev, state.data_ptr(), count, out.ctypes.data, what="calibrate_camera")
-    return out
 
 
 def calibrate_camera(object_points, image_points, xy, counts=None, flags=0, K=None, D=None):
@@ -166,13 +159,7 @@ def calibrate_camera(object_points, image_points, xy, counts=None, flags=0, K=No
     # start poses under the start intrinsics: the batched PnP as it is
     K0 = np.array([k0[0], 0, k0[2], 0, k0[1], k0[3], 0, 0, 1.0])
     D0 = np.ascontiguousarray(k0[4:])
-    pose0, poses = torch.empty((frames, 12), **f64), torch.empty((frames, 12), **f64)
-    rms, its = torch.empty(frames, **f64), torch.empty(frames, dtype=torch.int32, device=dev)
-    status = torch.empty(frames, dtype=torch.int32, device=dev)
-    _native.call("camd_pnp_init", dev, ctypes.byref(pts), K0.ctypes.data, D0.ctypes.data, 5, int(planar), plane.ctypes.data,
-                 pose0.data_ptr(), what=what)
-    _native.call("camd_pnp_refine", dev, ctypes.byref(pts), K0.ctypes.data, D0.ctypes.data, 5, min_points, pose0.data_ptr(), 12,
-                 poses.data_ptr(), rms.data_ptr(), its.data_ptr(), status.data_ptr(), what=what)
+    poses, status = pnp.start_poses(pts, K0, D0.ctypes.data, 5, planar, plane, min_points, dev, what)
     used_host = np.flatnonzero(status.cpu().numpy() == 0).astype(np.int32)
     n_used, n_points = len(used_host), int(lengths[used_host].sum())
     if n_used == 0:
@@ -190,20 +177,12 @@ def calibrate_camera(object_points, image_points, xy, counts=None, flags=0, K=No
     ws = torch.empty((n_used, _native.CALIB_WORKSPACE_DOUBLES), **f64)
     err = torch.empty(n_used, **f64)
     common = (ctypes.byref(pts), used.data_ptr(), n_used, state.data_ptr())
-    linearise = lambda: _native.call("camd_calib_linearise", dev, *common, cur.data_ptr(), ws.data_ptr(), what=what)  # noqa: E731
-    linearise()
-    while True:
-        _native.call("camd_calib_step", dev, *common, cur.data_ptr(), cand.data_ptr(), ws.data_ptr(), what=what)
-        done, accept = _read(state, dev, 2)  # the only read-back of an evaluation: 16 bytes
-        if accept:
-            linearise()
-        if done:
-            break
+    _lm.iterate(state, dev, what,
+                lambda: _native.call("camd_calib_step", dev, *common, cur.data_ptr(), cand.data_ptr(), ws.data_ptr(), what=what),
+                lambda: _native.call("camd_calib_linearise", dev, *common, cur.data_ptr(), ws.data_ptr(), what=what))
     _native.call("camd_calib_finish", dev, *common, ws.data_ptr(), err.data_ptr(), what=what)
-    s = _read(state, dev, _native.CALIB_STATE_DOUBLES)
-    if int(s[_native.CALIB_STATUS]) != STATUS_OK:
-        raise ValueError("calibrate_camera: status %d (%s) after %d evaluations, smallest pivot %.3g"
-                         % (s[_native.CALIB_STATUS], STATUS_TEXT[3], s[_native.CALIB_EVALUATIONS], s[_native.CALIB_PIVOT]))
+    s = _lm.read_state(state, dev, _native.CALIB_STATE_DOUBLES, what)
+    _lm.check_status(what, s[_native.CALIB_STATUS], s[_native.CALIB_EVALUATIONS], s[_native.CALIB_PIVOT])
     k = s[_native.CALIB_K:_native.CALIB_K + 9]
     T = pnp.poses_to_T(cur, fill=(frames, used.long()))
     error = torch.full((frames,), float("nan"), **f64)

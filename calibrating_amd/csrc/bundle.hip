@@ -26,10 +26,12 @@
 // butterfly.  k_bundle_solve: one workgroup places the pairs' blocks in rising order into the lower triangle in LDS
 // (6 N (6 N + 1) / 2 doubles, 37 KB at N = 16), damps, transforms the anchor, factors the 6 N - 7 kept rows in place
 // (right-looking Cholesky: every element takes its subtractions in rising column order whatever the thread) and solves.
-// k_bundle_evaluate / k_bundle_update: the candidates and the LM rule of pnp_common.hpp (LM_*, lm_better).  No atomics:
-// the same input gives the same bits on every run.
+// k_bundle_evaluate / k_bundle_update: the candidates and the accept / damp / stop bookkeeping of the joint solvers
+// (joint_common.hpp's lm_update, shared with calibrate.hip and stereo_calibrate.hip; their arrow template is not used
+// here: the many blocks are 3 x 3 and the shared one is factored in LDS).  No atomics: the same input gives the same bits
+// on every run.
 #include "compact.hpp"
-#include "pnp_common.hpp"
+#include "joint_common.hpp"
 
 namespace camd {
 
@@ -45,8 +47,8 @@ enum { BP_AA = 0, BP_BB = 21, BP_BA = 42, BP_GA = 78, BP_GB = 84, BP_DA = 90, BP
 // a partial of the candidate: its cost, |dX|^2, |X|^2, points whose candidate is behind a view or whose block did not factor
 enum { BE_COST = 0, BE_STEP = 1, BE_NORM = 2, BE_BAD = 3 };
 enum {
-    BS_DONE = CAMD_BUNDLE_DONE, BS_ACCEPT = CAMD_BUNDLE_ACCEPT, BS_LAMBDA = CAMD_BUNDLE_LAMBDA, BS_COST = CAMD_BUNDLE_COST,
-    BS_EVALS = CAMD_BUNDLE_EVALUATIONS, BS_ITERS = CAMD_BUNDLE_ITERATIONS, BS_STATUS = CAMD_BUNDLE_STATUS,
+    BS_ACCEPT = CAMD_BUNDLE_ACCEPT, BS_LAMBDA = CAMD_BUNDLE_LAMBDA, BS_COST = CAMD_BUNDLE_COST,
+    BS_EVALS = CAMD_BUNDLE_EVALUATIONS, BS_STATUS = CAMD_BUNDLE_STATUS,
     BS_CONVERGED = CAMD_BUNDLE_CONVERGED, BS_SOLVED = CAMD_BUNDLE_SOLVED, BS_PIVOT = CAMD_BUNDLE_PIVOT,
     BS_FIXED = CAMD_BUNDLE_FIXED, BS_ANCHOR = CAMD_BUNDLE_ANCHOR, BS_AXIS = CAMD_BUNDLE_AXIS, BS_COST0 = CAMD_BUNDLE_COST0,
     BS_POSES = CAMD_BUNDLE_POSES, BS_CAND = CAMD_BUNDLE_CANDIDATE, BS_STEP = CAMD_BUNDLE_STEP, BS_K = CAMD_BUNDLE_K,
@@ -640,21 +642,10 @@ __global__ __launch_bounds__(64) void k_bundle_update(BundleArgs g, int max_eval
         norm += pose_norm2(g.state + BS_POSES + 12 * v + 9);
     }
     const double c = g.state[BS_COST], c2 = s[BE_BAD] == 0. ? s[BE_COST] : INFINITY;  // a point behind a view: infinite
-    const bool small = solved && lm_small(step, norm);
-    const bool better = uniform(solved && lm_better(c2, c));
+    const bool better = lm_update(g.state, lane, solved, c, c2, step, norm, max_evaluations);
+    if (lane == 0 && g.state[BS_EVALS] == 1.) g.state[BS_COST0] = c;  // (the count lm_update has just written)
     if (better)
         for (int e = lane; e < 12 * g.views; e += 64) g.state[BS_POSES + e] = g.state[BS_CAND + e];
-    if (lane == 0) {
-        const double lambda = lm_next(g.state[BS_LAMBDA], better), evals = g.state[BS_EVALS] + 1.;
-        const bool stopped = lm_stopped(small, lambda);
-        if (evals == 1.) g.state[BS_COST0] = c;
-        if (better) g.state[BS_ITERS] += 1.;
-        g.state[BS_LAMBDA] = lambda;
-        g.state[BS_EVALS] = evals;
-        g.state[BS_ACCEPT] = better ? 1. : 0.;
-        g.state[BS_CONVERGED] = stopped ? 1. : 0.;
-        g.state[BS_DONE] = (stopped || evals >= (double)max_evaluations) ? 1. : 0.;
-    }
 }
 
 // ---- stage 6: the points back to their rows, and every used point's depth in both of its views ------------------------

@@ -7,31 +7,33 @@
 // frames.  Per frame i the sums over its points are A_i (6 x 6), B_i (6 x 9), C_i (9 x 9), gp_i, gk_i, c_i: 136 doubles in
 // the workspace.  The block is solved from the reduced system
 //   sum_i (C_i - B_i^T (A_i + l diag A_i)^-1 B_i) + l diag sum_i C_i,
-// and every frame's step follows by back-substitution.  Damping and stopping are pnp_common.hpp's one rule (LM_*), which
-// pnp.hip follows too; the acceptance of a step is lm_better, shared with stereo_calibrate.hip.
+// and every frame's step follows by back-substitution.
+//
+// Shared with stereo_calibrate.hip, in joint_common.hpp: the frame's workspace (ArrowBlock<9>), its three passes over the
+// points (arrow_linearise), its back-substitution (arrow_frame_step), its candidate row, and the accept / damp / stop
+// bookkeeping (lm_update, bundle.hip's too).  Kept here: point_terms (the Jacobian in the intrinsics), the single-level
+// sum over frames with the frame's Schur nest written out in k_calib_solve (arrow_frame_schur's, accumulating), the
+// block's solve with its mask and the order of FINAL's scaling, the move of the poses and of K in the update, the
+// start's homographies.
 //
 // Kernels.  k_calib_linearise and k_calib_evaluate sum over a frame's points: one wavefront per frame, four frames per
-// workgroup, no workgroup barrier, the butterfly of pnp_common.hpp.  136 accumulators do not fit beside the Jacobian, so
-// the linearisation makes three passes over the points: A gp c, then B, then C gk.  k_calib_solve and k_calib_update sum
-// over FRAMES: one wavefront, lane l takes frames l, l + 64, ... in rising order, then the same butterfly -- a fixed order
-// without atomics, so the same input gives the same bits on every run.  Lambda, the costs, the accept decision, both
-// parameter sets and the stop flag live in `state` on the device; the host reads two numbers per evaluation.
+// workgroup, no workgroup barrier, the butterfly of pnp_common.hpp.  k_calib_solve and k_calib_update sum over FRAMES: one
+// wavefront, lane l takes frames l, l + 64, ... in rising order, then the same butterfly -- a fixed order without atomics,
+// so the same input gives the same bits on every run.  Lambda, the costs, the accept decision, both parameter sets and
+// the stop flag live in `state` on the device; the host reads two numbers per evaluation.
 //
 // cv2's own iteration is UNPINNED.
-#include "pnp_common.hpp"
+#include "joint_common.hpp"
 
 namespace camd {
 
 constexpr int CALIB_MAX_EVALUATIONS = 100;      // every case of tests/calibrate_cases.py ends below half of it
 constexpr int CALIB_WS = CAMD_CALIB_WORKSPACE_DOUBLES, CALIB_CAND = CAMD_CALIB_CANDIDATE_DOUBLES;
-// the workspace of one frame
-enum { WS_A = 0, WS_B = 21, WS_C = 75, WS_GP = 120, WS_GK = 126, WS_COST = 135 };
-// the state (doubles; include/calibrating_amd.h names the places the host reads and writes)
+using WS = ArrowBlock<9>;  // the workspace of one frame
+// the state beyond lm_update's places (doubles; include/calibrating_amd.h names the places the host reads and writes)
 enum {
-    CS_DONE = CAMD_CALIB_DONE, CS_ACCEPT = CAMD_CALIB_ACCEPT, CS_LAMBDA = CAMD_CALIB_LAMBDA, CS_COST = CAMD_CALIB_COST,
-    CS_EVALS = CAMD_CALIB_EVALUATIONS, CS_ITERS = CAMD_CALIB_ITERATIONS, CS_STATUS = CAMD_CALIB_STATUS,
-    CS_CONVERGED = CAMD_CALIB_CONVERGED, CS_K = CAMD_CALIB_K, CS_DK = CAMD_CALIB_DK, CS_MASK = CAMD_CALIB_MASK,
-    CS_SOLVED = CAMD_CALIB_SOLVED, CS_PIVOT = CAMD_CALIB_PIVOT
+    CS_LAMBDA = CAMD_CALIB_LAMBDA, CS_COST = CAMD_CALIB_COST, CS_STATUS = CAMD_CALIB_STATUS, CS_CONVERGED = CAMD_CALIB_CONVERGED,
+    CS_K = CAMD_CALIB_K, CS_DK = CAMD_CALIB_DK, CS_MASK = CAMD_CALIB_MASK, CS_SOLVED = CAMD_CALIB_SOLVED, CS_PIVOT = CAMD_CALIB_PIVOT
 };
 
 struct CalibArgs {
@@ -51,24 +53,11 @@ __device__ __forceinline__ void load_intrinsics(const double* k, Pinhole& cam, L
     lens = {k[4], k[5], k[6], k[7], k[8], 0., 0., 0., 0., 0., 0., 0.};
 }
 
-// the rows of used frame u; a frame index or a range outside the arrays reads nothing
-__device__ __forceinline__ Frame used_frame(const CalibArgs& a, int u)
-{
-    const int f = a.used[u];
-    Frame none = {0, 0, 0, PNP_NONFINITE};
-    if (f < 0 || f >= a.p.frames) return none;
-    Frame fr = frame_rows(a.p, f, 1);
-    if (fr.status != PNP_OK) fr.n = 0;
-    return fr;
-}
-
 // one point under R, t, cam, lens: pose_terms' residual r and 2 x 6 Jacobian Jp with respect to the pose, and the 2 x 9
-// Jacobian Jk with respect to fx fy cx cy k1 k2 p1 p2 k3
-struct PointTerms {
-    double r[2], Jp[2][6], Jk[2][9];
-};
-__device__ __forceinline__ void point_terms(const camd_pnp_points& p, const Frame& fr, int i, const Pinhole& cam, const Lens& k,
-                                            const double* R, const double* t, PointTerms& o)
+// Jacobian Jk with respect to fx fy cx cy k1 k2 p1 p2 k3; returned: the point's cost |r|^2
+using PointTerms = ArrowTerms<9, false>;
+__device__ __forceinline__ double point_terms(const camd_pnp_points& p, const Frame& fr, int i, const Pinhole& cam, const Lens& k,
+                                              const double* R, const double* t, PointTerms& o)
 {
     const Projected n = pose_terms(p, fr, i, cam, k, R, t, o.r, o.Jp);
     const double x = n.x, y = n.y, xd = n.xd, yd = n.yd;
@@ -80,6 +69,7 @@ __device__ __forceinline__ void point_terms(const camd_pnp_points& p, const Fram
     o.Jk[0][8] = cam.fx * (x * r6);
     o.Jk[1][4] = cam.fy * (y * r2), o.Jk[1][5] = cam.fy * (y * r4), o.Jk[1][6] = cam.fy * a3, o.Jk[1][7] = cam.fy * a1;
     o.Jk[1][8] = cam.fy * (y * r6);
+    return o.r[0] * o.r[0] + o.r[1] * o.r[1];
 }
 
 // ---- the sums over a frame's points -------------------------------------------------------------------------------
@@ -87,66 +77,14 @@ __global__ __launch_bounds__(256) void k_calib_linearise(CalibArgs a)
 {
     const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= a.used_n) return;  // (the whole wave; there is no barrier to miss)
-    const Frame fr = used_frame(a, u);
+    const Frame fr = used_frame(a.p, a.used, u);
     Pinhole cam;
     Lens k;
     load_intrinsics(a.state + CS_K, cam, k);
     double R[9], t[3];
     load_pose(a.poses + (size_t)u * 12, R, t);
-    double* w = a.ws + (size_t)u * CALIB_WS;
-    {  // pass 1: A, gp, c
-        double A[21] = {}, g[6] = {}, c = 0.;
-        for (int i = lane; i < fr.n; i += 64) {
-            PointTerms o;
-            point_terms(a.p, fr, i, cam, k, R, t, o);
-            add_outer<6>(A, o.Jp[0], o.Jp[1]);
-            add_gradient<6>(g, o.Jp[0], o.Jp[1], o.r);
-            c += o.r[0] * o.r[0] + o.r[1] * o.r[1];
-        }
-        wave_sum_all<21>(A);
-        wave_sum_all<6>(g);
-        c = wave_sum(c);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < 21; q++) w[WS_A + q] = A[q];
-#pragma unroll
-            for (int q = 0; q < 6; q++) w[WS_GP + q] = g[q];
-            w[WS_COST] = c;
-        }
-    }
-    {  // pass 2: B
-        double B[54] = {};
-        for (int i = lane; i < fr.n; i += 64) {
-            PointTerms o;
-            point_terms(a.p, fr, i, cam, k, R, t, o);
-#pragma unroll
-            for (int p = 0; p < 6; p++)
-#pragma unroll
-                for (int q = 0; q < 9; q++) B[p * 9 + q] += o.Jp[0][p] * o.Jk[0][q] + o.Jp[1][p] * o.Jk[1][q];
-        }
-        wave_sum_all<54>(B);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < 54; q++) w[WS_B + q] = B[q];
-        }
-    }
-    {  // pass 3: C, gk
-        double C[45] = {}, g[9] = {};
-        for (int i = lane; i < fr.n; i += 64) {
-            PointTerms o;
-            point_terms(a.p, fr, i, cam, k, R, t, o);
-            add_outer<9>(C, o.Jk[0], o.Jk[1]);
-            add_gradient<9>(g, o.Jk[0], o.Jk[1], o.r);
-        }
-        wave_sum_all<45>(C);
-        wave_sum_all<9>(g);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < 45; q++) w[WS_C + q] = C[q];
-#pragma unroll
-            for (int q = 0; q < 9; q++) w[WS_GK + q] = g[q];
-        }
-    }
+    arrow_linearise<9, false>([&](int i, PointTerms& o) { return point_terms(a.p, fr, i, cam, k, R, t, o); }, fr.n, lane,
+                              a.ws + (size_t)u * CALIB_WS);
 }
 
 // the candidate of one frame: its step by back-substitution from the block's step, its pose, and the cost there
@@ -155,22 +93,9 @@ __global__ __launch_bounds__(256) void k_calib_evaluate(CalibArgs a)
     const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= a.used_n) return;
     if (!uniform(a.state[CS_SOLVED] != 0.)) return;  // no step: k_calib_update rejects
-    const Frame fr = used_frame(a, u);
-    const double* w = a.ws + (size_t)u * CALIB_WS;
-    double L[21], d[6], k2[9], R[9], t[3], pivot;
-    damped<6>(w + WS_A, a.state[CS_LAMBDA], L);
-    cholesky<6>(L, pivot);  // (k_calib_solve factored it: it did not fail)
-#pragma unroll
-    for (int p = 0; p < 6; p++) {
-        double s = w[WS_GP + p];
-#pragma unroll
-        for (int q = 0; q < 9; q++) s += w[WS_B + p * 9 + q] * a.state[CS_DK + q];
-        d[p] = -s;
-    }
-    cholesky_solve<6>(L, d);
-    load_pose(a.poses + (size_t)u * 12, R, t);
-    double R2[9], t2[3] = {t[0] + d[3], t[1] + d[4], t[2] + d[5]};
-    rotate_left(d, R, R2);
+    const Frame fr = used_frame(a.p, a.used, u);
+    double d[6], k2[9], t[3], R2[9], t2[3];
+    arrow_frame_step<9>(a.ws + (size_t)u * CALIB_WS, a.state[CS_LAMBDA], a.state + CS_DK, a.poses + (size_t)u * 12, d, t, R2, t2);
 #pragma unroll
     for (int q = 0; q < 9; q++) k2[q] = a.state[CS_K + q] + a.state[CS_DK + q];
     Pinhole cam;
@@ -179,17 +104,10 @@ __global__ __launch_bounds__(256) void k_calib_evaluate(CalibArgs a)
     double c = 0.;
     for (int i = lane; i < fr.n; i += 64) {
         PointTerms o;
-        point_terms(a.p, fr, i, cam, k, R2, t2, o);
-        c += o.r[0] * o.r[0] + o.r[1] * o.r[1];
+        c += point_terms(a.p, fr, i, cam, k, R2, t2, o);
     }
     c = wave_sum(c);
-    if (lane == 0) {
-        double* o = a.cand + (size_t)u * CALIB_CAND;
-        store_pose(o, R2, t2);
-        o[12] = c;
-        o[13] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-        o[14] = pose_norm2(t);
-    }
+    if (lane == 0) arrow_candidate_store(a.cand + (size_t)u * CALIB_CAND, R2, t2, c, d, t);
 }
 
 // ---- the sums over frames: one wavefront ---------------------------------------------------------------------------
@@ -205,37 +123,38 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
     int bad = 0;
     for (int u = lane; u < a.used_n; u += 64) {
         const double* w = a.ws + (size_t)u * CALIB_WS;
+        // arrow_frame_schur's nest, adding each finished number where it is made (joint_common.hpp says why it is not called)
         double L[21], y[6], frame_pivot;
-        damped<6>(w + WS_A, lambda, L);
+        damped<6>(w + WS::A, lambda, L);
         bad |= !cholesky<6>(L, frame_pivot);
 #pragma unroll
-        for (int p = 0; p < 6; p++) y[p] = w[WS_GP + p];
+        for (int p = 0; p < 6; p++) y[p] = w[WS::GP + p];
         cholesky_solve<6>(L, y);
 #pragma unroll
         for (int q = 0; q < 9; q++) {
-            double s = w[WS_GK + q];
+            double s = w[WS::GK + q];
 #pragma unroll
-            for (int p = 0; p < 6; p++) s -= w[WS_B + p * 9 + q] * y[p];
+            for (int p = 0; p < 6; p++) s -= w[WS::B + p * 9 + q] * y[p];
             g[q] += s;
         }
 #pragma unroll
         for (int j = 0; j < 9; j++) {
 #pragma unroll
-            for (int p = 0; p < 6; p++) y[p] = w[WS_B + p * 9 + j];
+            for (int p = 0; p < 6; p++) y[p] = w[WS::B + p * 9 + j];
             cholesky_solve<6>(L, y);
 #pragma unroll
             for (int q = 0; q <= j; q++) {
-                double s = w[WS_C + j * (j + 1) / 2 + q];
+                double s = w[WS::C + j * (j + 1) / 2 + q];
 #pragma unroll
-                for (int p = 0; p < 6; p++) s -= w[WS_B + p * 9 + q] * y[p];
+                for (int p = 0; p < 6; p++) s -= w[WS::B + p * 9 + q] * y[p];
                 S[j * (j + 1) / 2 + q] += s;
             }
-            dC[j] += w[WS_C + j * (j + 1) / 2 + j];
+            dC[j] += w[WS::C + j * (j + 1) / 2 + j];
         }
         if (FINAL) {
-            cost += w[WS_COST];
-            const Frame fr = used_frame(a, u);
-            a.error[u] = sqrt(__ddiv_rn(w[WS_COST], (double)(fr.n > 0 ? fr.n : 1)));
+            cost += w[WS::COST];
+            const Frame fr = used_frame(a.p, a.used, u);
+            a.error[u] = sqrt(__ddiv_rn(w[WS::COST], (double)(fr.n > 0 ? fr.n : 1)));
         }
     }
     wave_sum_all<45>(S);
@@ -283,14 +202,15 @@ __global__ __launch_bounds__(64) void k_calib_solve(CalibArgs a)
     }
 }
 
-// accept or reject the candidate, move lambda, decide whether to stop (the LM rule on the joint step and parameters)
+// accept or reject the candidate, move lambda, decide whether to stop (lm_update); after a step that is taken the frames'
+// poses and the intrinsics move here
 __global__ __launch_bounds__(64) void k_calib_update(CalibArgs a, int max_evaluations)
 {
     const int lane = threadIdx.x;
     const bool solved = a.state[CS_SOLVED] != 0.;
     double c = 0., c2 = 0., step = 0., norm = 0.;
     for (int u = lane; u < a.used_n; u += 64) {
-        c += a.ws[(size_t)u * CALIB_WS + WS_COST];
+        c += a.ws[(size_t)u * CALIB_WS + WS::COST];
         if (solved) {
             const double* o = a.cand + (size_t)u * CALIB_CAND;
             c2 += o[12], step += o[13], norm += o[14];
@@ -303,24 +223,12 @@ __global__ __launch_bounds__(64) void k_calib_update(CalibArgs a, int max_evalua
         k[q] = a.state[CS_K + q], dk[q] = a.state[CS_DK + q];
         step += dk[q] * dk[q], norm += k[q] * k[q];
     }
-    const bool small = solved && lm_small(step, norm);
-    const bool better = uniform(solved && lm_better(c2, c));
-    if (better)
-        for (int u = lane; u < a.used_n; u += 64)
-            for (int q = 0; q < 12; q++) a.poses[(size_t)u * 12 + q] = a.cand[(size_t)u * CALIB_CAND + q];
+    if (!lm_update(a.state, lane, solved, c, c2, step, norm, max_evaluations)) return;
+    for (int u = lane; u < a.used_n; u += 64)
+        for (int q = 0; q < 12; q++) a.poses[(size_t)u * 12 + q] = a.cand[(size_t)u * CALIB_CAND + q];
     if (lane == 0) {
-        const double lambda = lm_next(a.state[CS_LAMBDA], better), evals = a.state[CS_EVALS] + 1.;
-        const bool stopped = lm_stopped(small, lambda);
-        if (better) {
 #pragma unroll
-            for (int q = 0; q < 9; q++) a.state[CS_K + q] = k[q] + dk[q];
-            a.state[CS_ITERS] += 1.;
-        }
-        a.state[CS_LAMBDA] = lambda;
-        a.state[CS_EVALS] = evals;
-        a.state[CS_ACCEPT] = better ? 1. : 0.;
-        a.state[CS_CONVERGED] = stopped ? 1. : 0.;
-        a.state[CS_DONE] = (stopped || evals >= (double)max_evaluations) ? 1. : 0.;
+        for (int q = 0; q < 9; q++) a.state[CS_K + q] = k[q] + dk[q];
     }
 }
 

@@ -10,7 +10,8 @@
 //   LM_*, lm_small, lm_next, lm_stopped        the one Levenberg-Marquardt rule (damping, stopping); pose_norm2: its |p|^2
 //   lm_better                                  the joint solvers' acceptance: a lower cost, or one within the rounding of the sums
 //   rotate_left; null_vector, direct_linear_transform   R <- exp([w]x) R; the Hartley-normalised start (H or P)
-// pnp.hip accepts a step by the bare comparison of the costs; calibrate.hip and stereo_calibrate.hip by lm_better.
+// pnp.hip accepts a step by the bare comparison of the costs; the joint solvers (calibrate.hip, stereo_calibrate.hip,
+// bundle.hip) by lm_better, inside joint_common.hpp's lm_update: what those solvers share beyond these primitives is there.
 #pragma once
 
 #include <climits>

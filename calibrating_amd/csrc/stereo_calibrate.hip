@@ -9,8 +9,13 @@
 // frame i the sums over its points are A_i (6 x 6, both cameras), B_i (6 x 6), C_i (6 x 6, camera 2), gp_i, gr_i, c_i: 91
 // doubles in the workspace.  The rig's step is solved from the reduced system
 //   sum_i (C_i - B_i^T (A_i + l diag A_i)^-1 B_i) + l diag sum_i C_i,
-// and every frame's step follows by back-substitution.  Damping, stopping and the acceptance of a step are
-// pnp_common.hpp's (LM_*, lm_better).
+// and every frame's step follows by back-substitution.
+//
+// Shared with calibrate.hip, in joint_common.hpp: the frame's workspace (ArrowBlock<6>), its three passes over the points
+// (arrow_linearise), its contribution to the reduced system (arrow_frame_schur), its back-substitution
+// (arrow_frame_step), its candidate row, and the accept / damp / stop bookkeeping (lm_update, bundle.hip's too).  Kept
+// here: rig_terms with compose (two cameras, the Jacobians in the rig), the two-level sum over frames, the rig's solve and
+// candidate, the move of the frames' poses in the NEXT linearisation.
 //
 // Camera 2's terms come from pose_terms at the composed pose (R R_i, R t_i + t), whose 2 x 6 Jacobian J2 = [Jw | Jd] gives
 //   with respect to the frame:  [Jw R | Jd R]                    (exp([R w_i]x) R R_i = R exp([w_i]x) R_i)
@@ -18,8 +23,7 @@
 // (tests/stereo_calibrate_ref.py checks both against finite differences).
 //
 // Kernels.  k_stereo_linearise and k_stereo_evaluate sum over a frame's points: one wavefront per frame, four frames per
-// workgroup, no workgroup barrier, the butterfly of pnp_common.hpp; 91 accumulators do not fit beside two Jacobians, so
-// the linearisation makes three passes over the points: A gp c, then B, then C gr.  The sums over FRAMES have two levels,
+// workgroup, no workgroup barrier, the butterfly of pnp_common.hpp.  The sums over FRAMES have two levels,
 // unlike calibrate.hip's: k_stereo_reduce gives every used frame a lane of its own, which factors the frame's damped
 // block and forms its contribution to the reduced system (21 + 6 doubles, diag C_i, the cost); the 64 frames of a
 // workgroup are summed by the butterfly into one partial.  k_stereo_solve, one wavefront, then adds the partials -- lane l
@@ -29,21 +33,19 @@
 // numbers per evaluation (camd_calib_read: the first two places of the state are calibrate.hip's).
 //
 // cv2's own iteration and its 1e-5 stop are UNPINNED.
-#include "pnp_common.hpp"
+#include "joint_common.hpp"
 
 namespace camd {
 
 constexpr int STEREO_MAX_EVALUATIONS = 100;  // every case of tests/stereo_calibrate_cases.py ends below half of it
 constexpr int STEREO_WS = CAMD_STEREO_WORKSPACE_DOUBLES, STEREO_CAND = CAMD_STEREO_CANDIDATE_DOUBLES;
 constexpr int STEREO_PARTIAL = CAMD_STEREO_PARTIAL_DOUBLES;
-// the workspace of one frame
-enum { SW_A = 0, SW_B = 21, SW_C = 57, SW_GP = 78, SW_GR = 84, SW_COST = 90 };
+using WS = ArrowBlock<6>;  // the workspace of one frame
 // a partial of the reduced system: S 21, g 6, diag C 6, the cost, then the count of frames whose block did not factor
 enum { SP_S = 0, SP_G = 21, SP_DC = 27, SP_COST = 33, SP_BAD = 34 };
-// the state (doubles; include/calibrating_amd.h names the places the host reads and writes)
+// the state beyond lm_update's places (doubles; include/calibrating_amd.h names the places the host reads and writes)
 enum {
-    SS_DONE = CAMD_STEREO_DONE, SS_ACCEPT = CAMD_STEREO_ACCEPT, SS_LAMBDA = CAMD_STEREO_LAMBDA, SS_COST = CAMD_STEREO_COST,
-    SS_EVALS = CAMD_STEREO_EVALUATIONS, SS_ITERS = CAMD_STEREO_ITERATIONS, SS_STATUS = CAMD_STEREO_STATUS,
+    SS_ACCEPT = CAMD_STEREO_ACCEPT, SS_LAMBDA = CAMD_STEREO_LAMBDA, SS_COST = CAMD_STEREO_COST, SS_STATUS = CAMD_STEREO_STATUS,
     SS_CONVERGED = CAMD_STEREO_CONVERGED, SS_RIG = CAMD_STEREO_RIG, SS_STEP = CAMD_STEREO_STEP,
     SS_CAND = CAMD_STEREO_CANDIDATE, SS_SOLVED = CAMD_STEREO_SOLVED, SS_PIVOT = CAMD_STEREO_PIVOT
 };
@@ -61,18 +63,6 @@ struct StereoArgs {
     double* partial;  // ceil(used_n / 64) x 36
     double* error;    // used_n: sqrt(c_i / 2 n_i)
 };
-
-// the rows of used frame u (camera 1's image rows; camera 2's lie at the same places); a frame index or a range outside
-// the arrays reads nothing
-__device__ __forceinline__ Frame used_frame(const StereoArgs& a, int u)
-{
-    const int f = a.used[u];
-    Frame none = {0, 0, 0, PNP_NONFINITE};
-    if (f < 0 || f >= a.p1.frames) return none;
-    Frame fr = frame_rows(a.p1, f, 1);
-    if (fr.status != PNP_OK) fr.n = 0;
-    return fr;
-}
 
 // a frame's pose in camera 2: Rc = R Ri, tc = R ti + t; rt = R ti
 __device__ __forceinline__ void compose(const double* R, const double* t, const double* Ri, const double* ti, double* Rc, double* tc,
@@ -92,29 +82,35 @@ struct RigPose {
     double Ri[9], ti[3], R[9], Rc[9], tc[3], rt[3];
 };
 
-// one point in both cameras: the residuals, camera 1's Jacobian with respect to the frame (J1), camera 2's with respect to
-// the frame (Jf) and to the rig (Jr)
-struct RigTerms {
-    double r1[2], r2[2], J1[2][6], Jf[2][6], Jr[2][6];
-};
-__device__ __forceinline__ void rig_terms(const StereoArgs& a, const Frame& fr, int i, const RigPose& q, RigTerms& o)
+// the cost of one point in both cameras, grouped as every sum of it here is
+__device__ __forceinline__ double rig_cost(const double* r1, const double* r2)
+{
+    return (r1[0] * r1[0] + r1[1] * r1[1]) + (r2[0] * r2[0] + r2[1] * r2[1]);
+}
+
+// one point in both cameras.  Camera 1 sees the frame alone: its residual r0 and Jacobian J0 with respect to the frame.
+// Camera 2 sees the rig too: its residual r, its Jacobian with respect to the frame (Jp) and to the rig (Jk).  Returned:
+// the point's cost
+using RigTerms = ArrowTerms<6, true>;
+__device__ __forceinline__ double rig_terms(const StereoArgs& a, const Frame& fr, int i, const RigPose& q, RigTerms& o)
 {
     double J2[2][6];
-    pose_terms(a.p1, fr, i, a.cam1, a.k1, q.Ri, q.ti, o.r1, o.J1);
-    pose_terms(a.p2, fr, i, a.cam2, a.k2, q.Rc, q.tc, o.r2, J2);
+    pose_terms(a.p1, fr, i, a.cam1, a.k1, q.Ri, q.ti, o.r0, o.J0);
+    pose_terms(a.p2, fr, i, a.cam2, a.k2, q.Rc, q.tc, o.r, J2);
 #pragma unroll
     for (int e = 0; e < 2; e++) {
         const double* g = J2[e] + 3;
 #pragma unroll
         for (int j = 0; j < 3; j++) {
-            o.Jf[e][j] = J2[e][0] * q.R[j] + J2[e][1] * q.R[3 + j] + J2[e][2] * q.R[6 + j];
-            o.Jf[e][3 + j] = g[0] * q.R[j] + g[1] * q.R[3 + j] + g[2] * q.R[6 + j];
-            o.Jr[e][3 + j] = g[j];
+            o.Jp[e][j] = J2[e][0] * q.R[j] + J2[e][1] * q.R[3 + j] + J2[e][2] * q.R[6 + j];
+            o.Jp[e][3 + j] = g[0] * q.R[j] + g[1] * q.R[3 + j] + g[2] * q.R[6 + j];
+            o.Jk[e][3 + j] = g[j];
         }
-        o.Jr[e][0] = J2[e][0] + (q.rt[1] * g[2] - q.rt[2] * g[1]);
-        o.Jr[e][1] = J2[e][1] + (q.rt[2] * g[0] - q.rt[0] * g[2]);
-        o.Jr[e][2] = J2[e][2] + (q.rt[0] * g[1] - q.rt[1] * g[0]);
+        o.Jk[e][0] = J2[e][0] + (q.rt[1] * g[2] - q.rt[2] * g[1]);
+        o.Jk[e][1] = J2[e][1] + (q.rt[2] * g[0] - q.rt[0] * g[2]);
+        o.Jk[e][2] = J2[e][2] + (q.rt[0] * g[1] - q.rt[1] * g[0]);
     }
+    return rig_cost(o.r0, o.r);
 }
 
 // ---- the sums over a frame's points -------------------------------------------------------------------------------
@@ -124,7 +120,7 @@ __global__ __launch_bounds__(256) void k_stereo_linearise(StereoArgs a)
 {
     const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= a.used_n) return;  // (the whole wave; there is no barrier to miss)
-    const Frame fr = used_frame(a, u);
+    const Frame fr = used_frame(a.p1, a.used, u);  // (camera 1's image rows; camera 2's lie at the same places)
     RigPose q;
     double t[3];
     double* pose = a.poses + (size_t)u * 12;
@@ -136,62 +132,7 @@ __global__ __launch_bounds__(256) void k_stereo_linearise(StereoArgs a)
     }
     load_pose(a.state + SS_RIG, q.R, t);
     compose(q.R, t, q.Ri, q.ti, q.Rc, q.tc, q.rt);
-    double* w = a.ws + (size_t)u * STEREO_WS;
-    {  // pass 1: A, gp, c
-        double A[21] = {}, g[6] = {}, c = 0.;
-        for (int i = lane; i < fr.n; i += 64) {
-            RigTerms o;
-            rig_terms(a, fr, i, q, o);
-            add_outer<6>(A, o.J1[0], o.J1[1]);
-            add_outer<6>(A, o.Jf[0], o.Jf[1]);
-            add_gradient<6>(g, o.J1[0], o.J1[1], o.r1);
-            add_gradient<6>(g, o.Jf[0], o.Jf[1], o.r2);
-            c += (o.r1[0] * o.r1[0] + o.r1[1] * o.r1[1]) + (o.r2[0] * o.r2[0] + o.r2[1] * o.r2[1]);
-        }
-        wave_sum_all<21>(A);
-        wave_sum_all<6>(g);
-        c = wave_sum(c);
-        if (lane == 0) {
-#pragma unroll
-            for (int p = 0; p < 21; p++) w[SW_A + p] = A[p];
-#pragma unroll
-            for (int p = 0; p < 6; p++) w[SW_GP + p] = g[p];
-            w[SW_COST] = c;
-        }
-    }
-    {  // pass 2: B
-        double B[36] = {};
-        for (int i = lane; i < fr.n; i += 64) {
-            RigTerms o;
-            rig_terms(a, fr, i, q, o);
-#pragma unroll
-            for (int p = 0; p < 6; p++)
-#pragma unroll
-                for (int r = 0; r < 6; r++) B[p * 6 + r] += o.Jf[0][p] * o.Jr[0][r] + o.Jf[1][p] * o.Jr[1][r];
-        }
-        wave_sum_all<36>(B);
-        if (lane == 0) {
-#pragma unroll
-            for (int p = 0; p < 36; p++) w[SW_B + p] = B[p];
-        }
-    }
-    {  // pass 3: C, gr
-        double C[21] = {}, g[6] = {};
-        for (int i = lane; i < fr.n; i += 64) {
-            RigTerms o;
-            rig_terms(a, fr, i, q, o);
-            add_outer<6>(C, o.Jr[0], o.Jr[1]);
-            add_gradient<6>(g, o.Jr[0], o.Jr[1], o.r2);
-        }
-        wave_sum_all<21>(C);
-        wave_sum_all<6>(g);
-        if (lane == 0) {
-#pragma unroll
-            for (int p = 0; p < 21; p++) w[SW_C + p] = C[p];
-#pragma unroll
-            for (int p = 0; p < 6; p++) w[SW_GR + p] = g[p];
-        }
-    }
+    arrow_linearise<6, true>([&](int i, RigTerms& o) { return rig_terms(a, fr, i, q, o); }, fr.n, lane, a.ws + (size_t)u * STEREO_WS);
 }
 
 // the candidate of one frame: its step by back-substitution from the rig's step, its pose, and the cost there in both
@@ -201,24 +142,10 @@ __global__ __launch_bounds__(256) void k_stereo_evaluate(StereoArgs a)
     const int lane = threadIdx.x & 63, u = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= a.used_n) return;
     if (!uniform(a.state[SS_SOLVED] != 0.)) return;  // no step: k_stereo_update rejects
-    const Frame fr = used_frame(a, u);
-    const double* w = a.ws + (size_t)u * STEREO_WS;
-    double L[21], d[6], Ri[9], ti[3], pivot;
-    damped<6>(w + SW_A, a.state[SS_LAMBDA], L);
-    cholesky<6>(L, pivot);  // (k_stereo_reduce factored it: it did not fail)
-#pragma unroll
-    for (int p = 0; p < 6; p++) {
-        double s = w[SW_GP + p];
-#pragma unroll
-        for (int r = 0; r < 6; r++) s += w[SW_B + p * 6 + r] * a.state[SS_STEP + r];
-        d[p] = -s;
-    }
-    cholesky_solve<6>(L, d);
-    load_pose(a.poses + (size_t)u * 12, Ri, ti);
+    const Frame fr = used_frame(a.p1, a.used, u);
     RigPose q;
-    double t2[3];
-    rotate_left(d, Ri, q.Ri);
-    q.ti[0] = ti[0] + d[3], q.ti[1] = ti[1] + d[4], q.ti[2] = ti[2] + d[5];
+    double d[6], ti[3], t2[3];
+    arrow_frame_step<6>(a.ws + (size_t)u * STEREO_WS, a.state[SS_LAMBDA], a.state + SS_STEP, a.poses + (size_t)u * 12, d, ti, q.Ri, q.ti);
     load_pose(a.state + SS_CAND, q.R, t2);
     compose(q.R, t2, q.Ri, q.ti, q.Rc, q.tc, q.rt);
     double c = 0.;
@@ -226,15 +153,12 @@ __global__ __launch_bounds__(256) void k_stereo_evaluate(StereoArgs a)
         double r1[2], r2[2], J[2][6];
         pose_terms(a.p1, fr, i, a.cam1, a.k1, q.Ri, q.ti, r1, J);
         pose_terms(a.p2, fr, i, a.cam2, a.k2, q.Rc, q.tc, r2, J);
-        c += (r1[0] * r1[0] + r1[1] * r1[1]) + (r2[0] * r2[0] + r2[1] * r2[1]);
+        c += rig_cost(r1, r2);
     }
     c = wave_sum(c);
     if (lane == 0) {
         double* o = a.cand + (size_t)u * STEREO_CAND;
-        store_pose(o, q.Ri, q.ti);
-        o[12] = c;
-        o[13] = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-        o[14] = pose_norm2(ti);
+        arrow_candidate_store(o, q.Ri, q.ti, c, d, ti);
         o[15] = 0.;
     }
 }
@@ -252,36 +176,10 @@ __global__ __launch_bounds__(64) void k_stereo_reduce(StereoArgs a)
     int bad = 0;
     if (u < a.used_n) {
         const double* w = a.ws + (size_t)u * STEREO_WS;
-        double L[21], y[6], frame_pivot;
-        damped<6>(w + SW_A, lambda, L);
-        bad = !cholesky<6>(L, frame_pivot);
-#pragma unroll
-        for (int p = 0; p < 6; p++) y[p] = w[SW_GP + p];
-        cholesky_solve<6>(L, y);
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            double s = w[SW_GR + r];
-#pragma unroll
-            for (int p = 0; p < 6; p++) s -= w[SW_B + p * 6 + r] * y[p];
-            g[r] = s;
-        }
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-#pragma unroll
-            for (int p = 0; p < 6; p++) y[p] = w[SW_B + p * 6 + j];
-            cholesky_solve<6>(L, y);
-#pragma unroll
-            for (int r = 0; r <= j; r++) {
-                double s = w[SW_C + j * (j + 1) / 2 + r];
-#pragma unroll
-                for (int p = 0; p < 6; p++) s -= w[SW_B + p * 6 + r] * y[p];
-                S[j * (j + 1) / 2 + r] = s;
-            }
-            dC[j] = w[SW_C + j * (j + 1) / 2 + j];
-        }
-        cost = w[SW_COST];
+        bad = arrow_frame_schur<6>(w, lambda, S, g, dC);
+        cost = w[WS::COST];
         if (FINAL) {
-            const Frame fr = used_frame(a, (int)u);
+            const Frame fr = used_frame(a.p1, a.used, (int)u);
             a.error[u] = sqrt(__ddiv_rn(cost, 2. * (double)(fr.n > 0 ? fr.n : 1)));
         }
     }
@@ -356,15 +254,15 @@ __global__ __launch_bounds__(64) void k_stereo_solve(StereoArgs a, int partials)
     }
 }
 
-// accept or reject the candidate, move lambda, decide whether to stop (the LM rule on the joint step and parameters);
-// the frames' poses follow in k_stereo_linearise
+// accept or reject the candidate, move lambda, decide whether to stop (lm_update); after a step that is taken the rig
+// moves here, the frames' poses follow in k_stereo_linearise
 __global__ __launch_bounds__(64) void k_stereo_update(StereoArgs a, int max_evaluations)
 {
     const int lane = threadIdx.x;
     const bool solved = a.state[SS_SOLVED] != 0.;
     double c = 0., c2 = 0., step = 0., norm = 0.;
     for (int u = lane; u < a.used_n; u += 64) {
-        c += a.ws[(size_t)u * STEREO_WS + SW_COST];
+        c += a.ws[(size_t)u * STEREO_WS + WS::COST];
         if (solved) {
             const double* o = a.cand + (size_t)u * STEREO_CAND;
             c2 += o[12], step += o[13], norm += o[14];
@@ -377,21 +275,9 @@ __global__ __launch_bounds__(64) void k_stereo_update(StereoArgs a, int max_eval
 #pragma unroll
     for (int p = 0; p < 6; p++) step += a.state[SS_STEP + p] * a.state[SS_STEP + p];
     norm += pose_norm2(rig + 9);
-    const bool small = solved && lm_small(step, norm);
-    const bool better = uniform(solved && lm_better(c2, c));
-    if (lane == 0) {
-        const double lambda = lm_next(a.state[SS_LAMBDA], better), evals = a.state[SS_EVALS] + 1.;
-        const bool stopped = lm_stopped(small, lambda);
-        if (better) {
+    if (lm_update(a.state, lane, solved, c, c2, step, norm, max_evaluations) && lane == 0) {
 #pragma unroll
-            for (int p = 0; p < 12; p++) a.state[SS_RIG + p] = rig2[p];
-            a.state[SS_ITERS] += 1.;
-        }
-        a.state[SS_LAMBDA] = lambda;
-        a.state[SS_EVALS] = evals;
-        a.state[SS_ACCEPT] = better ? 1. : 0.;
-        a.state[SS_CONVERGED] = stopped ? 1. : 0.;
-        a.state[SS_DONE] = (stopped || evals >= (double)max_evaluations) ? 1. : 0.;
+        for (int p = 0; p < 12; p++) a.state[SS_RIG + p] = rig2[p];
     }
 }
 

@@ -97,6 +97,21 @@ def batch_layout(object_points, image_points, counts):
     return frames, lengths, shared
 
 
+def start_poses(pts, K, dist_ptr, ndist, planar, plane, min_points, dev, what):
+    """The batched PnP as it is, for a joint solver's start: ``camd_pnp_init`` + ``camd_pnp_refine`` under ``K`` (9 host
+    doubles) and ``ndist`` coefficients at ``dist_ptr`` -> (poses (frames, 12) float64, status (frames,) int32), on ``dev``."""
+    import torch
+    f64 = dict(dtype=torch.float64, device=dev)
+    pose0, poses = torch.empty((pts.frames, 12), **f64), torch.empty((pts.frames, 12), **f64)
+    rms, its = torch.empty(pts.frames, **f64), torch.empty(pts.frames, dtype=torch.int32, device=dev)
+    status = torch.empty(pts.frames, dtype=torch.int32, device=dev)
+    _native.call("camd_pnp_init", dev, ctypes.byref(pts), K.ctypes.data, dist_ptr, ndist, int(planar), plane.ctypes.data,
+                 pose0.data_ptr(), what=what)
+    _native.call("camd_pnp_refine", dev, ctypes.byref(pts), K.ctypes.data, dist_ptr, ndist, min_points, pose0.data_ptr(), 12,
+                 poses.data_ptr(), rms.data_ptr(), its.data_ptr(), status.data_ptr(), what=what)
+    return poses, status
+
+
 def _start_poses(T0, frames):
     T0 = np.asarray(T0, np.float64)
     if T0.shape not in ((4, 4), (frames, 4, 4)):

@@ -13,15 +13,14 @@ import ctypes
 
 import numpy as np
 
-from . import _native, geometry, pnp
+from . import _lm, _native, geometry, pnp
 from ._arrays import K9, dist, dtype_name, to_caller, to_device
+from ._lm import STATUS_OK, STATUS_SINGULAR, STATUS_TEXT  # noqa: F401
 
 # cv2's values
 CALIB_FIX_INTRINSIC = 0x00100
 CALIB_USE_EXTRINSIC_GUESS = 0x400000
 
-STATUS_OK, STATUS_SINGULAR = 0, 3
-STATUS_TEXT = {0: "ok", 3: "singular or not converged at the cap"}
 FRAME_STATUS_TEXT = {0: "ok", 1: "too few points", 2: "non-finite input in either camera", 3: "no start pose in either camera"}
 
 
@@ -46,12 +45,6 @@ def rig_start(T1, T2):
         rs.append(geometry.rodrigues(R).reshape(3))
         ts.append(B[:3, 3] - R @ A[:3, 3])
     return geometry.rodrigues(np.median(np.array(rs), axis=0)), np.median(np.array(ts), axis=0)
-
-
-def _read(state, dev, count):
-    out = np.empty(count)
-    _native.call("camd_calib_read", dev, state.data_ptr(), count, out.ctypes.data, what="stereo_calibrate")
-    return out
 
 
 def stereo_calibrate(object_points, image_points1, image_points2, K1, D1, K2, D2, counts=None, flags=CALIB_FIX_INTRINSIC,
@@ -111,14 +104,8 @@ def stereo_calibrate(object_points, image_points1, image_points2, K1, D1, K2, D2
     f64 = dict(dtype=torch.float64, device=dev)
     # start poses: the batched PnP as it is, once per camera
     start, status = [], []
-    for p, (Kf, Dv, dptr, nd) in zip((pts1, pts2), cams):
-        pose0, pose = torch.empty((frames, 12), **f64), torch.empty((frames, 12), **f64)
-        rms, its = torch.empty(frames, **f64), torch.empty(frames, dtype=torch.int32, device=dev)
-        st = torch.empty(frames, dtype=torch.int32, device=dev)
-        _native.call("camd_pnp_init", dev, ctypes.byref(p), Kf.ctypes.data, dptr, nd, int(planar), plane.ctypes.data,
-                     pose0.data_ptr(), what=what)
-        _native.call("camd_pnp_refine", dev, ctypes.byref(p), Kf.ctypes.data, dptr, nd, min_points, pose0.data_ptr(), 12,
-                     pose.data_ptr(), rms.data_ptr(), its.data_ptr(), st.data_ptr(), what=what)
+    for p, (Kf, _, dptr, nd) in zip((pts1, pts2), cams):
+        pose, st = pnp.start_poses(p, Kf, dptr, nd, planar, plane, min_points, dev, what)
         start.append(pose), status.append(st)
     s1, s2 = status[0].cpu().numpy(), status[1].cpu().numpy()
     # 1 and 2 are properties of the rows (the object rows and the counts are shared: 1 comes from both or neither)
@@ -143,20 +130,12 @@ def stereo_calibrate(object_points, image_points1, image_points2, K1, D1, K2, D2
     rig = _native.StereoRig(pts1, pts2, cams[0][0].ctypes.data, cams[0][2], cams[1][0].ctypes.data, cams[1][2], used.data_ptr(),
                             state.data_ptr(), cur.data_ptr(), cand.data_ptr(), ws.data_ptr(), partials.data_ptr(), err.data_ptr(),
                             cams[0][3], cams[1][3], n_used, 0)
-    linearise = lambda: _native.call("camd_stereo_linearise", dev, ctypes.byref(rig), what=what)  # noqa: E731
-    linearise()
-    while True:
-        _native.call("camd_stereo_step", dev, ctypes.byref(rig), what=what)
-        done, accept = _read(state, dev, 2)  # the only read-back of an evaluation: 16 bytes
-        if accept:
-            linearise()  # (takes the frames' candidates first)
-        if done:
-            break
+    # (a linearisation after a step that was taken gives the frames their candidates first)
+    _lm.iterate(state, dev, what, lambda: _native.call("camd_stereo_step", dev, ctypes.byref(rig), what=what),
+                lambda: _native.call("camd_stereo_linearise", dev, ctypes.byref(rig), what=what))
     _native.call("camd_stereo_finish", dev, ctypes.byref(rig), what=what)
-    s = _read(state, dev, _native.STEREO_STATE_DOUBLES)
-    if int(s[_native.STEREO_STATUS]) != STATUS_OK:
-        raise ValueError("stereo_calibrate: status %d (%s) after %d evaluations, smallest pivot %.3g"
-                         % (s[_native.STEREO_STATUS], STATUS_TEXT[3], s[_native.STEREO_EVALUATIONS], s[_native.STEREO_PIVOT]))
+    s = _lm.read_state(state, dev, _native.STEREO_STATE_DOUBLES, what)
+    _lm.check_status(what, s[_native.STEREO_STATUS], s[_native.STEREO_EVALUATIONS], s[_native.STEREO_PIVOT])
     T = pnp.poses_to_T(cur, fill=(frames, used.long()))
     error = torch.full((frames,), float("nan"), **f64)
     error[used.long()] = err
