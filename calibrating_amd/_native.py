@@ -41,6 +41,7 @@ INTER_LANCZOS4 = 4
 VALUE_F64, VALUE_F32, VALUE_U8 = 0, 1, 2  # value_type of camd_point_cloud_to_arr2d / camd_uvzs_to_arr2d
 VALUE_U16 = 3  # a uint16 depth in millimetres: camd_vis_depth only
 NEAREST_MAX_RADIUS = 32  # CAMD_NEAREST_MAX_RADIUS
+SPLINE_MAX_POINTS = 1024  # CAMD_SPLINE_MAX_POINTS
 POINTS_PIXELS = 0x100  # CAMD_POINTS_PIXELS, or-ed into camd_undistort_points' out_type
 # camd_calib_*: the sizes and the places of the state (CAMD_CALIB_*)
 CALIB_STATE_DOUBLES, CALIB_WORKSPACE_DOUBLES, CALIB_CANDIDATE_DOUBLES = 40, 136, 16
@@ -262,6 +263,11 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "camd_hull_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "camd_hull_mask": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "camd_spline_assemble": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
+    "camd_spline_solve": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "camd_spline_eval": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                 c_void_p]),
+    "camd_spline_upsize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "camd_cloud_workspace_bytes": (c_size_t, [c_size_t]),
     "camd_cloud_to_uvzs": (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_void_p,
                                    c_size_t, c_void_p, c_void_p, c_void_p]),

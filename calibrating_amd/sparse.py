@@ -8,7 +8,8 @@ Arguments are checked before the device is touched: ``inter_type="rbf"`` (SciPy'
 ``constrained_type`` (``cv2.convexHull`` / ``drawContours``, whose rasterisation nothing here can pin) raise
 ``NotImplementedError`` on a machine without a GPU too.  The fill inside the samples' convex hull is a function of its own
 with a mask contract of its own: ``interpolate_uvzs_in_hull`` / ``interpolate_sparse2d_in_hull`` / ``convex_hull_mask``
-(csrc/hull.hip), batched over frames.
+(csrc/hull.hip), batched over frames.  What ``inter_type="rbf"`` computes has names of its own too, a float64 result and a
+cap on the samples: ``interpolate_uvzs_rbf`` / ``interpolate_sparse2d_rbf`` (csrc/spline.hip), batched over frames.
 """
 import ctypes
 
@@ -24,14 +25,17 @@ COLLINEAR_TOL = 1e-9
 # interpolate_uvzs_in_hull / convex_hull_mask (csrc/hull.hip): the rows one frame may hold, and the bits of its status word
 MAX_HULL_POINTS = 4096  # CAMD_HULL_MAX_POINTS
 STATUS_NO_SAMPLE, STATUS_DEGENERATE, STATUS_OUT_OF_RANGE = 1, 2, 4
+# interpolate_uvzs_rbf (csrc/spline.hip): the rows one frame may hold -- what one workgroup factors -- and its status values
+MAX_SPLINE_POINTS = _native.SPLINE_MAX_POINTS
+SPLINE_NO_SAMPLE, SPLINE_SINGULAR, SPLINE_NON_FINITE = 1, 2, 4
 
 
-def _require_finite(uv, what):
+def _require_finite(uv, what, columns="u, v"):
     """Non-finite coordinates are refused before any kernel is launched (for tensors: one flag read back)."""
     import torch
     ok = bool(np.isfinite(uv).all()) if is_np(uv) else bool(torch.isfinite(uv).all().item())
     if not ok:
-        raise ValueError("%s: u, v must be finite" % what)
+        raise ValueError("%s: %s must be finite" % (what, columns))
 
 
 # ---- a. scatter ------------------------------------------------------------------------------------------------------
@@ -265,9 +269,10 @@ def _fit_plane(lib, uv, z, zname, n):
 
 
 # ---- d'. the plane inside the samples' convex hull -------------------------------------------------------------------
-def _hull_layout(rows, width, counts, what):
+def _hull_layout(rows, width, counts, what, limit=None):
     """(flat rows (N, width), frame lengths, batched) of the three ways the rows are given: (n, width) one frame,
-    (f, n, width) a batch, ragged (N, width) with ``counts``.  Refuses everything else; nothing touches the device."""
+    (f, n, width) a batch, ragged (N, width) with ``counts``.  Refuses everything else; nothing touches the device.
+    ``limit``: (rows a frame may hold, that constant's name, advice for the message) where they are not the hull's."""
     check_array(rows, what)
     shape = tuple(int(s) for s in rows.shape)
     if counts is not None:
@@ -285,8 +290,9 @@ def _hull_layout(rows, width, counts, what):
         lengths, batched = np.full(shape[0], shape[1], np.int64), True
     else:
         raise ValueError("%s must be (n, %d) or (f, n, %d), got %s" % (what, width, width, shape))
-    if lengths.max() > MAX_HULL_POINTS:
-        raise ValueError("%s: a frame of %d rows, at most MAX_HULL_POINTS = %d are supported" % (what, lengths.max(), MAX_HULL_POINTS))
+    cap, cap_name, advice = limit or (MAX_HULL_POINTS, "MAX_HULL_POINTS", "")
+    if lengths.max() > cap:
+        raise ValueError("%s: a frame of %d rows, at most %s = %d are supported%s" % (what, lengths.max(), cap_name, cap, advice))
     return rows.reshape(-1, width), lengths, batched
 
 
@@ -564,6 +570,238 @@ def interpolate_sparse2d_in_hull(sparse2d, reciprocal=False):
     if int(uvzs.shape[0]) > MAX_HULL_POINTS:
         raise ValueError("sparse2d holds %d samples, at most MAX_HULL_POINTS = %d are supported" % (uvzs.shape[0], MAX_HULL_POINTS))
     return to_caller(interpolate_uvzs_in_hull(uvzs, hw, reciprocal=reciprocal), was_np)
+
+
+# ---- d3. the thin-plate spline through the samples (csrc/spline.hip) ---------------------------------------------------
+_SPLINE_LIMIT = (MAX_SPLINE_POINTS, "MAX_SPLINE_POINTS",
+                 " (one workgroup factors a frame's matrix): thin the samples first, e.g. scatter them through uvzs_to_arr2d "
+                 "on a coarser grid and take arr2d_to_uvzs of that")
+
+
+def _spline_start(lengths, device):
+    import torch
+    return torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(device)
+
+
+def _spline_smooth(smooth):
+    smooth = float(smooth)
+    if smooth != smooth:
+        raise ValueError("smooth must be a number, got nan")
+    return smooth
+
+
+def _spline_rows(rows, counts, what, least):
+    """``_hull_layout`` of rows (.., >= least) under the spline's limit, and their width."""
+    check_array(rows, what)
+    width = int(rows.shape[-1]) if len(rows.shape) >= 2 else 0
+    if width < least:
+        raise ValueError("%s must be (n, >= %d) or (f, n, >= %d), got %s" % (what, least, least, tuple(rows.shape)))
+    return _hull_layout(rows, width, counts, what, _SPLINE_LIMIT) + (width,)
+
+
+def _check_spline_mask(mask, frames, hw, batched):
+    if mask is None:
+        return
+    check_array(mask, "mask")
+    if tuple(mask.shape) != tuple(hw) and not (batched and tuple(mask.shape) == (frames,) + tuple(hw)):
+        raise ValueError("mask must be %s%s, got %s" % (tuple(hw), " or %s" % ((frames,) + tuple(hw),) if batched else "",
+                                                       tuple(mask.shape)))
+
+
+def _spline_eval(rows, width, lengths, cap, weights, mask, hw, grid_step):
+    """``camd_spline_eval`` -> float64 (frames, h, w); ``mask`` checked by ``_check_spline_mask``: (h, w) is every frame's."""
+    import torch
+    frames, dev = len(lengths), rows.device
+    m = None
+    if mask is not None:
+        m = (to_device(mask, device=dev) != 0).view(torch.uint8)
+        if m.dim() == 2:
+            m = m[None].expand(frames, -1, -1)
+        m = m.contiguous()
+    out = torch.empty((frames,) + tuple(hw), dtype=torch.float64, device=dev)
+    call("camd_spline_eval", dev, rows.data_ptr(), width, int(rows.shape[0]), _spline_start(lengths, dev).data_ptr(), frames, cap,
+         weights.data_ptr(), None if m is None else m.data_ptr(), hw[1], hw[0], grid_step, out.data_ptr(), what="spline_eval")
+    return out
+
+
+def spline_assemble(uvzs, smooth=0.5, counts=None):
+    """Stage 1 of ``interpolate_uvzs_rbf``: float64 A = Phi - smooth I; (n, n) for (n, >= 2) rows, (f, c, c) with c the
+    longest frame for a batch (f, n, >= 2) or ragged rows with ``counts`` -- a shorter frame fills its leading block, the
+    rest is 0.  Phi[i][j] = r^2 log r of the distance r between rows i and j, 0 at r = 0; symmetric bit for bit."""
+    import torch
+    flat, lengths, batched, width = _spline_rows(uvzs, counts, "uvzs", 2)
+    smooth = _spline_smooth(smooth)
+    was_np = is_np(uvzs)
+    _require_finite(flat[:, :2], "spline_assemble")
+    frames, cap = len(lengths), max(1, int(lengths.max()))
+    rows = to_device(flat, dtype="float64", cast=True)
+    A = torch.zeros((frames, cap, cap), dtype=torch.float64, device=rows.device)
+    call("camd_spline_assemble", rows.device, rows.data_ptr(), width, int(rows.shape[0]),
+         _spline_start(lengths, rows.device).data_ptr(), frames, cap, smooth, A.data_ptr(), what="spline_assemble")
+    return to_caller(A if batched else A[0, :int(lengths[0]), :int(lengths[0])], was_np)
+
+
+def spline_solve(A, z, counts=None):
+    """Stage 2: ``(weights, status)`` of A w = z by LU with partial pivoting (the largest |a|, of equal ones the lowest row),
+    one workgroup per frame.  A (n, n) with z (n,) -> weights (n,) and a scalar status; A (f, c, c) with z (f, c), or with
+    ragged z (N,) and ``counts`` (frame f is the leading counts[f] block) -> weights (f, c), 0 beyond a frame's rows, and
+    status (f,) int32: 0, ``SPLINE_NO_SAMPLE``, ``SPLINE_SINGULAR`` (a zero or non-finite pivot) or ``SPLINE_NON_FINITE``
+    (in A or z); the last two leave NaN weights.  ``A`` is left as it was: the kernel factors a copy in place."""
+    import torch
+    check_array(A, "A")
+    check_array(z, "z")
+    shape = tuple(int(v) for v in A.shape)
+    if len(shape) == 2 and shape[0] == shape[1] and shape[0] >= 1 and counts is None:
+        batched, cap, lengths = False, shape[0], np.array([shape[0]], np.int64)
+        ok = tuple(z.shape) == (shape[0],)
+    elif len(shape) == 3 and shape[1] == shape[2] and shape[0] >= 1 and shape[1] >= 1:
+        batched, cap = True, shape[1]
+        if counts is None:
+            lengths, ok = np.full(shape[0], cap, np.int64), tuple(z.shape) == shape[:2]
+        else:
+            lengths = np.asarray(counts)
+            if lengths.ndim != 1 or lengths.dtype.kind not in "iu" or len(lengths) != shape[0] or (lengths < 0).any():
+                raise ValueError("counts must hold one non-negative integer per frame of A (%d)" % shape[0])
+            lengths = lengths.astype(np.int64)
+            ok = tuple(z.shape) == (int(lengths.sum()),) and lengths.max() <= cap
+    else:
+        raise ValueError("A must be (n, n) or (f, c, c) with n, f, c >= 1, got %s" % (shape,))
+    if not ok:
+        raise ValueError("z %s does not go with A %s%s" % (tuple(z.shape), shape, "" if counts is None else " and counts"))
+    if cap > MAX_SPLINE_POINTS:
+        raise ValueError("A: a frame of %d rows, at most %s = %d are supported%s" % (cap, _SPLINE_LIMIT[1], MAX_SPLINE_POINTS, _SPLINE_LIMIT[2]))
+    was_np, frames = is_np(A), len(lengths)
+    work = to_device(A, dtype="float64", cast=True)
+    if not was_np and work.data_ptr() == A.data_ptr():
+        work = work.clone()
+    rhs = to_device(z, dtype="float64", cast=True, device=work.device).reshape(-1)
+    weights = torch.zeros((frames, cap), dtype=torch.float64, device=work.device)
+    status = torch.empty(frames, dtype=torch.int32, device=work.device)
+    call("camd_spline_solve", work.device, rhs.data_ptr(), 1, int(rhs.shape[0]), _spline_start(lengths, work.device).data_ptr(), frames,
+         cap, work.data_ptr(), weights.data_ptr(), status.data_ptr(), what="spline_solve")
+    return to_caller((weights, status) if batched else (weights[0], status[0]), was_np)
+
+
+def spline_eval(uvs, weights, hw, counts=None, mask=None, grid_step=1):
+    """Stage 3: float64 (h, w) -- (f, h, w) of a batch -- with pixel (x, y) = sum_i w_i phi(|(x, y) * grid_step - (u_i, v_i)|),
+    added in row order.  ``uvs`` as ``spline_assemble`` takes them; ``weights`` (n,), of a batch (f, c) with c at least the
+    longest frame, as ``spline_solve`` returns them.  ``mask`` (h, w), or (f, h, w) of a batch: where it is 0 the pixel is 0
+    and costs nothing.  ``grid_step`` s: ``hw`` is a coarse image whose pixel (x, y) stands at (x s, y s) of the samples'
+    frame."""
+    import torch
+    flat, lengths, batched, width = _spline_rows(uvs, counts, "uvs", 2)
+    check_array(weights, "weights")
+    frames, longest = len(lengths), int(lengths.max())
+    wshape = tuple(int(v) for v in weights.shape)
+    if not ((batched and len(wshape) == 2 and wshape[0] == frames and wshape[1] >= max(1, longest)) or
+            (not batched and wshape == (longest,))):
+        raise ValueError("weights %s do not go with %d frame(s) of at most %d rows" % (wshape, frames, longest))
+    h, w = positive_hw(hw)
+    grid_step = int(grid_step)
+    if grid_step < 1 or h * grid_step >= 2 ** 31 or w * grid_step >= 2 ** 31:
+        raise ValueError("grid_step must be a positive integer with hw * grid_step below 2**31, got %r" % (grid_step,))
+    _check_spline_mask(mask, frames, (h, w), batched)
+    was_np = is_np(uvs)
+    _require_finite(flat[:, :2], "spline_eval")
+    rows = to_device(flat, dtype="float64", cast=True)
+    if longest == 0 and not batched:
+        wt = torch.zeros((1, 1), dtype=torch.float64, device=rows.device)
+    else:
+        wt = to_device(weights, dtype="float64", cast=True, device=rows.device).reshape(frames, -1)
+    out = _spline_eval(rows, width, lengths, int(wt.shape[1]), wt, mask, (h, w), grid_step)
+    return to_caller(out if batched else out[0], was_np)
+
+
+def interpolate_uvzs_rbf(uvzs, hw=None, smooth=0.5, counts=None, mask=None, return_info=False):
+    """The reference's ``interpolate_uvzs(uvzs, hw, inter_type="rbf")`` (utils.py:373-388), i.e.
+    ``scipy.interpolate.Rbf(u, v, z, function="thin_plate", smooth=smooth)`` at every pixel, under a name of its own
+    (``interpolate_uvzs(inter_type="rbf")`` keeps raising): float64 (h, w) for (n, 3) rows, (f, h, w) for a batch (f, n, 3)
+    or ragged rows (N, 3) with ``counts``.  NumPy in -> NumPy out, CUDA in -> CUDA out.
+
+    With phi(r) = r^2 log r, phi(0) = 0: A = Phi - smooth I over the samples' distances, A w = z by LU with partial
+    pivoting, pixel (x, y) = sum_i w_i phi(|(x, y) - (u_i, v_i)|) in row order (``spline_assemble`` / ``spline_solve`` /
+    ``spline_eval``, one kernel each).  A frame gets the same bits alone and anywhere in a batch.  At most
+    ``MAX_SPLINE_POINTS`` rows per frame: more are refused before the device is touched -- thin them through
+    ``uvzs_to_arr2d`` on a coarser grid.  Non-finite u, v, z are refused.  A frame without rows is zeros.
+    ``hw=None`` -> ``(int(max v) + 2, int(max u) + 2)``, the reference's rule.  ``mask`` (h, w) or (f, h, w): pixels where
+    it is 0 are written 0 and cost nothing; ``convex_hull_mask`` makes the reference's ``constrained_type`` of it.
+
+    ``return_info`` adds ``dict(weights, status)``: status 0, ``SPLINE_NO_SAMPLE`` (1) or ``SPLINE_SINGULAR`` (2: a zero or
+    non-finite pivot, e.g. two rows on one (u, v) at smooth = 0 -- the frame is NaN and is not repaired)."""
+    import torch
+    flat, lengths, batched, _ = _spline_rows(uvzs, counts, "uvzs", 3)
+    if int(flat.shape[1]) != 3:
+        raise ValueError("uvzs must be (n, 3) or (f, n, 3), got %s" % (tuple(uvzs.shape),))
+    smooth = _spline_smooth(smooth)
+    was_np, total = is_np(uvzs), int(flat.shape[0])
+    if hw is None:
+        if total == 0:
+            raise ValueError("hw=None needs at least one sample")
+        m = flat[:, :2].max(0) if was_np else flat[:, :2].max(0).values.cpu().numpy()
+        if not np.isfinite(m).all():
+            raise ValueError("interpolate_uvzs_rbf: u, v, z must be finite")
+        hw = int(m[1]) + 2, int(m[0]) + 2
+    h, w = positive_hw(hw)
+    frames, cap = len(lengths), max(1, int(lengths.max()))
+    _check_spline_mask(mask, frames, (h, w), batched)
+    _require_finite(flat, "interpolate_uvzs_rbf", "u, v, z")
+    rows = to_device(flat, dtype="float64", cast=True)
+    dev, who = rows.device, "interpolate_uvzs_rbf"
+    start = _spline_start(lengths, dev)
+    A = torch.empty((frames, cap, cap), dtype=torch.float64, device=dev)
+    weights = torch.zeros((frames, cap), dtype=torch.float64, device=dev)
+    status = torch.empty(frames, dtype=torch.int32, device=dev)
+    call("camd_spline_assemble", dev, rows.data_ptr(), 3, total, start.data_ptr(), frames, cap, smooth, A.data_ptr(), what=who)
+    call("camd_spline_solve", dev, rows.data_ptr() + 16, 3, total, start.data_ptr(), frames, cap, A.data_ptr(), weights.data_ptr(),
+         status.data_ptr(), what=who)
+    out = _spline_eval(rows, 3, lengths, cap, weights, mask, (h, w), 1)
+    out = to_caller(out if batched else out[0], was_np)
+    if not return_info:
+        return out
+    if not batched:
+        weights, status = weights[0, :int(lengths[0])], status[0]
+    return out, dict(zip(("weights", "status"), to_caller((weights, status), was_np)))
+
+
+def interpolate_sparse2d_rbf(sparse2d, smooth=0.5, mask=None):
+    """``interpolate_uvzs_rbf`` of the non-zero, finite pixels of an (h, w) image (utils.py:347-353 with
+    ``inter_type="rbf"``): float64 (h, w).  More than ``MAX_SPLINE_POINTS`` such pixels are refused."""
+    import torch
+    check_array(sparse2d, "sparse2d")
+    if len(sparse2d.shape) != 2:
+        raise ValueError("sparse2d must be (h, w), got %s" % (tuple(sparse2d.shape),))
+    hw = positive_hw(sparse2d.shape)
+    was_np = is_np(sparse2d)
+    refusal = "sparse2d holds %d samples, at most MAX_SPLINE_POINTS = %d are supported" + _SPLINE_LIMIT[2]
+    if was_np:  # counted on the host: the refusal comes before the device is touched
+        with np.errstate(invalid="ignore"):
+            n = int(np.count_nonzero((sparse2d != 0) & np.isfinite(sparse2d)))
+        if n > MAX_SPLINE_POINTS:
+            raise ValueError(refusal % (n, MAX_SPLINE_POINTS))
+    _check_spline_mask(mask, 1, hw, False)
+    s = to_device(sparse2d)
+    uvzs = arr2d_to_uvzs(s, (s != 0) & torch.isfinite(s))
+    if int(uvzs.shape[0]) > MAX_SPLINE_POINTS:
+        raise ValueError(refusal % (int(uvzs.shape[0]), MAX_SPLINE_POINTS))
+    m = None if mask is None else to_device(mask, device=s.device)
+    return to_caller(interpolate_uvzs_rbf(uvzs, hw, smooth, mask=m), was_np)
+
+
+def spline_upsize(coarse, hw):
+    """``cv2.resize(coarse * hw[1] / coarse.shape[1], hw[::-1], interpolation=INTER_NEAREST)`` of a float64 (h, w) image: the
+    last step of the reference's ``FeatureMatchingAsStereoMatching`` (stereo_matching.py:139-140), kept in float64."""
+    import torch
+    check_array(coarse, "coarse")
+    if len(coarse.shape) != 2 or dtype_name(coarse) != "float64":
+        raise ValueError("coarse must be float64 (h, w), got %s %s" % (dtype_name(coarse), tuple(coarse.shape)))
+    h, w = positive_hw(coarse.shape)
+    oh, ow = positive_hw(hw)
+    if oh > 65535:
+        raise ValueError("images of more than 65535 rows are not supported")
+    src = to_device(coarse)
+    out = torch.empty((oh, ow), dtype=torch.float64, device=src.device)
+    call("camd_spline_upsize", src.device, src.data_ptr(), w, h, 1, out.data_ptr(), ow, oh, what="spline_upsize")
+    return to_caller(out, is_np(coarse))
 
 
 # ---- e. triangulation of matches -------------------------------------------------------------------------------------

@@ -102,15 +102,22 @@ class FeatureMatchingAsStereoMatching(MetaStereoMatching):
 
     ``downscale`` (not in the reference, which hard-codes 8 because its KDTree fill took 44 s at full resolution):
     ``downscale=1`` fills at full resolution.  ``uvs*`` may be NumPy arrays or CUDA tensors; tensors stay on the device
-    and the disparity comes back as a tensor."""
+    and the disparity comes back as a tensor.
+
+    ``inter_type`` (not in the reference either): ``"nearest"`` is the reference's fill; ``"rbf"`` fills the grid with
+    the thin-plate spline ``sparse.interpolate_uvzs_rbf`` -- smooth instead of Voronoi blocks, float64, at most
+    ``sparse.MAX_SPLINE_POINTS`` matches -- and blows it up the same way (``sparse.spline_upsize``)."""
 
     accepts_device_tensors = True
 
-    def __init__(self, feature_matching, downscale=8):
+    def __init__(self, feature_matching, downscale=8, inter_type="nearest"):
         self.feature_matching = feature_matching
         self.downscale = int(downscale)
         if self.downscale < 1:
             raise ValueError("downscale must be a positive integer, got %r" % (downscale,))
+        if inter_type not in ("nearest", "rbf"):
+            raise ValueError('inter_type must be "nearest" or "rbf", got %r' % (inter_type,))
+        self.inter_type = inter_type
 
     def __call__(self, img1, img2):
         from . import sparse
@@ -128,6 +135,11 @@ class FeatureMatchingAsStereoMatching(MetaStereoMatching):
             uvs1 = uvs1.to(torch.float64) * scale  # (float64 like NumPy's float * int tuple)
             uvs2 = torch.as_tensor(uvs2, device=uvs1.device).to(torch.float64) * scale
             uvds = torch.cat((uvs1, (uvs1 - uvs2)[:, :1]), 1)
+        if self.inter_type == "rbf":
+            disparity = sparse.interpolate_uvzs_rbf(uvds, resize_shape)
+            if resize_shape != hw:
+                disparity = sparse.spline_upsize(disparity, hw)
+            return dict(disparity=disparity, matched=matched)
         disparity = sparse.interpolate_uvzs(uvds, resize_shape, constrained_type=None, inter_type="nearest",
                                             resize_hw=hw if resize_shape != hw else None)
         return dict(disparity=disparity, matched=matched)

@@ -1045,6 +1045,42 @@ int camd_nearest_fill_in_hull(const double* sorted_uv, const uint32_t* sorted_id
                               size_t z_stride, int w, int h, double distance, const int* vertices, const int* hull_counts,
                               int vertex_capacity, float* out, void* queue);
 
+/* ---- sparse samples filled by their thin-plate spline, batched over frames (csrc/spline.hip) ----
+ * The device side of the reference's interpolate_uvzs(inter_type="rbf"): scipy.interpolate.Rbf(u, v, z,
+ * function="thin_plate", smooth=s) evaluated at every pixel (utils.py:373-388).  float64 throughout, every product and sum
+ * rounded on its own, in the order given here; tests/spline_ref.py restates each stage.
+ *   phi(dx, dy) = r == 0 ? 0 : (r * r) * log(r)   with r = sqrt(dx * dx + dy * dy)
+ * The frames' rows follow one another in one array; start: frames + 1 int64 ON THE DEVICE, rising, frame f owns rows
+ * start[f] .. start[f + 1].  A range that leaves the rows or is longer than `capacity` is read nowhere and counts as a frame
+ * without rows.  capacity (1 .. CAMD_SPLINE_MAX_POINTS) is the leading dimension of every frame's matrix and weights;
+ * 1 <= frames <= 65535.  A frame's numbers depend on its own rows only.                                                  */
+#define CAMD_SPLINE_MAX_POINTS 1024 /* rows of one frame: what one workgroup factors */
+#define CAMD_SPLINE_NO_SAMPLE 1     /* status: the frame has no row (nothing else is written for it) */
+#define CAMD_SPLINE_SINGULAR 2      /* status: a zero or non-finite pivot; the frame's weights are NaN */
+#define CAMD_SPLINE_NON_FINITE 4    /* status: a non-finite z or matrix entry; the frame's weights are NaN */
+/* 1. A: frames x capacity x capacity; of frame f with n rows the leading n x n are written:
+ *   A[i][j] = A[j][i] = phi(u_i - u_j, v_i - v_j) for j < i (computed once, stored twice),   A[i][i] = 0 - smooth.
+ * uvz: rows of uvz_stride >= 2 doubles, u and v the first two.                                                           */
+int camd_spline_assemble(const double* uvz, int uvz_stride, size_t rows, const long long* start, int frames, int capacity,
+                         double smooth, double* A, void* queue);
+/* 2. A w = z of every frame, one workgroup per frame, A factored IN PLACE (it is destroyed).  z: the frame's right-hand
+ * sides, z_stride doubles apart (uvz + 2 with uvz_stride).  Gaussian elimination with partial pivoting: at step k the pivot
+ * row is the i >= k with the largest |A[i][k]|, of equal ones the lowest; rows k and p are exchanged; for i > k:
+ *   m = A[i][k] / A[k][k],   A[i][j] = A[i][j] - m * A[k][j] (j > k),   b[i] = b[i] - m * b[k]
+ * then, k = n - 1 ... 0:   w[k] = b[k] / A[k][k],   b[i] = b[i] - A[i][k] * w[k] (i < k).
+ * weights: frames x capacity, the first n of a frame are written; status: frames int32, 0 or one CAMD_SPLINE_* value.    */
+int camd_spline_solve(const double* z, int z_stride, size_t rows, const long long* start, int frames, int capacity, double* A,
+                      double* weights, int* status, void* queue);
+/* 3. out: frames x out_h x out_w float64, every pixel written once:
+ *   out[y][x] = sum over i = 0 .. n - 1, in that order, of  w_i * phi(x * grid_step - u_i, y * grid_step - v_i)   (s = s + t)
+ * mask: NULL, or frames x out_h x out_w uint8: where it is 0 the pixel is written 0.0 and nothing is evaluated.          */
+int camd_spline_eval(const double* uvz, int uvz_stride, size_t rows, const long long* start, int frames, int capacity,
+                     const double* weights, const uint8_t* mask, int out_w, int out_h, int grid_step, double* out, void* queue);
+/* out (frames x out_h x out_w) = cv2.resize(INTER_NEAREST) of (src * out_w) / w, src frames x h x w float64: pixel (X, Y)
+ * reads (min(floor(X * ifx), w - 1), min(floor(Y * ify), h - 1)) with ifx = 1 / (out_w / w) -- what the reference's
+ * FeatureMatchingAsStereoMatching does to its coarse disparity (stereo_matching.py:139-140).                             */
+int camd_spline_upsize(const double* src, int w, int h, int frames, double* out, int out_w, int out_h, void* queue);
+
 /* ---- the essential matrix of matched pixels by RANSAC over 8-point samples (csrc/essential.hip) ----
  * The device side of epipolar_geometry.find_essential_matrix.  A contract of this library's OWN: cv2.findEssentialMat is
  * not restated (UNPINNED); tests/essential_ref.py restates every stage in NumPy, bit for bit.
