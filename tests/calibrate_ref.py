@@ -33,9 +33,9 @@ def free_mask(flags):
     return m
 
 
-def homography(obj, uv, plane):
+def homography(obj, uv, plane, null="eigh"):
     """plane coordinates (the object points turned by ``plane``, x and y) -> raw pixels, as the kernel forms it"""
-    return pnp_ref.normalised_dlt((obj @ plane.T)[:, :2], uv)
+    return pnp_ref.normalised_dlt((obj @ plane.T)[:, :2], uv, null)
 
 
 def initial_camera_matrix(Hs, xy):
